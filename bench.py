@@ -10,10 +10,16 @@ all-gather + merge.  `config.inner_sequence_ms_per_step` is the kernel sequence 
 the timed region starts.  With --gpus N the index is row-sharded N ways (one process per GPU, RCCL);
 total work is fixed, so scaling is "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--queries Q] [--topk k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--queries Q] [--topk k] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the scan launch over the
-last, largest row segment), timed with hipEvents on the launch stream inside the library;
+Prints ONE JSON line (rank 0).  A plain run builds the index, runs W warm-up and K timed steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step) with the static `config` of the workload.
+--dump-outputs DIR writes what the last timed step returned -- `scores.npy` (fp16 scores as float32, [Q, k]) and `doc_ids.npy` (int32 doc
+ids as float64, [Q, k]) -- from seeded inputs that are the same on every run with the same arguments.
+
+Everything below is measured only with --full (after the timed steps, in this order).  `config` gains the result digest, the unproven
+query count, `inner_sequence_ms_per_step` and (N > 1) `allgather_plus_merge_ms`.  `roofline` is for the dominant kernel (the scan launch
+over the last, largest row segment), timed with hipEvents on the launch stream inside the library during the timed steps;
 `cpu_baseline` times the oracle's CPU port (fp32-accumulate GEMM + top-k, all host cores) on a
 bounded row sample (rank 0, N = 1 only).
 
@@ -50,6 +56,11 @@ def parse():
     ap.add_argument("--rows", type=int, default=N_ROWS_FULL)
     ap.add_argument("--queries", type=int, default=512)
     ap.add_argument("--topk", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/scores.npy (float32) and DIR/doc_ids.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: rooflines, CPU baselines, the clustered leg, e2e and e2e_k100 "
+                         "(the --no-* switches below only apply with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-e2e", action="store_true", help="MIPS half only")
@@ -218,6 +229,21 @@ def cpu_baseline(args, queries_cpu):
                          ", ".join("%d -> %.2f s" % kv for kv in sorted(sweep.items())), cores, args.rows)}
 
 
+def dump_outputs(out_dir, dist, idx):
+    """What the timed call returned in its last step: scores fp16 [Q, k] as float32, doc ids int32 [Q, k] as float64 (both exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), dist.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "doc_ids.npy"), idx.detach().cpu().numpy().astype(np.float64))
+
+
+def headline(args, world, elapsed, config):
+    """The result line's headline fields: queries/s of the timed steps and the milliseconds one timed step took (slowest rank)."""
+    return {"metric": "mips_queries_per_sec", "value": args.queries * args.steps / elapsed, "unit": "queries/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f16",
+            "data": "synthetic", "config": config}
+
+
 def main():
     args = parse()
     from emdr2_amd import dist_util
@@ -237,7 +263,8 @@ def main():
     queries = torch.randn((args.queries, DIM), generator=gq, device="cuda", dtype=torch.float32).to(torch.float16)
     nq, k = args.queries, args.topk
 
-    index.exchange_events = [] if world > 1 else None      # (start, end) hipEvent pairs around all-gather + merge, recorded by the index
+    # (start, end) hipEvent pairs around all-gather + merge, recorded by the index (--full only)
+    index.exchange_events = [] if world > 1 and args.full else None
 
     def step():
         # the plug-in operator itself: fp16 check, shard search, host read of the proof flags (+ all-exact path for flagged queries),
@@ -253,13 +280,34 @@ def main():
     for _ in range(args.warmup):
         out = step()
     fence()
-    lib.emdr2_mips_set_timing(1)
+    if args.full:
+        lib.emdr2_mips_set_timing(1)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                     # every rank holds the same merged result
+        dump_outputs(args.dump_outputs, out[0], out[1])
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    config = {"workload": "BASELINE configs[1]: MIPS-only top-%d, %d queries/search over a %d x %d fp16 index resident in HBM"
+                          % (k, nq, args.rows, DIM),
+              "rows": args.rows, "dim": DIM, "queries_per_step": nq, "top_k": k,
+              "parallelism": "index row-sharded x%d, all-gather(top-k) + merge" % world,
+              "cus": int(lib.emdr2_device_cu_count()),
+              "timed_call": "DistributedBruteForceIndex.search_mips_index (flag read + exact fallback + exchange included)",
+              "rows_per_rank": [b - a for a, b in shard_bounds(args.rows, world)],
+              "allgather_bytes_per_rank": (nq * k * 16) if world > 1 else 0}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, elapsed, config)), flush=True)
+        dist_util.shutdown()
+        return
+
     digest = result_digest(out[0], out[1])
     digests_agree = None
     if world > 1:                                           # every rank must hold the same merged result
@@ -308,11 +356,6 @@ def main():
         hbm_regime = {"queries": 64, "bound": "hbm", "achieved": gb64, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                       "frac": gb64 / HBM_PEAK_GBPS, "kernel_ms": ms64, "rows_per_launch": int(big64)}
 
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-
     exchange_ms = None
     if world > 1 and index.exchange_events:
         timed = index.exchange_events[-args.steps:]
@@ -320,7 +363,6 @@ def main():
     index.exchange_events = None
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
         flops = 2.0 * nq * big * DIM
         bytes_alg = float(big) * DIM * 2
         tflops = flops / (dom_ms * 1e-3) / 1e12
@@ -349,27 +391,15 @@ def main():
                 roofline["traffic"] = pj["traffic_bytes"]
                 roofline["traffic_source"] = ("profiles/r06_mips_summary.json, same library (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE; L2->fabric requests, "
                                               "Infinity-Cache hits included)")
-        result = {
-            "metric": "mips_queries_per_sec", "value": nq * args.steps / elapsed, "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f16",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: MIPS-only top-%d, %d queries/search over a %d x %d fp16 index resident in HBM"
-                                   % (k, nq, args.rows, DIM),
-                       "rows": args.rows, "dim": DIM, "queries_per_step": nq, "top_k": k,
-                       "parallelism": "index row-sharded x%d, all-gather(top-k) + merge" % world,
-                       "cus": int(lib.emdr2_device_cu_count()), "unproven_queries": flags_total,
+        config.update({"unproven_queries": flags_total,
                        # scores + doc ids of all queries of the last timed search: equal for any number of shards / ranks
                        "result_sha256": digest, "result_identical_on_all_ranks": digests_agree,
-                       "timed_call": "DistributedBruteForceIndex.search_mips_index (flag read + exact fallback + exchange included)",
                        "inner_sequence_ms_per_step": inner_ms,
-                       # what makes the 1 -> N curve interpretable: rows scanned per rank, bytes every rank contributes to the ONE
-                       # all-gather of a search, and the time from the all-gather to the merged result (rank 0, hipEvents)
-                       "rows_per_rank": [b - a for a, b in shard_bounds(args.rows, world)],
-                       "allgather_bytes_per_rank": (nq * k * 16) if world > 1 else 0,
-                       "allgather_plus_merge_ms": exchange_ms},
-            "roofline": roofline,
-        }
+                       # what makes the 1 -> N curve interpretable (with rows_per_rank and allgather_bytes_per_rank): the time from the
+                       # all-gather to the merged result (rank 0, hipEvents)
+                       "allgather_plus_merge_ms": exchange_ms})
+        result = headline(args, world, elapsed, config)
+        result["roofline"] = roofline
         if hbm_regime is not None:
             result["roofline_hbm_regime"] = hbm_regime
         if world == 1 and not args.no_cpu_baseline:

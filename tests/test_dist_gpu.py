@@ -129,7 +129,7 @@ def test_bench_under_the_drivers_launcher_is_not_launched_twice():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "1000000", "--no-e2e", "--no-cpu-baseline"]
+           "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "1000000", "--full", "--no-e2e", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -146,7 +146,7 @@ def _plain_bench(extra_env=None, extra_args=()):
     env = dict(os.environ, EMDR2_SINGLE_DEVICE="1", EMDR2_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "2000000", "--e2e-steps", "1", "--e2e-warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--rows", "2000000", "--e2e-steps", "1", "--e2e-warmup", "1",
            "--batch", "4", "--layers", "2", "--keep-last-layers", "0", "--no-cpu-baseline"] + list(extra_args)
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]

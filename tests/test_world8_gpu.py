@@ -41,13 +41,13 @@ def _one_line(cmd, env, timeout):
 
 
 def test_plain_bench_command_with_eight_ranks_full_index_full_depth_and_an_injected_allocation_failure():
-    """configs[3] dry: `python bench.py --gpus 8 --rows 21015324 --queries 512 --no-e2e-k100` (+ the per-rank batch that fits eight ranks on
+    """configs[3] dry: `python bench.py --gpus 8 --full --rows 21015324 --queries 512 --no-e2e-k100` (+ the per-rank batch that fits eight ranks on
     one GPU).  (1) MIPS half: N/8 row shards, ONE 16-byte-record all-gather, merged top-50 of all 512 queries bit-identical on the eight ranks
     and to a SINGLE-shard search of the same 21M rows (digest over scores + doc ids); nothing unproven.  (2) e2e half: 12 layers x 4
     stacks, K = 50, question groups with nothing recomputed, rank 5 hits an (injected) allocation failure in its FIRST step between a
     group's forward and backward: all eight give the step up together, re-run it, and after the timed steps hold bit-identical parameters."""
     import torch
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--rows", str(ROWS), "--queries", "512", "--no-e2e-k100", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "8", "--full", "--rows", str(ROWS), "--queries", "512", "--no-e2e-k100", "--steps", "2", "--warmup", "1",
            "--batch", "8", "--micro-batches", "8", "--e2e-steps", "2", "--e2e-warmup", "1", "--no-cpu-baseline", "--e2e-timeout", "900"]
     r = _one_line(cmd, _env({"EMDR2_BENCH_INJECT_OOM": "5,1"}), timeout=1500)
     from emdr2_amd.data.emdr2_index import shard_bounds

@@ -3,7 +3,7 @@
 # usage: tools/bench_ab.sh "ENV1=a ENV2=b" "ENV1=c" ...   (each arg = one env setting string)
 cd "${GRAFT_REPO_ROOT:-.}"
 for cfg in "$@"; do
-  env $cfg python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1 > /tmp/_b.json
+  env $cfg python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1 > /tmp/_b.json
   python - "$cfg" <<'PY'
 import json,sys
 d=json.load(open('/tmp/_b.json')); r=d['roofline']

@@ -22,6 +22,7 @@ def synth_rows(lo, hi, seed=1234):
 
 
 bench.synth_rows = synth_rows
-if "--no-e2e" not in sys.argv:
-    sys.argv.append("--no-e2e")
+for flag in ("--full", "--no-e2e"):                 # the whole MIPS half as before --full existed, without the e2e legs
+    if flag not in sys.argv:
+        sys.argv.append(flag)
 bench.main()

@@ -16,7 +16,7 @@ for a in 0 4 3 1 2; do
 done
 echo "== production library (no switches)" >> $O/ablation.txt
 python tools/scan_launches.py $ROWS 512 >> $O/ablation.txt 2>&1
-bash tools/power_probe.sh mips_q512 python bench.py --steps 60 --warmup 2 --no-e2e --no-cpu-baseline > $O/power_mips_q512.txt 2>&1
+bash tools/power_probe.sh mips_q512 python bench.py --full --steps 60 --warmup 2 --no-e2e --no-cpu-baseline > $O/power_mips_q512.txt 2>&1
 cp gpurun_out/power_mips_q512.txt $O/power_mips_q512_samples.txt; tail -1 gpurun_out/power_mips_q512_cmd.txt > $O/power_mips_q512_bench_line.json
 bash tools/power_probe.sh gemm_nt python tools/gemm_loop.py 768 3072 > $O/power_gemm_nt.txt 2>&1
 cp gpurun_out/power_gemm_nt.txt $O/power_gemm_nt_samples.txt; tail -3 gpurun_out/power_gemm_nt_cmd.txt > $O/power_gemm_nt_cmd_tail.txt

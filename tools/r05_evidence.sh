@@ -22,15 +22,15 @@ if [ "$1" != "quick" ]; then
   cp $O/mips_summary.json $R/profiles/r05_mips_summary.json
 fi
 # (2) the benchmark line (both halves + the k = 100 and clustered legs), the N/8-shard search, kernel timelines, attention shapes
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --rows 2626916 --no-e2e --no-cpu-baseline --no-clustered > $O/bench_shard.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --rows 2626916 --no-e2e --no-cpu-baseline --no-clustered > $O/bench_shard.json 2>> $O/bench.err
 python tools/mips_timeline.py 2626916 512 50 > $O/mips_timeline_shard.txt 2>&1
 python tools/mips_timeline.py 21015324 512 50 > $O/mips_timeline_full.txt 2>&1
 python tools/attn_varlen_bench.py > $O/attn_varlen.txt 2>&1
 python tools/attn_cross_bench.py > $O/attn_cross.txt 2>&1
 if [ "$1" != "quick" ]; then
   python tools/attn_bench.py 800 512 0.1 0 > $O/attn_dense.txt 2>&1
-  ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/r05_stats; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_stats -- python $R/bench.py --no-cpu-baseline --no-clustered --no-e2e-k100 > $O/bench_profiled.json 2> $O/bench_profiled.err; cp $(ls /tmp/r05_stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv )
+  ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/r05_stats; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_stats -- python $R/bench.py --full --no-cpu-baseline --no-clustered --no-e2e-k100 > $O/bench_profiled.json 2> $O/bench_profiled.err; cp $(ls /tmp/r05_stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv )
 fi
 rm -rf $R/gpurun_out/pmc_scan8_p? $R/gpurun_out/pmc_gemm5_p? $R/gpurun_out/pmc_calib_p?
 ls -la $O

@@ -22,18 +22,18 @@ if [ "$1" != "quick" ]; then
   cp $O/mips_summary.json $R/profiles/r06_mips_summary.json
 fi
 # (2) the benchmark line (both halves + the k = 100 and clustered legs), the N/8-shard search, kernel timelines, attention shapes
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --rows 2626916 --no-e2e --no-cpu-baseline --no-clustered > $O/bench_shard.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --rows 2626916 --no-e2e --no-cpu-baseline --no-clustered > $O/bench_shard.json 2>> $O/bench.err
 python tools/mips_timeline.py 2626916 512 50 > $O/mips_timeline_shard.txt 2>&1
 python tools/mips_timeline.py 21015324 512 50 > $O/mips_timeline_full.txt 2>&1
 python tools/attn_varlen_bench.py > $O/attn_varlen.txt 2>&1
 python tools/attn_cross_bench.py > $O/attn_cross.txt 2>&1
 if [ "$1" != "quick" ]; then
   python tools/attn_bench.py 800 512 0.1 0 > $O/attn_dense.txt 2>&1
-  ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/r06_stats; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_stats -- python $R/bench.py --no-cpu-baseline --no-clustered --no-e2e-k100 > $O/bench_profiled.json 2> $O/bench_profiled.err; cp $(ls /tmp/r06_stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv )
+  ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/r06_stats; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_stats -- python $R/bench.py --full --no-cpu-baseline --no-clustered --no-e2e-k100 > $O/bench_profiled.json 2> $O/bench_profiled.err; cp $(ls /tmp/r06_stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv )
 fi
 # (3) round 6: the 8-rank dry runs of configs[3] / [4] on this one GPU (gloo), the planted task, the fp32 validation mode, the dQ-atomics probe
-EMDR2_SINGLE_DEVICE=1 EMDR2_DIST_BACKEND=gloo python bench.py --gpus 8 --rows 21015324 --queries 512 --no-e2e-k100 --steps 5 --warmup 2 --batch 8 --micro-batches 8 --e2e-steps 3 --e2e-warmup 1 --no-cpu-baseline > $O/bench_world8_gloo.json 2> $O/bench_world8_gloo.err
+EMDR2_SINGLE_DEVICE=1 EMDR2_DIST_BACKEND=gloo python bench.py --gpus 8 --full --rows 21015324 --queries 512 --no-e2e-k100 --steps 5 --warmup 2 --batch 8 --micro-batches 8 --e2e-steps 3 --e2e-warmup 1 --no-cpu-baseline > $O/bench_world8_gloo.json 2> $O/bench_world8_gloo.err
 python tools/planted_task.py /tmp/planted_r06 --steps 300 --both 2> /dev/null | grep "^{" > $O/planted_task.jsonl
 python -m pytest tests/test_parity_fp32_gpu.py -q -s 2>&1 | grep "fp32 parity\|passed\|failed" > $O/fp32_parity.txt
 /opt/rocm/bin/hipcc -O3 -munsafe-fp-atomics --offload-arch=gfx950 tools/atomic_dq_probe.hip -o tools/atomic_dq_probe > /dev/null 2>&1 && tools/atomic_dq_probe 3 > $O/atomic_dq_probe.txt 2>&1
