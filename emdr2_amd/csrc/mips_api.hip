@@ -56,6 +56,14 @@ size_t carve(char *base, int dim, Workspace *w)
     return off;
 }
 
+// int8 shadow image of a shard (mips_scan8i.hip): filter segments of at least `min_rows` rows that the persistent fp16 scan would take run on it
+struct Shadow {
+    const void *image;
+    const float *table;
+    int64_t min_rows;
+};
+long g_shadow_launches = 0;
+
 bool bad_shape(int64_t n_rows, int dim) { return n_rows < 0 || n_rows >= ((int64_t)1 << 31) - 1024 || dim < 64 || dim > 8192 || (dim % 32) != 0; }
 
 } // namespace
@@ -124,7 +132,7 @@ static const int kBN[3] = {512, 256, 128};
 static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq,
                        const void *queries, int n_q, int k, const int32_t *ids, void *out_dist, int32_t *out_idx,
                        int64_t *out_row, uint32_t *out_flags, void *workspace, size_t workspace_bytes,
-                       emdr2_stream_t stream_, int f32, uint4 *out_rec = nullptr)
+                       emdr2_stream_t stream_, int f32, uint4 *out_rec = nullptr, const Shadow *shadow = nullptr)
 {
     if (!tiled || !emax_sq || !queries || !out_flags || !workspace) return EMDR2_E_BADARG;
     if (!out_rec && (!out_dist || !out_idx || !out_row)) return EMDR2_E_BADARG;
@@ -136,7 +144,8 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
     const int kp = k <= 56 ? 64 : 128;
     const int seg0 = env_int("EMDR2_MIPS_SEG0", 8192) / 512 * 512;
     const int growth = env_int("EMDR2_MIPS_GROWTH", 8);    // r04: 8 (was 16): with cheaper selects a tighter threshold for the next segment pays (tools/mips_timeline.py)
-    if (seg0 < 512 || seg0 > (int)CAPQ - 512 || growth < 2) return EMDR2_E_BADARG;
+    const int growth_i8 = env_int("EMDR2_MIPS_GROWTH_I8", 2); // ... of the segments that run on the int8 shadow image
+    if (seg0 < 512 || seg0 > (int)CAPQ - 512 || growth < 2 || growth_i8 < 2) return EMDR2_E_BADARG;
     const int force_variant = env_int("EMDR2_MIPS_VARIANT", -1);
     const int cus = env_int("EMDR2_MIPS_GRID", cu_count());
     const int scan_kernel = env_int("EMDR2_MIPS_KERNEL", 1); // 1 = lockstep v1, 2 = ping-pong
@@ -176,10 +185,15 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         sp.tune = env_int("EMDR2_MIPS_TUNE", 17);
         sp.trace = (unsigned long long *)w.cand + (size_t)511 * CAPQ; // scratch tail of the candidate area (ABL 9 only)
 
-        int scan8_launches = 0;
+        int scan8_launches = 0;                              // (fp16 and int8 launches share the progress counters zeroed above: both count)
+        // the int8 query image and the per-query constants live where the fragment-tiled query image of the experiment kernels would
+        // (half its size + 8 KiB); packed only if some segment of this search can take the int8 path
+        const bool shadow_ok = shadow && variant <= 1 && scan_kernel == 1 && (dim % 256) == 0 && n_rows - dense_rows >= shadow->min_rows;
+        char *const q8_tiled = w.q_frag;
+        float *const qc = (float *)(w.q_frag + (size_t)(dim / 64) * 512 * 64);
+        if (shadow_ok && (rc = mips_launch_pack_queries_i8(qp, nqp, dim, BN, q8_tiled, qc, stream))) return rc;
         const bool couple = EXP_MIPS_COUPLE();
         int64_t done = 0, seg_end = dense_rows;
-        int64_t next_boundary = (int64_t)seg0 * growth;
         int mode = 1;
         while (done < n_rows) {
             sp.tile_begin = (int)(done / BM);
@@ -196,12 +210,17 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
                 }
                 if (hipEventRecord(g_timing.ev[2 * g_timing.n], stream) != hipSuccess) return EMDR2_E_LAUNCH;
             }
+            bool int8_segment = false;
             EXP_MIPS_SCAN_VARIANT(mode, variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc)
             {
                 rc = -4;
                 if (mode == 0 && variant <= 1 && scan_kernel == 1) {
                     unsigned *prog = (couple && scan8_launches < 8) ? prog0 + (size_t)SCAN8_PROG_UINTS * scan8_launches : nullptr;
-                    rc = mips_launch_scan8(sp, BN, done, seg_end, cus, prog, stream);
+                    if (shadow_ok && seg_end - done >= shadow->min_rows) {
+                        rc = mips_launch_scan8i(sp, shadow->image, shadow->table, q8_tiled, qc, BN, done, seg_end, cus, prog, stream);
+                        if (rc == 0) { int8_segment = true; ++g_shadow_launches; }
+                    }
+                    if (rc == -4) rc = mips_launch_scan8(sp, BN, done, seg_end, cus, prog, stream);
                     if (rc == 0) ++scan8_launches;
                 }
                 if (rc == -4) rc = mips_launch_scan(variant, mode, sp, grid, stream);
@@ -212,12 +231,16 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
                 g_timing.rows[g_timing.n] = seg_end - done;
                 ++g_timing.n;
             }
+            // survivors of an int8 segment carry integer sums: they get their fp32 scores before the select (or the finalize) reads them
+            if (int8_segment && (rc = mips_launch_rescore(sp, qp, (unsigned)kp, stream))) return rc;
             // (the select after the LAST segment runs inside the finalize launch)
             if (seg_end < n_rows && (rc = mips_launch_select(w.cand, w.count, w.cand8, count8, w.tau, out_flags + q0, CAPQ, kp, nqp, stream))) return rc;
             done = seg_end;
+            // the next segment ends at `growth` times the rows done so far -- at `growth_i8` times once a segment of that length runs on the int8
+            // image: its survivors are ~6 x the fp16 filter's and each costs a 1.5 KB gather in the re-score, so a fresher threshold pays there
+            const int64_t next_boundary = done * ((shadow_ok && done * (growth_i8 - 1) >= shadow->min_rows) ? growth_i8 : growth);
             seg_end = next_boundary < n_rows ? next_boundary : n_rows;
             if (n_rows - seg_end < seg_end / 2) seg_end = n_rows; // do not leave a short tail for a last launch (a launch + a select cost ~70 us)
-            next_boundary *= growth;
             mode = 0;
         }
 
@@ -276,6 +299,34 @@ int emdr2_mips_search_records(const void *tiled, int64_t n_rows, int dim, int64_
     return search_impl(tiled, n_rows, dim, row_base, emax_sq, queries, n_q, k, ids, nullptr, nullptr, nullptr, out_flags, workspace,
                        workspace_bytes, stream, f32 ? 1 : 0, (uint4 *)out_records);
 }
+
+int emdr2_mips_shadow_bytes(int64_t n_rows, int dim, size_t *image_bytes, size_t *table_bytes)
+{
+    if (!image_bytes || !table_bytes || bad_shape(n_rows, dim) || (dim % 256) != 0) return EMDR2_E_BADARG;
+    const int64_t padded = (n_rows + 511) / 512 * 512;
+    *image_bytes = (size_t)padded * dim;
+    *table_bytes = (size_t)(padded / 256) * 4 * sizeof(float);
+    return EMDR2_OK;
+}
+
+int emdr2_mips_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream)
+{
+    if (!tiled || !shadow || !table || !nonfinite || ((uintptr_t)table & 15) || bad_shape(n_rows, dim) || (dim % 256) != 0) return EMDR2_E_BADARG;
+    return mips_launch_seal_shadow(tiled, n_rows, dim, shadow, (float *)table, nonfinite, (hipStream_t)stream);
+}
+
+int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const void *shadow,
+                             const void *table, int64_t shadow_min_rows, const void *queries, int n_q, int k, const int32_t *ids, int f32,
+                             void *out_dist, int32_t *out_idx, int64_t *out_row, void *out_records, uint32_t *out_flags, void *workspace,
+                             size_t workspace_bytes, emdr2_stream_t stream)
+{
+    if (!shadow || !table || ((uintptr_t)table & 15) || shadow_min_rows < 1 || (dim % 256) != 0) return EMDR2_E_BADARG;
+    const Shadow sh = {shadow, (const float *)table, shadow_min_rows};
+    return search_impl(tiled, n_rows, dim, row_base, emax_sq, queries, n_q, k, ids, out_dist, out_idx, out_row, out_flags, workspace,
+                       workspace_bytes, stream, f32 ? 1 : 0, (uint4 *)out_records, &sh);
+}
+
+int emdr2_mips_shadow_launches(void) { return (int)g_shadow_launches; }
 
 int emdr2_mips_merge_records(const void *records_in, int n_shards, int n_q, int k, int f32, void *out_dist, int32_t *out_idx, int64_t *out_row,
                              emdr2_stream_t stream)

@@ -32,6 +32,16 @@ int mips_launch_scan(int variant, int mode, const ScanParams &p, int grid, hipSt
 // `prog`: SCAN8_PROG_UINTS zeroed uints per launch (pair progress counters, one 256-byte line each) or nullptr
 #define SCAN8_PROG_UINTS (256 * 64)
 int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t row_end, int cus, unsigned *prog, hipStream_t stream);
+// int8 shadow path (mips_scan8i.hip).  Shadow image: the stripe-tiled geometry with 64 int8 k-values per 64-byte row; table: one float4
+// {s_b, N_b, D_b, -} per 256-row block; `nonfinite` is OR-ed with 1 if the fp16 image holds an inf / NaN (such a shard stays on fp16)
+int mips_launch_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *e8, float *blk, unsigned *nonfinite, hipStream_t stream);
+// int8 query image [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -}
+int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream);
+// mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_rescore has run
+int mips_launch_scan8i(const ScanParams &p, const void *e8_tiled, const float *blk, const void *q8_tiled, const float *qc, int bn, int64_t row_begin,
+                       int64_t row_end, int cus, unsigned *prog, hipStream_t stream);
+// fp32 scores (fp16 products of the fp16 image) for the entries an int8 segment appended: sub-lists, and the main list from `pre` on
+int mips_launch_rescore(const ScanParams &p, const void *queries, unsigned pre, hipStream_t stream);
 // production filter scan, ping-pong wave schedule (mode 0 only)
 int mips_launch_scan_pp(int variant, int depth, const ScanParams &p, int grid, hipStream_t stream);
 // production filter scan for 512 queries, query operand streamed straight to registers (mode 0, variant 0 only)

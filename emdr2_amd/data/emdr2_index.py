@@ -301,9 +301,16 @@ def shard_bounds(num_rows, world_size):
 
 
 class HipIndexShard(object):
-    """One contiguous row shard resident in this process's GPU, stripe-tiled for the HIP scan."""
+    """One contiguous row shard resident in this process's GPU, stripe-tiled for the HIP scan.
 
-    def __init__(self, dim, n_rows, row_base, device=None):
+    `shadow`: keep an int8 shadow image of the shard (+50 % HBM) and run the filter segments of at least `shadow_min_rows` rows of a
+    129..512-query search on it (csrc/mips_scan8i.hip); results are bit-identical with and without.  The image is only allocated for
+    shards that have such a segment, and only used while it is sealed against the current fp16 image and every row is finite."""
+
+    SHADOW_MIN_ROWS = 1 << 19
+    _DENSE_ROWS = 8192                                             # rows of the dense first segment of a search (csrc/mips_api.hip)
+
+    def __init__(self, dim, n_rows, row_base, device=None, shadow=True, shadow_min_rows=None):
         self.lib = _native.lib()
         if not torch.cuda.is_available():
             raise _native.NativeError("HipIndexShard needs a GPU; there is no CPU fallback")
@@ -318,6 +325,26 @@ class HipIndexShard(object):
         self._ws = None
         self._xws = None
         self._filled = 0
+        self.shadow_min_rows = int(self.SHADOW_MIN_ROWS if shadow_min_rows is None else shadow_min_rows)
+        self._want_shadow = bool(shadow) and self.dim % 256 == 0 and self.n_rows - self._DENSE_ROWS >= self.shadow_min_rows >= 1
+        self._shadow = None                                        # (int8 image, block table) sealed against self.tiled, or None
+        self._shadow_buf = self._spare_shadow_buf = None           # their storage (kept across seals), for self.tiled / the refresh spare
+
+    def _seal(self, tiled, into):
+        """Build the int8 shadow of the finished fp16 image `tiled` (on the current stream) into the buffers `into` (allocated on first
+        use) -> (buffers, shadow): shadow = the buffers, or None if the shard does not take the int8 path (no long segment, or a
+        non-finite row)."""
+        if not self._want_shadow:
+            return None, None
+        import ctypes
+        if into is None:
+            ib, tb = ctypes.c_size_t(), ctypes.c_size_t()
+            _native.check(self.lib.emdr2_mips_shadow_bytes(self.n_rows, self.dim, ctypes.byref(ib), ctypes.byref(tb)), "shadow_bytes")
+            into = (torch.empty(ib.value, dtype=torch.uint8, device=self.device), torch.empty(tb.value // 4, dtype=torch.float32, device=self.device))
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.emdr2_mips_seal_shadow(tiled.data_ptr(), self.n_rows, self.dim, into[0].data_ptr(), into[1].data_ptr(),
+                                                      bad.data_ptr(), _native.stream_ptr()), "seal_shadow")
+        return into, (into if int(bad.item()) == 0 else None)
 
     def append_rows(self, rows):
         """rows: fp16 [n, dim] (numpy or torch, host or device); appended at the next free local row."""
@@ -329,6 +356,7 @@ class HipIndexShard(object):
         n = rows.shape[0]
         if self._filled + n > self.n_rows:
             raise ValueError("shard overflow")
+        self._shadow = None
         for lo in range(0, n, _UPLOAD_ROWS):
             chunk = rows[lo:lo + _UPLOAD_ROWS]
             if isinstance(chunk, np.ndarray):                      # (a memory map: only this 1.5 GiB piece is ever resident on the host)
@@ -339,6 +367,8 @@ class HipIndexShard(object):
                                                         _native.stream_ptr()), "pack_rows")
             self._filled += chunk.shape[0]
             torch.cuda.current_stream().synchronize()  # the staging chunk is released next
+        if self._filled == self.n_rows:                # the shard becomes searchable: seal its shadow image
+            self._shadow_buf, self._shadow = self._seal(self.tiled, self._shadow_buf)
         return self
 
     # -- in-HBM refresh (config 5): a second image of the shard is filled while the first keeps serving searches ---------------
@@ -368,6 +398,9 @@ class HipIndexShard(object):
         searching stream wait for the stream that wrote the rows."""
         if getattr(self, "_spare", None) is None or self._refreshed != self.n_rows:
             raise RuntimeError("refresh incomplete (%d of %d rows)" % (getattr(self, "_refreshed", 0), self.n_rows))
+        # (the caller's stream has waited for the rows: the seal reads the finished spare image, then the images swap)
+        self._spare_shadow_buf, self._shadow = self._seal(self._spare, self._spare_shadow_buf)
+        self._shadow_buf, self._spare_shadow_buf = self._spare_shadow_buf, self._shadow_buf
         self.tiled, self._spare = self._spare, self.tiled
         self.emax_sq, self._spare_emax = self._spare_emax, self.emax_sq
         self._refreshed = 0
@@ -407,15 +440,27 @@ class HipIndexShard(object):
             return dist, idx, row, flags
         ws = self._workspace(k)
         ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        _native.check(self.lib.emdr2_mips_search(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base,
-                                                 self.emax_sq.data_ptr(), q.data_ptr(), nq, k, ids_ptr,
-                                                 dist.data_ptr(), idx.data_ptr(), row.data_ptr(), flags.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search")
+        if self._shadow is not None:
+            self._search_shadow(q, k, ids_ptr, False, dist, idx, row, None, flags, ws)
+        else:
+            _native.check(self.lib.emdr2_mips_search(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base,
+                                                     self.emax_sq.data_ptr(), q.data_ptr(), nq, k, ids_ptr,
+                                                     dist.data_ptr(), idx.data_ptr(), row.data_ptr(), flags.data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search")
         if exact_fallback:
             sel = torch.nonzero(flags).to(torch.int32).flatten()     # one host sync, like the reference's .item() loop
             if sel.numel():
                 self.search_exact(q, sel, k, dist, idx, row, flags)
         return dist, idx, row, flags
+
+    def _search_shadow(self, q, k, ids_ptr, f32, dist, idx, row, rec, flags, ws):
+        """emdr2_mips_search / _search_f32 / _search_records with the long filter segments on the sealed int8 shadow image."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _native.check(self.lib.emdr2_mips_search_shadow(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
+                                                        self._shadow[0].data_ptr(), self._shadow[1].data_ptr(), self.shadow_min_rows,
+                                                        q.data_ptr(), q.shape[0], k, ids_ptr, int(bool(f32)), ptr(dist), ptr(idx), ptr(row),
+                                                        ptr(rec), flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()),
+                      "mips_search_shadow")
 
     def search_records(self, queries, k, f32=False, out=None, exact_fallback=True):
         """The shard's canonical top-k as ONE uint8 [Q, k, 16] tensor of packed records {int64 global row | int32 doc id | score bits}
@@ -440,9 +485,12 @@ class HipIndexShard(object):
             return rec, flags
         ws = self._workspace(k)
         ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        _native.check(self.lib.emdr2_mips_search_records(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
-                                                         q.data_ptr(), nq, k, ids_ptr, int(bool(f32)), rec.data_ptr(), flags.data_ptr(),
-                                                         ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_records")
+        if self._shadow is not None:
+            self._search_shadow(q, k, ids_ptr, f32, None, None, None, rec, flags, ws)
+        else:
+            _native.check(self.lib.emdr2_mips_search_records(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
+                                                             q.data_ptr(), nq, k, ids_ptr, int(bool(f32)), rec.data_ptr(), flags.data_ptr(),
+                                                             ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_records")
         if exact_fallback:
             sel = torch.nonzero(flags).to(torch.int32).flatten()     # one host sync, like the reference's .item() loop
             if sel.numel():
@@ -493,9 +541,12 @@ class HipIndexShard(object):
             return dist, idx, row, flags
         ws = self._workspace(k)
         ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        _native.check(self.lib.emdr2_mips_search_f32(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
-                                                     q.data_ptr(), nq, k, ids_ptr, dist.data_ptr(), idx.data_ptr(), row.data_ptr(),
-                                                     flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_f32")
+        if self._shadow is not None:
+            self._search_shadow(q, k, ids_ptr, True, dist, idx, row, None, flags, ws)
+        else:
+            _native.check(self.lib.emdr2_mips_search_f32(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
+                                                         q.data_ptr(), nq, k, ids_ptr, dist.data_ptr(), idx.data_ptr(), row.data_ptr(),
+                                                         flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_f32")
         if exact_fallback:
             sel = torch.nonzero(flags).to(torch.int32).flatten()
             if sel.numel():

@@ -153,6 +153,25 @@ int emdr2_mips_merge_records(const void *records_in, int n_shards, int n_q, int 
 int emdr2_mips_pack_records(const void *dist, const int32_t *idx, const int64_t *row, const int32_t *sel, int n_sel, int k, int f32,
                             void *records, emdr2_stream_t stream);
 
+/*
+ * int8 shadow image: a second, int8 image of the shard in the stripe-tiled geometry plus three floats per 256-row
+ * block, from which the long filter segments of a 129..512-query search run at the int8 MFMA rate behind a rigorous per-block error bound;
+ * survivors are re-scored from the fp16 image before anything else sees them, so results are those of emdr2_mips_search bit for bit.
+ *   _shadow_bytes     sizes of the image and of the block table (dim % 256 == 0)
+ *   _seal_shadow      builds both from the FINISHED fp16 image (call again whenever the fp16 image changed); *nonfinite (device uint32,
+ *                     caller zeroes) is set to 1 if the image holds an inf / NaN -- such a shard must not be searched with its shadow
+ *   _search_shadow    emdr2_mips_search (f32 = 0), _search_f32 (f32 != 0) or, with out_records != NULL, _search_records, with filter segments
+ *                     of at least shadow_min_rows rows taken on the shadow image
+ *   _shadow_launches  number of int8 scan launches so far in this process (tests assert that the path really ran)
+ */
+int emdr2_mips_shadow_bytes(int64_t n_rows, int dim, size_t *image_bytes, size_t *table_bytes);
+int emdr2_mips_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream);
+int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const void *shadow,
+                             const void *table, int64_t shadow_min_rows, const void *queries, int n_q, int k, const int32_t *ids, int f32,
+                             void *out_dist, int32_t *out_idx, int64_t *out_row, void *out_records, uint32_t *out_flags, void *workspace,
+                             size_t workspace_bytes, emdr2_stream_t stream);
+int emdr2_mips_shadow_launches(void);
+
 /* Diagnostics for tests: fp32 MFMA scores S~[n_q, n_rows] (row-major float) of the scan kernel's
  * arithmetic, for measuring |S~ - exact| against the bound used by the validity check. */
 int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const void *queries, int n_q,

@@ -1,4 +1,4 @@
-"""Per-launch timing of one MIPS search (library hipEvent collector): rows, ms, TFLOP/s for every scan launch.  usage: python tools/scan_launches.py [rows] [queries]"""
+"""Per-launch timing of one MIPS search (library hipEvent collector): rows, ms, TFLOP/s for every scan launch.  usage: python tools/scan_launches.py [rows] [queries] [--fp16-only]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,11 +9,14 @@ if "--lib" in sys.argv:                                     # another build of t
 if "--exp" in sys.argv:                                     # experiments build: EMDR2_MIPS_ABLATE / _KERNEL / _VARIANT switches are live
     _native.LIB_PATH = _native.LIB_PATH.replace("libemdr2_hip.so", "libemdr2_hip_exp.so")
     sys.argv.remove("--exp")
+fp16_only = "--fp16-only" in sys.argv                      # no int8 shadow image: every filter segment on the fp16 kernels (A/B)
+if fp16_only:
+    sys.argv.remove("--fp16-only")
 from emdr2_amd.data.emdr2_index import HipIndexShard
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else bench.N_ROWS_FULL
 nq = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 lib = _native.lib()
-sh = HipIndexShard(768, rows, 0)
+sh = HipIndexShard(768, rows, 0, shadow=not fp16_only)
 for blk in bench.synth_rows(0, rows):
     sh.append_rows(blk)
 q = torch.randn((nq, 768), device="cuda").half()
