@@ -400,8 +400,10 @@ __global__ void __launch_bounds__(KNW * 64, 3) attention_bwd_dkv_kernel(BwdParam
         // this wave and its two SIMD mates.  (step 1 was issued in the prologue)
         if (step >= 1 && step + 1 < nstep) issue(step + 1, stage ^ 1);
         const int qh0 = step * QS;
-        // keys of this wave all ahead of every query of the step: P == 0 exactly and dS == 0
-        if (!wave_live || (CAUSAL && k0 > qh0 + QS - 1)) continue;
+        // keys of this wave all ahead of every query of the step: P == 0 exactly and dS == 0 -- unless a query of the step is masked
+        // EVERYWHERE (a padded query, or a real one whose visible keys are all padding): its row is uniform over all sk keys, keys ahead of
+        // it included, and feeds their dV.  Such a row has pm = -10000 log2(e) + log2(sk); every other row's is far above -7000.
+        if (!wave_live || (CAUSAL && k0 > qh0 + QS - 1 && __builtin_amdgcn_ballot_w64(st_all[stage][0][l31] > -7000.f) == ~0ull)) continue;
         const uint32_t qr32 = (uint32_t)__builtin_amdgcn_ballot_w64(__float_as_uint(st_all[stage][3][l31]) != 0u);     // bit q: query q of the step is a real token
         const uint32_t so = (uint32_t)(stage * 8192);
 

@@ -863,6 +863,21 @@ def _attn_side(x, info):
     return info, None, x.stride(0), x.stride(1), x.stride(2), x.shape[0], x.shape[1]
 
 
+def _pad_seq_head(x, s_to, h_to):
+    """x [b, s, heads, hn] (any strides) -> itself, or a fresh zero-padded [b, s_to, heads, h_to]."""
+    b, s, heads, hn = x.shape
+    if s == s_to and hn == h_to:
+        return x
+    out = x.new_zeros((b, s_to, heads, h_to))
+    out[:, :s, :, :hn] = x
+    return out
+
+
+def _pad_ids(ids, s_to):
+    b, s = ids.shape
+    return ids if s == s_to else torch.cat([ids, ids.new_zeros((b, s_to - s))], dim=1).contiguous()
+
+
 _SPLITKV_PLANS = {}
 
 
@@ -886,7 +901,8 @@ class AttentionCoreFn(torch.autograd.Function):
     slices and the backward writes dq, dk, dv straight into ONE packed gradient (no select_backward zero-fill + add chains).
     `ids_q` / `ids_k` are dense token ids [b, s] (masks: pad id 0 + optional history mask) or a PackedSeqs, in which case that side's
     tensors are [rows, ...] without a batch dimension (sequence b = rows cu[b] .. cu[b+1]).  hn == 64 runs the fused kernels
-    (attention.hip, attention_bwd.hip; dense keys need sk % 32 == 0); other dense shapes run QK^T GEMM + softmax kernel + PV GEMM.
+    (attention.hip, attention_bwd.hip; dense keys need sk % 32 == 0); other dense shapes run QK^T GEMM + softmax kernel + PV GEMM, head
+    dim and query count zero-padded to multiples of 32 where they are not (the statistics then cover the padded query grid).
     Only the row statistics (max, sum-exp) and the output are kept; the backward rebuilds the probabilities from them."""
 
     @staticmethod
@@ -947,13 +963,28 @@ class AttentionCoreFn(torch.autograd.Function):
             if sk % 32:
                 raise ValueError("dense attention operands need a key length that is a multiple of 32 (got %d: K x --seq-length; the reference's "
                                  "sequence lengths 256 / 512 are; packed layouts take any length)" % sk)
-            vT = head_transpose(v, b, sk, heads, hn)
-            S = torch.empty((b, heads, sq, sk), dtype=BF16, device=dev)
-            gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sq, sk, hn, b, q.stride(0), k.stride(0), heads * sq * sk, heads, q.stride(2),
-                    k.stride(2), sq * sk, alpha=scale)
-            _native.check(_lib().emdr2_softmax_mask_fwd(S.data_ptr(), iq.data_ptr(), ik.data_ptr(), b, heads, sq, sk, int(causal),
+            # the GEMMs contract over whole 32-element steps (gemm.hip: K % 32 == 0) -- QK^T over the head dim, the backward's dK / dV products
+            # over the queries: other head dims and query counts run zero-padded.  Exact: a zero head column adds nothing to a score or to a
+            # gradient, a padded query row (token id 0: a uniform row nobody reads, zero upstream gradient) nothing to dK / dV.  The row
+            # statistics (and the dropout mask's rows) are then those of the padded [b, heads, sp] grid.
+            hp, sp = (hn + 31) // 32 * 32, (sq + 31) // 32 * 32
+            padded = hp != hn or sp != sq
+            out = ctxo
+            if padded:
+                q, k, v = _pad_seq_head(q, sp, hp), _pad_seq_head(k, sk, hp), _pad_seq_head(v, sk, hp)
+                iq = _pad_ids(iq, sp)
+                m = torch.empty((b, heads, sp), dtype=torch.float32, device=dev)
+                l = torch.empty_like(m)
+                out = torch.empty((b, sp, heads, hp), dtype=BF16, device=dev)
+            vT = head_transpose(v, b, sk, heads, hp)
+            S = torch.empty((b, heads, sp, sk), dtype=BF16, device=dev)
+            gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sp, sk, hp, b, q.stride(0), k.stride(0), heads * sp * sk, heads, q.stride(2),
+                    k.stride(2), sp * sk, alpha=scale)
+            _native.check(_lib().emdr2_softmax_mask_fwd(S.data_ptr(), iq.data_ptr(), ik.data_ptr(), b, heads, sp, sk, int(causal),
                                                         m.data_ptr(), l.data_ptr(), float(drop_p), int(seed), _sp()), "softmax_fwd")
-            gemm_nt(S, sk, vT, sk, ctxo, heads * hn, sq, hn, sk, b, heads * sq * sk, heads * hn * sk, sq * heads * hn, heads, sq * sk, hn * sk, hn)
+            gemm_nt(S, sk, vT, sk, out, heads * hp, sp, hp, sk, b, heads * sp * sk, heads * hp * sk, sp * heads * hp, heads, sp * sk, hp * sk, hp)
+            if padded:
+                ctxo.copy_(out[:, :sq, :, :hn])
         ctx.save_for_backward(qsrc, kvsrc, m, l, ctxo)
         if stash_key and ATTN_STASH.mode == 'store':
             ATTN_STASH.store[stash_key] = (ctxo, m, l)
@@ -1019,6 +1050,16 @@ class AttentionCoreFn(torch.autograd.Function):
                                                   heads, sq, sk, hn, causal, scale, ctx.drop_p, ctx.seed, _sp()), "attention_bwd")
             return dqsrc, dkvsrc, None, None, None, None, None, None
         ids_q, ids_k = iq, ik
+        hp, sp = (hn + 31) // 32 * 32, (sq + 31) // 32 * 32                              # zero-padded like the forward (see there)
+        padded = hp != hn or sp != sq
+        if padded:
+            q, k, v = _pad_seq_head(q, sp, hp), _pad_seq_head(k, sk, hp), _pad_seq_head(v, sk, hp)
+            dctx = _pad_seq_head(dctx.view(b, sq, heads, hn), sp, hp).view(b, sp, heads * hp)
+            ids_q = _pad_ids(ids_q, sp)
+            outs = (dq, dk, dv, sq, hn)
+            dq = torch.empty((b, sp, heads, hp), dtype=BF16, device=dev)
+            dk, dv = torch.empty((b, sk, heads, hp), dtype=BF16, device=dev), torch.empty((b, sk, heads, hp), dtype=BF16, device=dev)
+            sq, hn, H = sp, hp, heads * hp
         # main orientation: S = scale Q K^T (recomputed), dP = dctx V^T, dS = P (dP_eff - D) with P rebuilt from (m, l)
         S = torch.empty((b, heads, sq, sk), dtype=BF16, device=dev)
         gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sq, sk, hn, b, q.stride(0), k.stride(0), heads * sq * sk, heads, q.stride(2), k.stride(2),
@@ -1045,6 +1086,10 @@ class AttentionCoreFn(torch.autograd.Function):
                 alpha=scale)
         dctxT = head_transpose(dctx.view(b, sq, heads, hn), b, sq, heads, hn)
         gemm_nt(St, sq, dctxT, sq, dv, dv.stride(1), sk, hn, sq, b, heads * sk * sq, heads * hn * sq, dv.stride(0), heads, sk * sq, hn * sq, hn)
+        if padded:
+            outs[0].copy_(dq[:, :outs[3], :, :outs[4]])
+            outs[1].copy_(dk[..., :outs[4]])
+            outs[2].copy_(dv[..., :outs[4]])
         return dqsrc, dkvsrc, None, None, None, None, None, None
 
 
