@@ -74,6 +74,13 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
+// a product that is rounded where it stands: never fused into an addition that consumes it
+__device__ __forceinline__ float mul_rounded(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // ---- LayerNorm (torch.nn.LayerNorm semantics, eps inside the sqrt; mpu/layers.py:28-36) -----------------------
 // one wave per row, H % 8 == 0, 16-B vector loads
 __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const uint16_t *x, const float *gamma, const float *beta, uint16_t *y,
@@ -83,16 +90,25 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const uint16_t *x, c
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const uint16_t *xr = x + row * H;
-    float s = 0.f, ss = 0.f;
+    float s = 0.f;
     for (int i = lane * 8; i < H; i += 512) {
         const uint4 v = *(const uint4 *)(xr + i);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const float a = bf2f((uint16_t)(w[j] & 0xffff)), b = bf2f((uint16_t)(w[j] >> 16)); s += a + b; ss += a * a + b * b; }
+        for (int j = 0; j < 4; ++j) s += bf2f((uint16_t)(w[j] & 0xffff)) + bf2f((uint16_t)(w[j] >> 16));
     }
-    s = wave_sum(s); ss = wave_sum(ss);
+    s = wave_sum(s);
     const float mu = s / H;
-    const float var = fmaxf(ss / H - mu * mu, 0.f);
+    // centred second pass (the row comes back from cache): E[x^2] - mu^2 in fp32 cancels to nothing on a row whose mean dwarfs its spread
+    float ss = 0.f, ss1 = 0.f;                                           // two chains: the even and the odd elements
+    for (int i = lane * 8; i < H; i += 512) {
+        const uint4 v = *(const uint4 *)(xr + i);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float a = bf2f((uint16_t)(w[j] & 0xffff)) - mu, b = bf2f((uint16_t)(w[j] >> 16)) - mu; ss += a * a; ss1 += b * b; }
+    }
+    ss = wave_sum(ss + ss1);
+    const float var = ss / H;
     const float rs = rsqrtf(var + eps);
     if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
     uint16_t *yr = y + row * H;
@@ -122,7 +138,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd768_kernel(const uint16_t *x
     uint4 v[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) v[i] = ld_stream(xr + (i * 32 + l31) * 8);
-    float f[3][8], s = 0.f, ss = 0.f;
+    float f[3][8], s = 0.f;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
@@ -130,13 +146,23 @@ __global__ void __launch_bounds__(256) layernorm_fwd768_kernel(const uint16_t *x
         for (int j = 0; j < 4; ++j) {
             f[i][2 * j] = bf2f((uint16_t)(w[j] & 0xffff)); f[i][2 * j + 1] = bf2f((uint16_t)(w[j] >> 16));
             s += f[i][2 * j] + f[i][2 * j + 1];
-            ss += f[i][2 * j] * f[i][2 * j] + f[i][2 * j + 1] * f[i][2 * j + 1];
         }
     }
 #pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }   // within the 32 lanes of the row
-    const float mu = s * (1.0f / 768.0f);
-    const float var = fmaxf(ss * (1.0f / 768.0f) - mu * mu, 0.f);
+    for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o);                                  // within the 32 lanes of the row
+    // centred second reduction over the registers (no memory traffic): E[x^2] - mu^2 in fp32 cancels to nothing on a row whose mean
+    // dwarfs its spread.  mul_rounded: ONE rounded mean for every element -- left to contraction, the compiler folds s * (1 / 768) into the
+    // subtraction of some elements (an unrounded mean) and not of others, and the first-order cancellation of the mean's rounding error
+    // in sum (x - mu)^2 is gone (rstd 5e-6 off on a row of 256 with one element at 258)
+    const float mu = mul_rounded(s, 1.0f / 768.0f);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { f[i][j] -= mu; ss += f[i][j] * f[i][j]; }
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const float var = ss * (1.0f / 768.0f);
     const float rs = rsqrtf(var + eps);
     if (live && l31 == 0) { mean[row] = mu; rstd[row] = rs; }
     if (!live) return;
@@ -150,8 +176,8 @@ __global__ void __launch_bounds__(256) layernorm_fwd768_kernel(const uint16_t *x
         uint32_t o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            o[j] = (uint32_t)f2bf(fmaf((f[i][2 * j] - mu) * rs, gm[2 * j], bt[2 * j])) |
-                   ((uint32_t)f2bf(fmaf((f[i][2 * j + 1] - mu) * rs, gm[2 * j + 1], bt[2 * j + 1])) << 16);
+            o[j] = (uint32_t)f2bf(fmaf(f[i][2 * j] * rs, gm[2 * j], bt[2 * j])) |
+                   ((uint32_t)f2bf(fmaf(f[i][2 * j + 1] * rs, gm[2 * j + 1], bt[2 * j + 1])) << 16);
         st_stream(yr + c, make_uint4(o[0], o[1], o[2], o[3]));
     }
 }
@@ -653,7 +679,8 @@ __global__ void __launch_bounds__(256) lse_gather_kernel(const uint16_t *logits,
     if (threadIdx.x == 0) {
         const float l = m + __logf(red[0] + red[1] + red[2] + red[3]);
         lse[row] = l;
-        gold[row] = bf2f(lr[labels[row]]) - l;
+        const long long lab = labels[row];                               // outside [0, V) (an ignore_index): gold logit 0, as the fused LM head defines it
+        gold[row] = (lab >= 0 && lab < V ? bf2f(lr[lab]) : 0.f) - l;
     }
 }
 

@@ -250,7 +250,8 @@ __global__ void __launch_bounds__(256) lse_fwd_f32_kernel(const float *logits, c
     if (threadIdx.x == 0) {
         const float l = m + logf((red[0] + red[1]) + (red[2] + red[3]));
         lse[row] = l;
-        gold[row] = lr[labels[row]] - l;
+        const long long lab = labels[row];                               // outside [0, V): gold logit 0, as in elementwise.hip
+        gold[row] = (lab >= 0 && lab < V ? lr[lab] : 0.f) - l;
     }
 }
 __global__ void __launch_bounds__(256) lse_bwd_f32_kernel(const float *logits, const long long *labels, const float *lse, const float *w, float *dlogits, int V)

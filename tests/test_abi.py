@@ -130,3 +130,26 @@ def test_fp32_validation_entry_points_validate_their_arguments(lib):
     assert lib.emdr2_f32_lse_gather_bwd(one, one, one, one, None, 4, 16, None) == -1
     assert lib.emdr2_f32_retriever_prior_fwd(one, one, one, one, 2, 2000, 16, 1.0, None) == -1    # K <= 1024
     assert lib.emdr2_f32_retriever_prior_bwd(one, one, one, one, one, None, 2, 4, 16, 1.0, None) == -1
+
+
+def test_vector_cast_entry_points_reject_odd_lengths_and_misaligned_pointers(lib):
+    """The four-elements-per-thread kernels (gradient exchange casts, flat Adam) take n % 4 == 0, 16-byte aligned fp32 and 8-byte aligned
+    bf16 pointers: anything else is refused (-1) before a launch; LayerNorm backward + mask takes H = 768 only (-4)."""
+    al, off4, off8 = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 4), ctypes.c_void_p(4096 + 8)
+    for n in (1, 6, 1027):
+        assert lib.emdr2_scale_cast_f32_to_bf16(al, al, n, 1.0, None) == -1
+        assert lib.emdr2_widen_bf16_to_f32(al, al, n, None) == -1
+        assert lib.emdr2_adam_step_flat(al, al, al, al, al, n, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None, 0.0, None) == -1
+    assert lib.emdr2_scale_cast_f32_to_bf16(off8, al, 1028, 1.0, None) == -1       # fp32 source: 16 bytes
+    assert lib.emdr2_scale_cast_f32_to_bf16(al, off4, 1028, 1.0, None) == -1       # bf16 destination: 8 bytes
+    assert lib.emdr2_widen_bf16_to_f32(al, off8, 1028, None) == -1
+    assert lib.emdr2_widen_bf16_to_f32(off4, al, 1028, None) == -1
+    for bad in range(4):
+        ptrs = [off8 if i == bad else al for i in range(4)]
+        assert lib.emdr2_adam_step_flat(ptrs[0], ptrs[1], ptrs[2], ptrs[3], al, 1028, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None, 0.0, None) == -1
+    assert lib.emdr2_adam_step_flat(al, al, al, al, off4, 1028, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None, 0.0, None) == -1
+    assert lib.emdr2_adam_step_flat(al, al, al, al, al, 1028, 6, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None, 0.0, None) == -1      # split % 4
+    assert lib.emdr2_adam_step_flat(al, al, al, al, al, 1028, 1032, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None, 0.0, None) == -1   # split > n
+    assert lib.emdr2_adam_step_flat(al, al, al, al, al, 1028, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0, None, 0.0, None) == -1      # step < 1
+    assert lib.emdr2_layernorm_bwd_mask(al, al, al, al, al, None, al, al, al, 4, 264, al, 0.1, 1, None) == -4
+    assert lib.emdr2_retriever_prior_fwd(al, al, al, al, 2, 1025, 64, 1.0, None) == -4
