@@ -25,7 +25,7 @@
 #define EXP_T8_STREAM(p, zs, KT, zs_addr, KT_STREAM, T8_DMA_ON) const int zs_addr = zs; const int KT_STREAM = KT; constexpr bool T8_DMA_ON = true;
 #define EXP_T8_HOST(p)
 #define EXP_TN_GENERAL_ONLY(general_only)
-// ---- mips_api.hip / mips_scan.hip / mips_scan8.hip ------------------------------------------------------------------------------------
+// ---- mips_api.hip / mips_scan.hip / mips_scan8.h (EXP_SCAN8_*: in the kernel template, so in its fp16 AND its int8 instance) ----------
 #define EXP_ENV_INT(name, dflt) (dflt)
 #define EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
 #define EXP_MIPS_COUPLE() true

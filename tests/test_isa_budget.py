@@ -64,6 +64,9 @@ def test_persistent_gemm_and_scan_kernels_fit_two_waves_per_simd(table):
     for sub in ("gemm8_kernel", "gemm8t_kernel", "mips_scan8_kernel"):
         for e in _sel(table, sub):
             assert e["vgpr_count"] + e["agpr_count"] <= 256, e
+    # the scan is one kernel template (csrc/mips_scan8.h): both its instances, fp16 and int8, are in the library and under the bound above
+    assert len(_sel(table, "mips_scan8_kernel")) == 2
+    assert len(_sel(table, "Scan8Fp16")) == 1 and len(_sel(table, "Scan8Int8")) == 1
 
 
 def test_attention_forward_does_not_copy_its_accumulators():
@@ -76,8 +79,10 @@ def test_attention_forward_does_not_copy_its_accumulators():
 
 def test_power_bound_kernels_use_the_16x16x32_mfma_shape():
     # at the board's power cap the 16 x 16 x 32 shape does ~19 % more flops than 32 x 32 x 16 (half the accumulator registers moved
-    # per flop); the MIPS scan and both persistent GEMMs are built on it
-    for sub, small, big in (("mips_scan8_kernel", "v_mfma_f32_16x16x32_f16", "v_mfma_f32_32x32x16_f16"),
+    # per flop); the MIPS scan (its fp16 instance, and its int8 instance on the int8 shape of the same geometry) and both persistent GEMMs are
+    # built on it
+    for sub, small, big in (("Scan8Fp16", "v_mfma_f32_16x16x32_f16", "v_mfma_f32_32x32x16_f16"),
+                            ("Scan8Int8", "v_mfma_i32_16x16x64_i8", "v_mfma_i32_32x32x32_i8"),
                             ("gemm8_kernel", "v_mfma_f32_16x16x32_bf16", "v_mfma_f32_32x32x16_bf16"),
                             ("gemm8t_kernel", "v_mfma_f32_16x16x32_bf16", "v_mfma_f32_32x32x16_bf16")):
         n_small = kr.count_opcode(kr.DEFAULT_LIB, small, sub)

@@ -40,7 +40,8 @@ static inline bool exp_gemm_use_gemm8() { static const int v = getenv("EMDR2_GEM
 #define EXP_T8_HOST(p) { static const int ablate_env = getenv("EMDR2_T8_ABLATE") ? atoi(getenv("EMDR2_T8_ABLATE")) : 0; (p).ablate = ablate_env; }
 #define EXP_TN_GENERAL_ONLY(general_only) { static const bool tn_old = getenv("EMDR2_TN_OLD") && atoi(getenv("EMDR2_TN_OLD")); general_only = tn_old; }
 // ---- MIPS: EMDR2_MIPS_SEG0 / _GROWTH / _VARIANT / _GRID / _KERNEL / _ABLATE / _TUNE / _COUPLE (mips_api.hip), schedule variants
-//      (tools/exp/mips_scan_variants*.inc), the filter-never-fires and late-start timing switches of the persistent scan ---------------------
+//      (tools/exp/mips_scan_variants*.inc), the filter-never-fires and late-start timing switches of the persistent scan (EXP_SCAN8_*: they
+//      sit in the kernel template of csrc/mips_scan8.h and so act on its fp16 AND its int8 instance) --------------------------------------------
 static inline int exp_env_int(const char *name, int dflt) { const char *v = getenv(name); return (v && *v) ? atoi(v) : dflt; }
 #define EXP_ENV_INT(name, dflt) exp_env_int(name, dflt)
 #define EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc) \
