@@ -54,12 +54,15 @@ __device__ __forceinline__ float gelu_erf(float x)
     const float hp = gelu_half_poly_exp(x, e);
     return fmaf(-fabsf(x), hp * e, fmaxf(x, 0.0f));
 }
+// step(x) of the derivative, keyed on the SIGN BIT like the copysign beside it: with x >= 0.0f, x = -0.0 took +P(t) / 2 AND the step,
+// gelu'(-0.0) = 1.5 instead of 0.5 (a bf16 pre-activation that underflowed from below is -0.0)
+__device__ __forceinline__ float gelu_step(float x) { return (int32_t)__float_as_uint(x) >= 0 ? 1.0f : 0.0f; }
 // both at once (one rcp, one exp2, one polynomial): the activation and its derivative of the same pre-activation
 __device__ __forceinline__ float gelu_erf_with_grad(float x, float &grad)
 {
     float e;
     const float hp = gelu_half_poly_exp(x, e);
-    grad = fmaf(e, fmaf(x, 0.3989422804014327f, -copysignf(hp, x)), x >= 0.0f ? 1.0f : 0.0f);
+    grad = fmaf(e, fmaf(x, 0.3989422804014327f, -copysignf(hp, x)), gelu_step(x));
     return fmaf(-fabsf(x), hp * e, fmaxf(x, 0.0f));
 }
 // d/dx of the erf-form GELU: Phi(x) + x phi(x) = step(x) + exp(-x^2 / 2) (x / sqrt(2 pi) - sign(x) P(t) / 2), same erf approximation and
@@ -68,7 +71,6 @@ __device__ __forceinline__ float gelu_erf_grad(float x)
 {
     float e;
     const float hp = gelu_half_poly_exp(x, e);
-    const float step = x >= 0.0f ? 1.0f : 0.0f;
-    return fmaf(e, fmaf(x, 0.3989422804014327f, -copysignf(hp, x)), step);
+    return fmaf(e, fmaf(x, 0.3989422804014327f, -copysignf(hp, x)), gelu_step(x));
 }
 #endif
