@@ -37,8 +37,8 @@ struct Workspace {
     char *q_frag;
     char *q_tiled;
     float *qnorm, *tau;
-    unsigned *count;       // [512] main-list counts, then [8][512] sub-list counts, then the pair-progress counters
-    uint2 *cand, *cand8;
+    unsigned *count;       // [512] main-list counts, then [8][512] sub-list counts, [512] pending counts, then the pair-progress counters
+    uint2 *cand, *cand8, *pend;
 };
 
 size_t carve(char *base, int dim, Workspace *w)
@@ -49,10 +49,11 @@ size_t carve(char *base, int dim, Workspace *w)
     char *a = take((size_t)(dim / 32) * 512 * 64);
     char *b = take(512 * sizeof(float));
     char *c = take(512 * sizeof(float));
-    char *d = take((512 + 8 * 512 + 8 * (size_t)SCAN8_PROG_UINTS) * sizeof(unsigned));       // candidate counts (main, per-XCD) + pair progress counters of up to 8 scan8 launches
+    char *d = take((512 + 8 * 512 + 512 + 8 * (size_t)SCAN8_PROG_UINTS) * sizeof(unsigned)); // candidate counts (main, per-XCD, pending) + pair progress counters of up to 8 scan8 launches
     char *e = take((size_t)512 * CAPQ * sizeof(uint2));
     char *g = take((size_t)512 * 8 * SUBCAP * sizeof(uint2));
-    if (w) { w->q_frag = f; w->q_tiled = a; w->qnorm = (float *)b; w->tau = (float *)c; w->count = (unsigned *)d; w->cand = (uint2 *)e; w->cand8 = (uint2 *)g; }
+    char *h = take((size_t)512 * PENDCAP * sizeof(uint2));     // deferred survivors of the int8 segments (mips_scan8i.hip)
+    if (w) { w->q_frag = f; w->q_tiled = a; w->qnorm = (float *)b; w->tau = (float *)c; w->count = (unsigned *)d; w->cand = (uint2 *)e; w->cand8 = (uint2 *)g; w->pend = (uint2 *)h; }
     return off;
 }
 
@@ -145,6 +146,8 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
     const int seg0 = env_int("EMDR2_MIPS_SEG0", 8192) / 512 * 512;
     const int growth = env_int("EMDR2_MIPS_GROWTH", 8);    // r04: 8 (was 16): with cheaper selects a tighter threshold for the next segment pays (tools/mips_timeline.py)
     const int growth_i8 = env_int("EMDR2_MIPS_GROWTH_I8", 2); // ... of the segments that run on the int8 shadow image
+    // an int8 survivor is re-scored right after its segment iff estimate + margin * eps reaches tau (mips_scan8i.hip triage_kernel): speed only
+    const float margin_i8 = (float)env_int("EMDR2_MIPS_MARGIN_PCT", 25) * 0.01f;
     if (seg0 < 512 || seg0 > (int)CAPQ - 512 || growth < 2 || growth_i8 < 2) return EMDR2_E_BADARG;
     const int force_variant = env_int("EMDR2_MIPS_VARIANT", -1);
     const int cus = env_int("EMDR2_MIPS_GRID", cu_count());
@@ -161,10 +164,10 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         if ((rc = mips_launch_pack_queries(qp, nqp, dim, BN, w.q_tiled, w.qnorm, stream))) return rc;
         EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
         const int64_t dense_rows = n_rows < seg0 ? n_rows : seg0;
-        unsigned *const count8 = w.count + 512, *const prog0 = count8 + 8 * 512;
-        // thresholds, counts, flags -- and the sub-list counts and pair-progress counters of the persistent scan launches -- in one launch
+        unsigned *const count8 = w.count + 512, *const pcount = count8 + 8 * 512, *const prog0 = pcount + 512;
+        // thresholds, counts, flags -- and the sub-list counts, pending counts and pair-progress counters of the persistent scan launches -- in one launch
         if ((rc = mips_launch_init(w.tau, w.count, out_flags + q0, BN, nqp, (unsigned)dense_rows, count8,
-                                   8 * 512 + (variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0), stream)))
+                                   9 * 512 + (variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0), stream)))
             return rc;
 
         ScanParams sp;
@@ -195,6 +198,7 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         const bool couple = EXP_MIPS_COUPLE();
         int64_t done = 0, seg_end = dense_rows;
         int mode = 1;
+        bool pending = false;                                // some int8 segment has run: its deferred survivors wait in w.pend
         while (done < n_rows) {
             sp.tile_begin = (int)(done / BM);
             sp.tile_end = (int)((seg_end + BM - 1) / BM);
@@ -231,10 +235,18 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
                 g_timing.rows[g_timing.n] = seg_end - done;
                 ++g_timing.n;
             }
-            // survivors of an int8 segment carry integer sums: they get their fp32 scores before the select (or the finalize) reads them
-            if (int8_segment && (rc = mips_launch_rescore(sp, qp, (unsigned)kp, stream))) return rc;
-            // (the select after the LAST segment runs inside the finalize launch)
-            if (seg_end < n_rows && (rc = mips_launch_select(w.cand, w.count, w.cand8, count8, w.tau, out_flags + q0, CAPQ, kp, nqp, stream))) return rc;
+            // survivors of an int8 segment carry integer sums: the likely winners get their fp32 scores before the select reads them, the others
+            // wait in the pending list behind an upper bound
+            if (int8_segment) {
+                if ((rc = mips_launch_triage(sp, qp, (unsigned)kp, shadow->table, qc, w.pend, pcount, margin_i8, stream))) return rc;
+                pending = true;
+            }
+            // (the select after the LAST segment runs inside the finalize launch -- after a select of its own when something is pending: the
+            // deferred pass wants the tightest tau, and its survivors must be in the main list before the final select)
+            if ((seg_end < n_rows || pending) &&
+                (rc = mips_launch_select(w.cand, w.count, w.cand8, count8, w.tau, out_flags + q0, CAPQ, kp, nqp, stream)))
+                return rc;
+            if (seg_end >= n_rows && pending && (rc = mips_launch_rescore_pending(sp, qp, w.pend, pcount, stream))) return rc;
             done = seg_end;
             // the next segment ends at `growth` times the rows done so far -- at `growth_i8` times once a segment of that length runs on the int8
             // image: its survivors are ~6 x the fp16 filter's and each costs a 1.5 KB gather in the re-score, so a fresher threshold pays there

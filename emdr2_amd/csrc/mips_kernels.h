@@ -5,6 +5,7 @@
 
 #define CAPQ 16384u /* candidate slots per query (8 B each) */
 #define SUBCAP 1024u /* ... plus 8 sub-lists of this many per query, one per XCD, filled by the persistent scan (mips_scan8.hip) */
+#define PENDCAP 8192u /* ... plus this many pending entries (upper bound bits, row) per query: deferred survivors of the int8 segments (mips_scan8i.hip) */
 
 struct ScanParams {
     const char *e_tiled;  // stripe-tiled index image
@@ -37,11 +38,15 @@ int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t ro
 int mips_launch_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *e8, float *blk, unsigned *nonfinite, hipStream_t stream);
 // int8 query image [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -}
 int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream);
-// mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_rescore has run
+// mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_triage has run
 int mips_launch_scan8i(const ScanParams &p, const void *e8_tiled, const float *blk, const void *q8_tiled, const float *qc, int bn, int64_t row_begin,
                        int64_t row_end, int cus, unsigned *prog, hipStream_t stream);
-// fp32 scores (fp16 products of the fp16 image) for the entries an int8 segment appended: sub-lists, and the main list from `pre` on
-int mips_launch_rescore(const ScanParams &p, const void *queries, unsigned pre, hipStream_t stream);
+// the entries an int8 segment appended (sub-lists, and the main list from `pre` on): fp32 scores (fp16 products of the fp16 image) for those whose
+// estimate + margin * eps reaches tau; the others go to `pend` [n_q][PENDCAP] / `pcount` [n_q] (zeroed per search) with score word -inf
+int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, const float *blk, const float *qc, void *pend, unsigned *pcount,
+                       float margin, hipStream_t stream);
+// after the select behind the last segment: pending entries whose bound still reaches tau get their fp32 score and join the main list
+int mips_launch_rescore_pending(const ScanParams &p, const void *queries, const void *pend, const unsigned *pcount, hipStream_t stream);
 // production filter scan, ping-pong wave schedule (mode 0 only)
 int mips_launch_scan_pp(int variant, int depth, const ScanParams &p, int grid, hipStream_t stream);
 // production filter scan for 512 queries, query operand streamed straight to registers (mode 0, variant 0 only)

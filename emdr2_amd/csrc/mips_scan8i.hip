@@ -1,8 +1,9 @@
 // emdr2_amd/csrc/mips_scan8i.hip -- the index scan of mips_scan8.hip on an int8 shadow image of the index: fused int8 MFMA GEMM  I = E8 Q8^T
 // + integer threshold filter, for the long filter segments of a 129..512-query search.
 //
-// The scan is only a filter: it proposes candidates, the re-score kernel below gives every survivor the fp32 score of its fp16
-// row before a select sees it, and finalize_kernel re-scores exactly and proves the result.  So the filter may be coarse as long as a rigorous
+// The scan is only a filter: it proposes candidates, the triage kernel below gives every likely winner the fp32 score of its fp16
+// row before a select sees it and parks the other survivors under a rigorous upper bound (they are read only if that bound still reaches the
+// final threshold), and finalize_kernel re-scores exactly and proves the result.  So the filter may be coarse as long as a rigorous
 // bound on its error is added before a row is pruned.  Rows are quantised per 256-row block b (this kernel's row tile) with one scale
 // s_b = max|e| / 127, queries per query with t_q = max|q| / 127; with the integer sum I of row r and query q
 //     S = t_q s_b I + (q - t_q q8).e_r + t_q q8.(e_r - s_b e8_r)    =>    |S - t_q s_b I| <= a_q N_b + b_q D_b =: eps(q, b)
@@ -14,7 +15,7 @@
 // slots, phases, barriers, partner coupling, survivor queue and sub-list protocol, instantiated here with Scan8Int8.  The int8 images have the fp16 images' geometry -- 64-byte rows, 16-byte groups XOR-swizzled with
 // (row >> 2) & 3 -- with 64 k-values per chunk instead of 32, and a lane's v_mfma_i32_16x16x64_i8 operand is one 16-byte group like the fp16
 // kernel's: half the K-tiles per item, half the bytes per MAC at every level.  A survivor's score word holds the INTEGER sum until
-// mips_launch_rescore has run.
+// mips_launch_triage has run.
 #include "mips_scan8.h"
 
 namespace {
@@ -43,6 +44,22 @@ __device__ __forceinline__ int s8i_theta(float tau, float t, float a, float b, f
     if (!(x > -2.0e9f)) return (int)0x80000000;
     if (x > 2.0e9f) return 0x7fffffff;
     return (int)x;
+}
+
+// The other direction, for a survivor with integer sum I: est = t s I and U(q, b, I) >= est + eps(q, b) + the fp32 accumulation slack of the
+// re-score (dim 2^-22 ||q|| N_b, the form finalize_kernel uses; ||q|| <= a_q + b_q).  Every step errs UPWARDS: est carries 1e-6 relative slack
+// over its three roundings (t s, the conversion of I, the product), eps and the slack 1e-4 over theirs, the sum 1e-6 over its additions.  So
+// U < tau implies that the exact score AND the fp32 sum rescore_wave_x4 would form are below tau.  A zero scale gives est = 0, which is exact.
+struct S8iBound { float est, eps, upper; };
+__device__ __forceinline__ S8iBound s8i_upper(int isum, float t, float a, float b, float s, float n, float d, float dim)
+{
+    S8iBound r;
+    r.est = t * s * (float)isum;
+    r.eps = (a * n + b * d) * 1.0001f;
+    const float slack = dim * 0x1p-22f * (a + b) * n * 1.0001f;
+    const float u = r.est + fabsf(r.est) * 1e-6f + r.eps + slack;
+    r.upper = u + fabsf(u) * 1e-6f;
+    return r;
 }
 
 // The int8 instance: integer sums against Theta(q, b), formed once per item and query column from the query's and the block's constants.
@@ -189,16 +206,88 @@ __global__ void pack_queries_i8_kernel(const uint4 *__restrict__ queries, int n_
     if (lane == 0) qc[q] = q < n_q ? make_float4(t, (ra + (ra + rb) * 0x1p-22f) * 1.001f, rb * 1.001f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// Re-score what one int8 segment appended: the score word of every new entry becomes the fp32 sum of the exact fp16 products of its row and
-// query (any fp32 accumulation order satisfies the eps of DESIGN 3.3, so select, finalize and the proof run unchanged).  New entries of query
-// q: the eight sub-lists up to min(count8, SUBCAP) and the main list from `pre` to min(count, capq); the entries below `pre` were kept by the
-// select before the segment and keep their scores bit for bit.  `pre` is kp: an int8 segment always follows a select over at least the
-// dense segment's rows, which leaves exactly kp entries.  grid (9 lists, n_q), one wave per entry.
-__global__ void __launch_bounds__(256) rescore_kernel(const char *__restrict__ tiled, const uint4 *__restrict__ queries, int nseg, uint2 *cand,
-                                                      const unsigned *__restrict__ count, uint2 *cand8, const unsigned *__restrict__ count8,
-                                                      unsigned capq, unsigned pre)
+// fp32 scores of four (row, query) pairs at a time: the sum of the exact fp16 products of a row of the fp16 image and the query, a lane's
+// segments in order, then the xor tree (any fp32 accumulation order satisfies the eps of DESIGN 3.3, so select, finalize and the proof run
+// unchanged -- but both callers form THIS sum, so which of them scores a row never shows in a score word).  All four rows' loads go out
+// before the first is used; rows past n_valid repeat rows[0].
+__device__ __forceinline__ void rescore_wave_x4(const char *__restrict__ tiled, const unsigned (&rows)[4], const uint4 *__restrict__ qrow, int nseg, int lane,
+                                                float (&out)[4])
 {
-    const int q = blockIdx.y, list = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nch = nseg >> 2;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int seg = lane; seg < nseg; seg += 64) {
+        uint4 ev[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ev[c] = *(const uint4 *)(tiled + tiled_seg_offset(rows[c], seg, nch));
+        const half8 qv = __builtin_bit_cast(half8, qrow[seg]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const half8 e = __builtin_bit_cast(half8, ev[c]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s[c] += (float)e[j] * (float)qv[j];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s[c] += __shfl_xor(s[c], o);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[c] = s[c];
+}
+
+// exclusive rank of the threads with `flag` among the block's 256 threads, and their number (two barriers; `sh` is 4 words)
+__device__ __forceinline__ unsigned block_rank_256(bool flag, unsigned *sh, unsigned &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
+    const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+    __syncthreads();                                           // (sh may still be read from the previous call)
+    if (lane == 0) sh[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const unsigned v = sh[w]; off += w < wave ? v : 0u; tot += v; }
+    total = tot;
+    return off + before;
+}
+
+// the block's work list sh_row[0, n) (entry sh_idx[j] of `dst`): fp32 score words, four per wave at a time
+__device__ __forceinline__ void rescore_worklist(const char *__restrict__ tiled, const uint4 *__restrict__ qrow, int nseg, const unsigned *sh_row,
+                                                 const unsigned *sh_idx, unsigned n, uint2 *dst, unsigned dst_end)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (unsigned j0 = 4 * wave; j0 < n; j0 += 16) {
+        unsigned rows[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) rows[c] = sh_row[j0 + c < n ? j0 + c : j0];
+        float sc[4];
+        rescore_wave_x4(tiled, rows, qrow, nseg, lane, sc);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (lane == 0 && j0 + c < n) {
+                const unsigned i = sh_idx[j0 + c];
+                if (i < dst_end) dst[i] = make_uint2(__float_as_uint(sc[c]), rows[c]);
+            }
+    }
+}
+
+// Triage of what one int8 segment appended.  New entries of query q: the eight sub-lists up to min(count8, SUBCAP) and the main list from `pre`
+// to min(count, capq); the entries below `pre` were kept by the select before the segment and keep their scores bit for bit.  `pre` is kp: an
+// int8 segment always follows a select over at least the dense segment's rows, which leaves exactly kp entries.  With est = t_q s_b I:
+//   est + margin eps >= tau_q (the tau the segment was scanned with): a likely winner.  Its score word becomes the fp32 score, in place, so the
+//     select that follows raises tau over the rows that matter;
+//   otherwise: (U, row) goes to the query's pending list and the score word becomes -inf, which the select ranks below the kp finite entries
+//     the main list holds.  mips_launch_rescore_pending reads the row at the end of the search only if U still reaches the final tau;
+//   the pending list is full: re-scored in place like a likely winner.  Nothing is ever dropped here and no flag is raised.
+// `margin` decides only who is read now and who (perhaps) later.  grid (9 lists, n_q); a block reserves its pending slots with ONE atomic.
+__global__ void __launch_bounds__(256) triage_kernel(const char *__restrict__ tiled, const uint4 *__restrict__ queries, int nseg, uint2 *cand,
+                                                     const unsigned *__restrict__ count, uint2 *cand8, const unsigned *__restrict__ count8, unsigned capq,
+                                                     unsigned pre, const float4 *__restrict__ blk, const float4 *__restrict__ qc,
+                                                     const float *__restrict__ tau, uint2 *pend, unsigned *pcount, float margin)
+{
+    __shared__ unsigned long long sh_def[CAPQ / 64];
+    __shared__ unsigned sh4[4], sh_base, sh_row[256], sh_idx[256];
+    const int q = blockIdx.y, list = blockIdx.x, tid = threadIdx.x;
     uint2 *ent;
     unsigned lo, hi;
     if (list < 8) {
@@ -207,26 +296,91 @@ __global__ void __launch_bounds__(256) rescore_kernel(const char *__restrict__ t
     } else {
         ent = cand + (size_t)q * capq; lo = pre; hi = count[q];
         if (hi > capq) hi = capq;
+        if (hi > CAPQ) hi = CAPQ;                              // (sh_def covers CAPQ entries; capq is CAPQ)
     }
+    if (lo >= hi) return;
+    const float4 c = qc[q];
+    const float tq = tau[q], dimf = (float)(nseg * 8);
+    uint2 *const pq = pend + (size_t)q * PENDCAP;
+    auto deferred = [&](unsigned i, uint2 &e, float &upper) {
+        e = ent[i];
+        const float4 b = blk[e.y >> 8];
+        const S8iBound r = s8i_upper((int)e.x, c.x, c.y, c.z, b.x, b.y, b.z, dimf);
+        upper = r.upper;
+        return !(r.est + margin * r.eps >= tq);
+    };
+    // pass 1: who is deferred (one ballot word per wave and 256 entries, which pass 2 reads back: the decision is taken once) and how many;
+    // one atomic reserves the block's slots (the count may pass PENDCAP: readers clamp it)
+    unsigned mine = 0;
+    for (unsigned i0 = lo; i0 < hi; i0 += 256) {
+        const unsigned i = i0 + tid;
+        uint2 e; float u;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(i < hi && deferred(i, e, u));
+        if ((tid & 63) == 0) { sh_def[((i0 - lo) >> 6) + (tid >> 6)] = m; mine += (unsigned)__popcll(m); }
+    }
+    if ((tid & 63) == 0) sh4[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned total = sh4[0] + sh4[1] + sh4[2] + sh4[3];
+        sh_base = total ? atomicAdd(&pcount[q], total) : 0u;
+    }
+    __syncthreads();
+    unsigned next = sh_base;
+    // pass 2: 256 entries at a time
     const uint4 *qrow = queries + (size_t)q * nseg;
-    const int nch = nseg >> 2;
-    for (unsigned i0 = lo + 2 * wave; i0 < hi; i0 += 8) {      // two entries in flight per wave
-        const bool two = i0 + 1 < hi;
-        const unsigned r0 = ent[i0].y, r1 = ent[two ? i0 + 1 : i0].y;
-        float s0 = 0.f, s1 = 0.f;
-        for (int seg = lane; seg < nseg; seg += 64) {
-            const half8 e0 = __builtin_bit_cast(half8, *(const uint4 *)(tiled + tiled_seg_offset(r0, seg, nch)));
-            const half8 e1 = __builtin_bit_cast(half8, *(const uint4 *)(tiled + tiled_seg_offset(r1, seg, nch)));
-            const half8 qv = __builtin_bit_cast(half8, qrow[seg]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { s0 += (float)e0[j] * (float)qv[j]; s1 += (float)e1[j] * (float)qv[j]; }
+    for (unsigned i0 = lo; i0 < hi; i0 += 256) {
+        const unsigned i = i0 + tid;
+        uint2 e = make_uint2(0u, 0u);
+        float u = 0.f;
+        if (i < hi) deferred(i, e, u);
+        const bool def = (sh_def[((i0 - lo) >> 6) + (tid >> 6)] >> (tid & 63)) & 1ull;
+        unsigned n_def;
+        const unsigned slot = next + block_rank_256(def, sh4, n_def);
+        next += n_def;
+        const bool parked = def && slot < PENDCAP;
+        if (parked) {
+            pq[slot] = make_uint2(__float_as_uint(u), e.y);
+            ent[i].x = 0xff800000u;
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }
-        if (lane == 0) {
-            ent[i0].x = __float_as_uint(s0);
-            if (two) ent[i0 + 1].x = __float_as_uint(s1);
-        }
+        unsigned n_now;
+        const unsigned w = block_rank_256(i < hi && !parked, sh4, n_now);
+        if (i < hi && !parked) { sh_row[w] = e.y; sh_idx[w] = i; }
+        __syncthreads();
+        rescore_worklist(tiled, qrow, nseg, sh_row, sh_idx, n_now, ent, hi);
+    }
+}
+
+// The deferred pass, after the select that follows the last segment: tau_q is the tightest threshold the search will have.  A pending entry
+// with U < tau_q is dropped unread -- its fp32 score is below tau_q like that of a row the scan pruned --, the others get their fp32 score and
+// go behind the main list's kp entries (at most kp + PENDCAP < capq), where the final select finds them.  grid (slices, n_q): a query's list
+// is cut into equal slices.
+__global__ void __launch_bounds__(256) rescore_pending_kernel(const char *__restrict__ tiled, const uint4 *__restrict__ queries, int nseg, uint2 *cand,
+                                                              unsigned *count, unsigned capq, const float *__restrict__ tau, const uint2 *__restrict__ pend,
+                                                              const unsigned *__restrict__ pcount)
+{
+    __shared__ unsigned sh4[4], sh_base, sh_row[256], sh_idx[256];
+    const int q = blockIdx.y, tid = threadIdx.x;
+    unsigned np = pcount[q];
+    if (np > PENDCAP) np = PENDCAP;
+    const unsigned lo = (unsigned)((uint64_t)np * blockIdx.x / gridDim.x), hi = (unsigned)((uint64_t)np * (blockIdx.x + 1) / gridDim.x);
+    if (lo >= hi) return;
+    const float tq = tau[q];
+    const uint2 *const pq = pend + (size_t)q * PENDCAP;
+    const uint4 *qrow = queries + (size_t)q * nseg;
+    uint2 *const main_list = cand + (size_t)q * capq;
+    for (unsigned i0 = lo; i0 < hi; i0 += 256) {
+        const unsigned i = i0 + tid;
+        const uint2 e = i < hi ? pq[i] : make_uint2(0u, 0u);
+        const bool keep = i < hi && !(__uint_as_float(e.x) < tq);
+        unsigned n_keep;
+        const unsigned w = block_rank_256(keep, sh4, n_keep);
+        if (n_keep == 0) continue;                             // (block-uniform)
+        if (tid == 0) sh_base = atomicAdd(&count[q], n_keep);
+        if (keep) sh_row[w] = e.y;
+        __syncthreads();
+        if (keep) sh_idx[w] = sh_base + w;
+        __syncthreads();
+        rescore_worklist(tiled, qrow, nseg, sh_row, sh_idx, n_keep, main_list, capq);
     }
 }
 
@@ -246,10 +400,18 @@ int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, v
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int mips_launch_rescore(const ScanParams &p, const void *queries, unsigned pre, hipStream_t stream)
+int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, const float *blk, const float *qc, void *pend, unsigned *pcount,
+                       float margin, hipStream_t stream)
 {
-    hipLaunchKernelGGL(rescore_kernel, dim3(9, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count, p.cand8,
-                       p.count8, p.capq, pre);
+    hipLaunchKernelGGL(triage_kernel, dim3(9, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count, p.cand8,
+                       p.count8, p.capq, pre, (const float4 *)blk, (const float4 *)qc, p.tau, (uint2 *)pend, pcount, margin);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int mips_launch_rescore_pending(const ScanParams &p, const void *queries, const void *pend, const unsigned *pcount, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rescore_pending_kernel, dim3(8, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count,
+                       p.capq, p.tau, (const uint2 *)pend, pcount);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
