@@ -41,6 +41,9 @@ SIGNATURES = {
     "emdr2_mips_seal_shadow": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "emdr2_mips_search_shadow": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_shadow_launches": (_i32, []),
+    "emdr2_mips_block_norm_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
+    "emdr2_mips_block_norms": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp]),
+    "emdr2_mips_update_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_debug_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "emdr2_mips_set_timing": (_i32, [_i32]),
     "emdr2_mips_timing_collect": (_i32, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i64), _i32, ctypes.POINTER(_i32)]),

@@ -110,6 +110,13 @@ def get_parser():
     g.add_argument('--max-training-rank', type=int, default=None)
     g.add_argument('--async-indexer', action='store_true')
     g.add_argument('--index-reload-interval', type=int, default=500)
+    g.add_argument('--index-refresh-in-place', action='store_true',
+                   help='(not in the reference) with --async-indexer: write re-embedded evidence rows into the index image that is being '
+                        'searched at every step boundary instead of filling a spare image and swapping it in every --index-reload-interval '
+                        'steps.  No spare fp16 image and no spare int8 shadow image: half the index HBM of the swap mode.  A choice of '
+                        'semantics, not a tuning knob: searches then see a MIX of two embedding generations -- rows already re-embedded in '
+                        'the current pass next to rows of the pass before -- where the default, the reference\'s update_index, replaces '
+                        'the whole index atomically')
     g.add_argument('--indexer-batch-size', type=int, default=128)
     g.add_argument('--indexer-log-interval', type=int, default=1000)
     g.add_argument('--report-topk-accuracies', nargs='+', type=int, default=[])

@@ -324,7 +324,41 @@ int emdr2_mips_shadow_bytes(int64_t n_rows, int dim, size_t *image_bytes, size_t
 int emdr2_mips_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream)
 {
     if (!tiled || !shadow || !table || !nonfinite || ((uintptr_t)table & 15) || bad_shape(n_rows, dim) || (dim % 256) != 0) return EMDR2_E_BADARG;
-    return mips_launch_seal_shadow(tiled, n_rows, dim, shadow, (float *)table, nonfinite, (hipStream_t)stream);
+    return mips_launch_seal_shadow(tiled, dim, 0, (n_rows + 255) / 256, shadow, (float *)table, nonfinite, (hipStream_t)stream);
+}
+
+int emdr2_mips_block_norm_bytes(int64_t n_rows, size_t *bytes)
+{
+    if (!bytes || bad_shape(n_rows, 64)) return EMDR2_E_BADARG;
+    *bytes = (size_t)((n_rows + 511) / 512 * 512 / 256) * sizeof(float);
+    return EMDR2_OK;
+}
+
+int emdr2_mips_block_norms(const void *tiled, int64_t n_rows, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq,
+                           emdr2_stream_t stream)
+{
+    const int64_t table_blocks = (n_rows + 511) / 512 * 2;
+    if (!tiled || !block_norm_sq || bad_shape(n_rows, dim) || first_block < 0 || n_blocks < 0 || first_block + n_blocks > table_blocks)
+        return EMDR2_E_BADARG;
+    return mips_launch_block_norms(tiled, dim, first_block, n_blocks, block_norm_sq, (hipStream_t)stream);
+}
+
+int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
+                           float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream_)
+{
+    if (!rows_rm || !tiled || !block_norm_sq || !emax_sq || bad_shape(n_rows_total, dim) || n_chunk < 0 || row_offset < 0 ||
+        row_offset + n_chunk > n_rows_total)
+        return EMDR2_E_BADARG;
+    if (shadow && (!table || !nonfinite || ((uintptr_t)table & 15) || (dim % 256) != 0)) return EMDR2_E_BADARG;
+    if (n_chunk == 0) return EMDR2_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t first_block = row_offset / 256, n_blocks = (row_offset + n_chunk - 1) / 256 - first_block + 1;   // the blocks these rows touch
+    int rc;
+    if ((rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, stream))) return rc;
+    if ((rc = mips_launch_block_norms(tiled, dim, first_block, n_blocks, block_norm_sq, stream))) return rc;
+    if ((rc = mips_launch_table_max(block_norm_sq, (n_rows_total + 511) / 512 * 2, emax_sq, stream))) return rc;
+    if (shadow) return mips_launch_seal_shadow(tiled, dim, first_block, n_blocks, shadow, (float *)table, nonfinite, stream);
+    return EMDR2_OK;
 }
 
 int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const void *shadow,

@@ -19,39 +19,111 @@ __global__ void pack_rows_kernel(const uint4 *__restrict__ rows_rm, int64_t n_ch
     *(uint4 *)(tiled + tiled_seg_offset(row_offset + r, seg, nseg >> 2)) = rows_rm[i];
 }
 
+// ||E[r]||^2 of one row by one wave, the same value in every lane: lane l takes the 8-element groups l, l + 64, ... in order, then a
+// butterfly over the lanes.  emax_sq of a freshly packed shard (row_norm_max_kernel, row-major rows) and of a shard updated in place
+// (block_norms_kernel, rows read back from the tiled image) must agree bit for bit -- the search's validity bound reads it -- so both
+// kernels go through this one routine and differ only in where a group comes from.  Whether the compiler contracts `s += x * x` into an
+// fma in one instance and not in the other cannot matter: the square of an fp16 value has at most 22 significant bits and is exact in
+// fp32, so the fma and the multiply-then-add round the same sum.
+struct RowMajorRow {
+    const uint4 *row;                                           // rows_rm + r * nseg
+    __device__ __forceinline__ uint4 operator()(int seg) const { return row[seg]; }
+};
+struct TiledRow {
+    const char *tiled;
+    int64_t row;
+    int nch;
+    __device__ __forceinline__ uint4 operator()(int seg) const { return *(const uint4 *)(tiled + tiled_seg_offset(row, seg, nch)); }
+};
+template <class Load>
+__device__ __forceinline__ float row_norm_sq_wave(const Load &load, int nseg, int lane)
+{
+    float s = 0.f;
+    for (int seg = lane; seg < nseg; seg += 64) {
+        const half8 h = __builtin_bit_cast(half8, load(seg));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float x = (float)h[j]; s += x * x; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
 __global__ void row_norm_max_kernel(const uint4 *__restrict__ rows_rm, int64_t n_chunk, int nseg, float *emax_sq)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     float best = 0.f;
-    for (int64_t r = wave; r < n_chunk; r += nwaves) {
-        float s = 0.f;
-        for (int seg = lane; seg < nseg; seg += 64) {
-            const uint4 v = rows_rm[r * nseg + seg];
-            const half8 h = __builtin_bit_cast(half8, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float x = (float)h[j]; s += x * x; }
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-        best = fmaxf(best, s);
-    }
+    for (int64_t r = wave; r < n_chunk; r += nwaves) best = fmaxf(best, row_norm_sq_wave(RowMajorRow{rows_rm + r * nseg}, nseg, lane));
     if (lane == 0 && best > 0.f) atomicMax((unsigned *)emax_sq, __float_as_uint(best)); // non-negative floats order as uints
+}
+
+// In-place row updates (emdr2_mips_update_rows): block_norm_sq[b] = max over the 256 rows of block b of ||E[r]||^2, read from the tiled
+// image (rows past the end of the shard are zero there, the image is padded to 512 rows).  One workgroup per block, 64 rows per wave.
+__global__ void __launch_bounds__(256) block_norms_kernel(const char *__restrict__ tiled, int nseg, int64_t first_block, float *__restrict__ block_norm_sq)
+{
+    __shared__ float sh[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t block = first_block + blockIdx.x;
+    float best = 0.f;
+#pragma unroll 4                                                 // (four rows' loads in flight; each row's own arithmetic is untouched)
+    for (int i = 0; i < 64; ++i) best = fmaxf(best, row_norm_sq_wave(TiledRow{tiled, block * 256 + wave * 64 + i, nseg >> 2}, nseg, lane));
+    if (lane == 0) sh[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) block_norm_sq[block] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+
+// *emax_sq = max of the whole table (one workgroup: 82,092 entries at the full index), so the bound can FALL when the row that held the
+// maximum was overwritten.  The maximum of non-negative floats does not depend on the order they are folded in.
+__global__ void __launch_bounds__(1024) table_max_kernel(const float *__restrict__ block_norm_sq, int64_t n_blocks, float *__restrict__ emax_sq)
+{
+    __shared__ float sh[16];
+    float best = 0.f;
+    for (int64_t i = threadIdx.x; i < n_blocks; i += 1024) best = fmaxf(best, block_norm_sq[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; ++w) best = fmaxf(best, sh[w]);
+        *emax_sq = best;
+    }
+}
+
+int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq, hipStream_t stream)
+{
+    if (n_blocks == 0) return 0;
+    hipLaunchKernelGGL(block_norms_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 8, first_block, block_norm_sq);
+    return CHECK_LAUNCH();
+}
+
+int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream)
+{
+    hipLaunchKernelGGL(table_max_kernel, dim3(1), dim3(1024), 0, stream, block_norm_sq, n_blocks, emax_sq);
+    return CHECK_LAUNCH();
+}
+
+// pack_rows_kernel alone: rows into the image, emax_sq untouched (the in-place update recomputes it from the block table)
+int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, hipStream_t stream)
+{
+    const int nseg = dim / 8;
+    const int64_t total = n_chunk * nseg;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg,
+                       row_offset, (char *)tiled);
+    return CHECK_LAUNCH();
 }
 
 int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled,
                           float *emax_sq, hipStream_t stream)
 {
-    const int nseg = dim / 8;
-    const int64_t total = n_chunk * nseg;
-    if (total == 0) return 0;
-    const int64_t blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg,
-                       row_offset, (char *)tiled);
+    if (n_chunk == 0) return 0;
+    const int rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, stream);
+    if (rc) return rc;
     int nb = (int)((n_chunk + 3) / 4);
     if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(row_norm_max_kernel, dim3(nb), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg, emax_sq);
+    hipLaunchKernelGGL(row_norm_max_kernel, dim3(nb), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, dim / 8, emax_sq);
     return CHECK_LAUNCH();
 }
 

@@ -35,7 +35,9 @@ int mips_launch_scan(int variant, int mode, const ScanParams &p, int grid, hipSt
 int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t row_end, int cus, unsigned *prog, hipStream_t stream);
 // int8 shadow path (mips_scan8i.hip).  Shadow image: the stripe-tiled geometry with 64 int8 k-values per 64-byte row; table: one float4
 // {s_b, N_b, D_b, -} per 256-row block; `nonfinite` is OR-ed with 1 if the fp16 image holds an inf / NaN (such a shard stays on fp16)
-int mips_launch_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *e8, float *blk, unsigned *nonfinite, hipStream_t stream);
+// Seals the 256-row blocks [first_block, first_block + n_blocks); the whole shard is [0, ceil(n_rows / 256)).
+int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, void *e8, float *blk, unsigned *nonfinite,
+                            hipStream_t stream);
 // int8 query image [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -}
 int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream);
 // mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_triage has run
@@ -58,6 +60,11 @@ int mips_launch_scan_ablate(int abl, const ScanParams &p, int grid, hipStream_t 
 
 int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled,
                           float *emax_sq, hipStream_t stream);
+// in-place row updates: rows into the image without touching emax_sq; block_norm_sq[b] = max ||E[r]||^2 over block b's 256 rows for
+// b in [first_block, first_block + n_blocks); *emax_sq = max of the table's n_blocks entries
+int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, hipStream_t stream);
+int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq, hipStream_t stream);
+int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream);
 int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, int64_t n_out, void *rows_rm,
                             hipStream_t stream);
 // queries row-major fp16 [n_q, dim] -> chunk-tiled image for BN rows (zero padded) + ||q||_2 upper bounds

@@ -108,12 +108,14 @@ __device__ __forceinline__ int quant8(float x, float inv)
 
 // One workgroup per 256-row block, one thread per row.  Pass 1: max |e| and max ||e_r||^2 of the block; pass 2 (the block is in L2 now):
 // quantise with the block's scale, write the int8 rows, measure ||e_r - s_b e8_r||.  Rows past the end of the shard are zero in the fp16
-// image and stay zero here.
-__global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict__ tiled, int nch, char *__restrict__ e8, float4 *__restrict__ blk,
-                                                          unsigned *__restrict__ nonfinite)
+// image and stay zero here.  Workgroup i seals block first_block + i and reads or writes nothing of any other block: a full seal is the range
+// [0, n_blocks), an in-place row update (emdr2_mips_update_rows) re-seals the blocks it touched with the very same code.
+__global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict__ tiled, int nch, int64_t first_block, char *__restrict__ e8,
+                                                          float4 *__restrict__ blk, unsigned *__restrict__ nonfinite)
 {
     __shared__ float sh[4];
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t block = first_block + blockIdx.x;
+    const int64_t row = block * 256 + threadIdx.x;
     const int nseg = nch * 4;
     float amax = 0.f, n2 = 0.f;
     bool bad = false;
@@ -161,7 +163,7 @@ __global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict
     // the residual e - s e8 was evaluated in fp32: each element is off by up to 2^-24 |s e8| + 2^-24 |e - s e8|, which matters exactly when the
     // quantisation is (nearly) exact -- ternary rows have d2 = 0 while 127 * fl(1 / 127) is not 1.  2^-22 N_b covers it.
     const float nb = sqrtf(n2) * 1.001f;
-    if (threadIdx.x == 0) blk[blockIdx.x] = make_float4(s, nb, (sqrtf(d2) + nb * 0x1p-22f) * 1.001f, 0.f);
+    if (threadIdx.x == 0) blk[block] = make_float4(s, nb, (sqrtf(d2) + nb * 0x1p-22f) * 1.001f, 0.f);
 }
 
 // int8 query image (chunk-tiled like the fp16 one, 64 k-values per chunk) + per query {t_q, a_q, b_q}; one wave per padded query row
@@ -386,11 +388,12 @@ __global__ void __launch_bounds__(256) rescore_pending_kernel(const char *__rest
 
 } // namespace
 
-int mips_launch_seal_shadow(const void *tiled, int64_t n_rows, int dim, void *e8, float *blk, unsigned *nonfinite, hipStream_t stream)
+int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, void *e8, float *blk, unsigned *nonfinite,
+                            hipStream_t stream)
 {
-    const int64_t blocks = (n_rows + 255) / 256;
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(seal_shadow_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const char *)tiled, dim / 32, (char *)e8, (float4 *)blk, nonfinite);
+    if (n_blocks == 0) return 0;
+    hipLaunchKernelGGL(seal_shadow_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 32, first_block, (char *)e8,
+                       (float4 *)blk, nonfinite);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

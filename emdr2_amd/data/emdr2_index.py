@@ -329,6 +329,9 @@ class HipIndexShard(object):
         self._want_shadow = bool(shadow) and self.dim % 256 == 0 and self.n_rows - self._DENSE_ROWS >= self.shadow_min_rows >= 1
         self._shadow = None                                        # (int8 image, block table) sealed against self.tiled, or None
         self._shadow_buf = self._spare_shadow_buf = None           # their storage (kept across seals), for self.tiled / the refresh spare
+        self._spare = None                                         # the second fp16 image of a swap refresh (begin_refresh)
+        self._refreshing = False                                   # between begin_refresh and commit_refresh
+        self._block_norms = None                                   # max ||row||^2 per 256-row block of self.tiled (update_rows), built on first use
 
     def _seal(self, tiled, into):
         """Build the int8 shadow of the finished fp16 image `tiled` (on the current stream) into the buffers `into` (allocated on first
@@ -380,6 +383,7 @@ class HipIndexShard(object):
         else:
             self._spare.zero_(); self._spare_emax.zero_()
         self._refreshed = 0
+        self._refreshing = True
 
     def refresh_rows(self, local_row, rows):
         """rows fp16 [n, dim] on this device -> spare image rows [local_row, local_row + n), enqueued on the CURRENT stream."""
@@ -404,6 +408,49 @@ class HipIndexShard(object):
         self.tiled, self._spare = self._spare, self.tiled
         self.emax_sq, self._spare_emax = self._spare_emax, self.emax_sq
         self._refreshed = 0
+        self._refreshing = False
+        self._block_norms = None                                   # (it described the image that has just been swapped out)
+
+    # -- in-place update: rows of the image that is being searched are overwritten, nothing is swapped, no second image exists ---
+    def update_rows(self, local_row, rows):
+        """rows fp16 [n, dim] on this device -> rows [local_row, local_row + n) of the LIVE image, enqueued on the CURRENT stream (the
+        device counterpart of the reference store's `add_block_data(..., allow_overwrite=True)`).  `emax_sq` and, when the shard has a
+        sealed int8 shadow, the touched 256-row blocks of the shadow image and its table are brought to exactly what a fresh build of
+        the same rows would hold (csrc: emdr2_mips_update_rows), so searches afterwards are those of a freshly built shard bit for bit.
+        The caller orders the update against searches of this shard, as for `refresh_rows`: a search running concurrently on another
+        stream would see a half-written block.  The block-norm table behind `emax_sq` is built on the first call (one pass over the
+        image) and again after a `commit_refresh`.  If an updated block holds an inf / NaN the shard stops using its shadow until the
+        next full seal, like a shard freshly built from such rows; that flag is read back with one `.item()` per call on a shard with a
+        sealed shadow (a host synchronisation on the current stream -- the search that follows does one of its own)."""
+        if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_cuda:
+            raise ValueError("rows must be a CUDA float16 [n, %d] tensor" % self.dim)
+        n = rows.shape[0]
+        if local_row < 0 or local_row + n > self.n_rows:
+            raise ValueError("update rows out of range")
+        if self._filled != self.n_rows:
+            raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
+        if self._refreshing:
+            raise RuntimeError("a swap refresh is in progress (begin_refresh without commit_refresh): its commit would discard the update")
+        if n == 0:
+            return
+        import ctypes
+        if self._block_norms is None:
+            nbytes = ctypes.c_size_t()
+            _native.check(self.lib.emdr2_mips_block_norm_bytes(self.n_rows, ctypes.byref(nbytes)), "block_norm_bytes")
+            table = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device)
+            _native.check(self.lib.emdr2_mips_block_norms(self.tiled.data_ptr(), self.n_rows, self.dim, 0, table.numel(), table.data_ptr(),
+                                                          _native.stream_ptr()), "block_norms")
+            self._block_norms = table
+        rows = rows.contiguous()
+        shadow = self._shadow
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device) if shadow is not None else None
+        _native.check(self.lib.emdr2_mips_update_rows(rows.data_ptr(), n, self.dim, local_row, self.n_rows, self.tiled.data_ptr(),
+                                                      self._block_norms.data_ptr(), self.emax_sq.data_ptr(),
+                                                      shadow[0].data_ptr() if shadow is not None else None,
+                                                      shadow[1].data_ptr() if shadow is not None else None,
+                                                      bad.data_ptr() if shadow is not None else None, _native.stream_ptr()), "update_rows")
+        if shadow is not None and int(bad.item()) != 0:
+            self._shadow = None
 
     def set_ids(self, ids):
         ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)) if not torch.is_tensor(ids) else ids.to(torch.int32)
@@ -693,6 +740,14 @@ class DistributedBruteForceIndex(object):
 
     def commit_refresh(self):
         self.shard.commit_refresh()
+
+    def update_rows(self, global_row, rows):
+        """rows fp16 [n, dim] -> rows [global_row, global_row + n) of the image this rank is searching (HipIndexShard.update_rows); the
+        range must lie inside this rank's shard (`local_rows()`)."""
+        lo, hi = self.local_rows()
+        if global_row < lo or global_row + rows.shape[0] > hi:
+            raise ValueError("rows [%d, %d) are not all in this rank's shard [%d, %d)" % (global_row, global_row + rows.shape[0], lo, hi))
+        self.shard.update_rows(global_row - lo, rows)
 
     def add_embed_data(self, all_embed_data):
         """Upload this rank's row shard (reference: emdr2_index.py:241-266; there: rank 0 uploads

@@ -104,18 +104,33 @@ class IndexBuilder(object):
     def refresh_batches(self, index):
         """Generator over this rank's work: each `next()` embeds one batch of the rank's own index rows and packs it into the spare
         image, on the current stream.  Lets a caller interleave re-indexing with training steps (AsyncIndexBuilder)."""
+        index.begin_refresh()
+        for start, emb in self.embed_batches(index):
+            index.refresh_rows(start, emb)
+            yield emb.shape[0]
+
+    def embed_batches(self, index):
+        """Generator over this rank's work without a sink: (first global row, fp16 [n, H] embeddings) of one batch of the rank's own
+        index rows per `next()`, computed on the current stream."""
         lo, hi = index.local_rows()
         ids = index.shard.ids
-        index.begin_refresh()
         for start in range(lo, hi, self.batch_size):
             end = min(start + self.batch_size, hi)
             doc_ids = ids[start - lo:end - lo] if ids is not None else torch.arange(start + 1, end + 1, dtype=torch.int32)
-            index.refresh_rows(start, self.embed(doc_ids))
+            emb = self.embed(doc_ids)
             self.track_and_report_progress(batch_size=end - start)
-            yield end - start
+            yield start, emb
 
-    def build_into_index(self, index):
-        """Synchronous full refresh of this rank's shard followed by the swap (all ranks call it)."""
+    def build_into_index(self, index, in_place=False):
+        """Synchronous full refresh of this rank's shard followed by the swap (all ranks call it).  `in_place` (not in the reference):
+        every embedded batch overwrites its rows of the image that is being searched (`index.update_rows`) -- no spare image, no swap;
+        a search issued between two batches would see rows of both generations."""
+        if in_place:
+            for start, emb in self.embed_batches(index):
+                index.update_rows(start, emb)
+            torch.cuda.current_stream().synchronize()
+            self._barrier()
+            return
         for _ in self.refresh_batches(index):
             pass
         torch.cuda.current_stream().synchronize()

@@ -14,6 +14,11 @@ Usage inside the training loop:
         indexer.pump()                         # enqueue a few re-embedding batches on the side stream
         train_step(...)
         indexer.maybe_swap(iteration)          # == NEW_INDEX_READY handling + update_evidence_embedding()
+
+Rolling mode (`in_place=True`, --index-refresh-in-place; not in the reference): no spare image.  What a `pump()` embedded is written into
+the image that is being searched at the next step boundary (`index.update_rows`), so the index costs its own size in HBM instead of twice
+that, and a row serves weights that are on average one pass old instead of one and a half.  Searches then see a mix of two embedding
+generations: a choice of semantics, which is why the atomic swap stays the default.
 """
 import copy
 
@@ -27,7 +32,7 @@ PACE_MARGIN = 0.9        # fraction of the reload interval a pass over the shard
 
 class AsyncIndexBuilder(IndexBuilder):
     def __init__(self, live_context_model, evidence_arena, index, seq_length_ret, cls_id, sep_id, pad_id=0, batch_size=128,
-                 log_interval=1000, index_reload_interval=500, batches_per_pump=None, process_group=None):
+                 log_interval=1000, index_reload_interval=500, batches_per_pump=None, process_group=None, in_place=False):
         snapshot = copy.deepcopy(live_context_model)
         for p in snapshot.parameters():
             p.requires_grad_(False)
@@ -37,6 +42,9 @@ class AsyncIndexBuilder(IndexBuilder):
         super().__init__(snapshot, evidence_arena, seq_length_ret, cls_id, sep_id, pad_id, batch_size, log_interval, process_group)
         self.live = live_context_model
         self.index = index
+        self.in_place = bool(in_place)
+        self._queued = []                                       # rolling mode: (first global row, staging rows, event) not yet applied
+        self.passes = 0                                         # rolling mode: completed passes over the shard
         self.index_reload_interval = index_reload_interval
         lo, hi = index.local_rows()
         n_batches = (hi - lo + batch_size - 1) // batch_size
@@ -60,14 +68,16 @@ class AsyncIndexBuilder(IndexBuilder):
                 for ps, pl in zip(self.model.parameters(), self.live.parameters()):
                     ps.copy_(pl)
                     ps.__dict__.pop("_emdr2_cache", None)
-            self._gen = self.refresh_batches(self.index)
+            self._gen = self.embed_batches(self.index) if self.in_place else self.refresh_batches(self.index)
         self.done_event = None
 
     def pump(self, n_batches=None):
         """Enqueue up to n re-embedding batches on the side stream; returns True once the whole shard has been enqueued."""
+        n = self.batches_per_pump if n_batches is None else n_batches
+        if self.in_place:
+            return self._pump_in_place(n)
         if self._gen is None:
             return True
-        n = self.batches_per_pump if n_batches is None else n_batches
         with torch.cuda.stream(self.stream):
             for _ in range(n):
                 try:
@@ -79,12 +89,66 @@ class AsyncIndexBuilder(IndexBuilder):
                     return True
         return False
 
+    def _pump_in_place(self, n):
+        """Rolling mode: embed up to n batches on the side stream into ONE contiguous staging tensor and queue it, with an event, for the
+        next step boundary.  Returns True when this call reached the end of the shard: the builder has then taken the next weight snapshot
+        and restarted at once -- no collective: ranks finish on different steps and need not agree."""
+        lo, hi = self.index.local_rows()
+        staging, first, filled, finished = None, None, 0, False
+        with torch.cuda.stream(self.stream):
+            for _ in range(n):
+                try:
+                    start, emb = next(self._gen)
+                except StopIteration:
+                    finished = True
+                    break
+                if staging is None:
+                    first = start
+                    staging = torch.empty((min(n * self.batch_size, hi - start), emb.shape[1]), dtype=torch.float16, device=emb.device)
+                staging[filled:filled + emb.shape[0]].copy_(emb)
+                filled += emb.shape[0]
+                if start + emb.shape[0] >= hi:
+                    finished = True
+                    break
+            if staging is not None:
+                event = torch.cuda.Event()
+                event.record(self.stream)
+                self._queued.append((first, staging[:filled], event))
+        if finished:
+            self.passes += 1
+            self.start()
+        return finished
+
+    def _apply_queued(self):
+        """At a step boundary: everything pumped so far goes into the live image, in order, on the current stream.  What is applied at a
+        step is a function of the step number alone -- never of how far the side stream happens to have got."""
+        cur = torch.cuda.current_stream()
+        for first, staging, event in self._queued:
+            cur.wait_event(event)                               # the side stream has had the whole step: this rarely waits
+            self.index.update_rows(first, staging)
+            staging.record_stream(cur)                          # allocated on the side stream, consumed here: not reused before the update has run
+        self._queued = []
+
     def ready(self):
         return self._gen is None and self.done_event is not None and self.done_event.query()
 
     def maybe_swap(self, iteration, force=False):
         """At a step boundary: if the pass is complete (on every rank) and the reload interval has gone by, swap in the new image and
         start the next pass.  Returns True when the index was updated."""
+        if self.in_place:
+            # Rolling mode.  The rows go in at EVERY boundary; the return value keeps the reference's cadence on the rank-uniform interval
+            # condition alone (the training loop logs and checkpoints on it: a collective save cannot be entered by some ranks only).
+            self._apply_queued()
+            while force:                                        # drain the current pass, a pump at a time (the staging tensor stays small)
+                done = self._pump_in_place(self.batches_per_pump)
+                self._apply_queued()
+                if done:
+                    break
+            if not force and iteration < self.last_reload_iteration + self.index_reload_interval:
+                return False
+            self.refreshes += 1
+            self.last_reload_iteration = iteration
+            return True
         # Only rank-uniform conditions may return before the collective below: `iteration`, `force` and the interval are the same on every
         # rank, the state of this rank's pass is not (the last shard is shorter, so ranks finish their passes on different steps).
         if not force and iteration < self.last_reload_iteration + self.index_reload_interval:

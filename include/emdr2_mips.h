@@ -172,6 +172,26 @@ int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t
                              size_t workspace_bytes, emdr2_stream_t stream);
 int emdr2_mips_shadow_launches(void);
 
+/*
+ * In-place row updates of a FINISHED shard (the device counterpart of the reference store's add_block_data(..., allow_overwrite=True)):
+ * every derived structure is left exactly as a fresh build of the same rows would leave it.
+ *   _block_norm_bytes  size of the block-norm table: one float per 256-row block of the padded image
+ *   _block_norms       (re)builds entries [first_block, first_block + n_blocks) from the image: entry b = max over the block's rows of
+ *                      ||E[r]||_2^2 (rows past n_rows are zero).  Called once over the whole table before the first update.
+ *   _update_rows       writes rows_rm (device fp16 [n_chunk, dim]) into image rows [row_offset, row_offset + n_chunk), rewrites the table
+ *                      entries of the blocks they touch, sets *emax_sq to the maximum of the WHOLE table -- bit for bit what _pack_rows
+ *                      leaves after a fresh build of the same rows, so it falls when the row that held the maximum is overwritten -- and,
+ *                      with shadow != NULL, re-seals exactly the touched blocks of the int8 shadow image and its table with the arithmetic
+ *                      of _seal_shadow, OR-ing 1 into *nonfinite (device uint32) if one of them holds an inf / NaN.  A few small launches
+ *                      on `stream`; nothing allocated, no host synchronisation.  The caller orders it against searches of the shard.
+ *                      n_chunk == 0 is a no-op.  shadow == NULL: table and nonfinite are ignored.
+ */
+int emdr2_mips_block_norm_bytes(int64_t n_rows, size_t *bytes);
+int emdr2_mips_block_norms(const void *tiled, int64_t n_rows, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq,
+                           emdr2_stream_t stream);
+int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
+                           float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream);
+
 /* Diagnostics for tests: fp32 MFMA scores S~[n_q, n_rows] (row-major float) of the scan kernel's
  * arithmetic, for measuring |S~ - exact| against the bound used by the validity check. */
 int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const void *queries, int n_q,
