@@ -25,6 +25,8 @@ SIGNATURES = {
     "emdr2_mips_layout_bytes": (_i32, [_i64, _i32, ctypes.POINTER(_sz)]),
     "emdr2_mips_pack_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp]),
     "emdr2_mips_unpack_rows": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "emdr2_mips_export_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp]),
+    "emdr2_mips_digest_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp]),
     "emdr2_mips_workspace_bytes": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_sz)]),
     "emdr2_mips_search": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_exact_workspace_bytes": (_i32, [_i64, _i32, ctypes.POINTER(_sz)]),

@@ -117,6 +117,14 @@ def get_parser():
                         'semantics, not a tuning knob: searches then see a MIX of two embedding generations -- rows already re-embedded in '
                         'the current pass next to rows of the pass before -- where the default, the reference\'s update_index, replaces '
                         'the whole index atomically')
+    g.add_argument('--save-index-snapshot', action='store_true',
+                   help='(not in the reference; needs --save) with --async-indexer: after every index update write the index just committed '
+                        'to the one file <save>/evidence_index.flat (+ .meta), overwritten atomically like the reference\'s embedding file, a '
+                        'chunk per step; with --load, start from <load>/evidence_index.flat when its meta is valid, fits the evidence and is '
+                        'not newer than the checkpoint, else from --embedding-path as without the flag.  Swap mode: the live index does not '
+                        'change between swaps, so a resumed run searches exactly what the uninterrupted run searched at that step; the '
+                        'refresher\'s in-flight pass is not saved and restarts.  With --index-refresh-in-place the snapshot is a mix of '
+                        'embedding generations, as the live index is, and the pass cursor is not saved')
     g.add_argument('--indexer-batch-size', type=int, default=128)
     g.add_argument('--indexer-log-interval', type=int, default=1000)
     g.add_argument('--report-topk-accuracies', nargs='+', type=int, default=[])
@@ -144,6 +152,8 @@ def parse_args(argv=None):
         args.eval_batch_size = args.batch_size
     if args.load and args.ict_load:
         raise ValueError("--load and --ict-load are exclusive (indexer_emdr2.py:47)")
+    if args.save_index_snapshot and not args.save:
+        raise ValueError("--save-index-snapshot needs --save (the snapshot lives next to the checkpoints)")
     args.iteration = 0
     # the reference's --fp16 (fp16 activations, fp32 masters inside FP16_Optimizer, dynamic loss scaling) maps to this build's ONLY
     # precision mode: bf16 activations and working weights, fp32 master weights and gradients, no loss scaling.  Said once, recorded in args.

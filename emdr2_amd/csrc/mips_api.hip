@@ -119,6 +119,23 @@ int emdr2_mips_unpack_rows(const void *tiled, int64_t n_rows_total, int dim, con
     return mips_launch_unpack_rows(tiled, dim, row_ids, n_out, rows_rm, (hipStream_t)stream);
 }
 
+int emdr2_mips_export_rows(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm,
+                           emdr2_stream_t stream)
+{
+    if (!tiled || !rows_rm || bad_shape(n_rows_total, dim) || n_chunk < 0 || row_offset < 0 || row_offset + n_chunk > n_rows_total)
+        return EMDR2_E_BADARG;
+    return mips_launch_export_rows(tiled, dim, row_offset, n_chunk, rows_rm, (hipStream_t)stream);
+}
+
+int emdr2_mips_digest_rows(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                           uint64_t *digest, emdr2_stream_t stream)
+{
+    if (!tiled || !digest || ((uintptr_t)digest & 7) || bad_shape(n_rows_total, dim) || n_chunk < 0 || row_offset < 0 ||
+        row_offset + n_chunk > n_rows_total)
+        return EMDR2_E_BADARG;
+    return mips_launch_digest_rows(tiled, dim, row_offset, n_chunk, row_base, digest, (hipStream_t)stream);
+}
+
 int emdr2_mips_workspace_bytes(int n_q, int dim, int k, size_t *bytes)
 {
     if (!bytes || n_q < 1 || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(0, dim)) return EMDR2_E_BADARG;

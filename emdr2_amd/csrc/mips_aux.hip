@@ -149,6 +149,100 @@ int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// index snapshots (emdr2_mips_export_rows / _digest_rows): a contiguous row range back to row-major, and its order-free 64-bit digest
+// ------------------------------------------------------------------------------------------------
+// The inverse of pack_rows_kernel for rows [row_lo, row_hi).  Eight lanes move one row's two neighbouring chunks: eight rows of a wave
+// read 512 contiguous bytes of each of the two 8 KiB blocks (the swizzle only permutes the four 16-byte slots inside a row's 64 bytes)
+// and write 128 contiguous bytes of each output row.  Row groups are aligned to 8 image rows, whatever row_lo is.
+__global__ void __launch_bounds__(256) export_rows_kernel(const char *__restrict__ tiled, int nch, int npairs, int64_t row_lo, int64_t row_hi,
+                                                          int64_t n_items, uint4 *__restrict__ rows_rm)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_items) return;
+    const int j = (int)(i & 7), rl = (int)((i >> 3) & 7);
+    const int64_t q = i >> 6;
+    const int64_t group = q / npairs;
+    const int pair = (int)(q - group * npairs);
+    const int64_t row = (row_lo & ~(int64_t)7) + group * 8 + rl;
+    const int seg = pair * 8 + j;
+    if (row < row_lo || row >= row_hi || seg >= nch * 4) return;
+    rows_rm[(row - row_lo) * (nch * 4) + seg] = *(const uint4 *)(tiled + tiled_seg_offset(row, seg, nch));
+}
+
+int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream)
+{
+    if (n_chunk == 0) return 0;
+    const int nch = dim / 32, npairs = (nch + 1) / 2;
+    const int64_t groups = ((row_offset + n_chunk + 7) >> 3) - (row_offset >> 3);
+    const int64_t items = groups * npairs * 64;
+    hipLaunchKernelGGL(export_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const char *)tiled, nch, npairs,
+                       row_offset, row_offset + n_chunk, items, (uint4 *)rows_rm);
+    return CHECK_LAUNCH();
+}
+
+// splitmix64's finaliser (include/emdr2_mips.h states the digest in full)
+__device__ __forceinline__ uint64_t digest_mix(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o)
+{
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// One workgroup per 128-row stripe, walking it in storage order: chunk after chunk, one contiguous 8 KiB block each (thread t takes the
+// 16-byte slots t and t + 256: rows t / 4 and 64 + t / 4).  acc(r) is a sum over position-tagged words, so a thread keeps one partial sum
+// for each of its two rows across all chunks, whatever slot the swizzle hands it; the four lanes of a row then fold their partial sums,
+// each row is finished once, and the workgroup issues ONE 64-bit add and ONE 64-bit xor.  Rows outside [row_lo, row_hi) -- the rest of a
+// partly covered stripe, the zero padding past the shard's end -- are read and left out.
+__global__ void __launch_bounds__(256) digest_rows_kernel(const char *__restrict__ tiled, int nch, int64_t first_stripe, int64_t row_lo, int64_t row_hi,
+                                                          int64_t row_base, unsigned long long *__restrict__ digest)
+{
+    __shared__ uint64_t sh_sum[4], sh_xor[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t stripe = first_stripe + blockIdx.x;
+    const uint4 *block = (const uint4 *)(tiled + (size_t)stripe * nch * STRIPE_CHUNK_BYTES);
+    const int ri = tid >> 2, sp = tid & 3;                            // (row 64 + ri has the same swizzle: bits 2..3 of the row agree)
+    const int s = sp ^ ((ri >> 2) & 3);
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll 2
+    for (int c = 0; c < nch; ++c) {
+        const uint4 a = block[(size_t)c * 512 + tid], b = block[(size_t)c * 512 + 256 + tid];
+        const uint64_t tag = (uint64_t)((c * 4 + s) * 4 + 1) << 32;    // word j of the row carries (j + 1) << 32
+        acc0 += digest_mix(a.x | tag) + digest_mix(a.y | (tag + (1ull << 32))) + digest_mix(a.z | (tag + (2ull << 32))) + digest_mix(a.w | (tag + (3ull << 32)));
+        acc1 += digest_mix(b.x | tag) + digest_mix(b.y | (tag + (1ull << 32))) + digest_mix(b.z | (tag + (2ull << 32))) + digest_mix(b.w | (tag + (3ull << 32)));
+    }
+    acc0 += shfl_xor_u64(acc0, 1); acc0 += shfl_xor_u64(acc0, 2);
+    acc1 += shfl_xor_u64(acc1, 1); acc1 += shfl_xor_u64(acc1, 2);
+    uint64_t sum = 0, x = 0;
+    if (sp == 0) {
+        const int64_t r0 = stripe * STRIPE_ROWS + ri, r1 = r0 + 64;
+        if (r0 >= row_lo && r0 < row_hi) { const uint64_t g = digest_mix(acc0 ^ ((uint64_t)(row_base + r0 + 1) * 0x9E3779B97F4A7C15ull)); sum += g; x ^= g; }
+        if (r1 >= row_lo && r1 < row_hi) { const uint64_t g = digest_mix(acc1 ^ ((uint64_t)(row_base + r1 + 1) * 0x9E3779B97F4A7C15ull)); sum += g; x ^= g; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sum += shfl_xor_u64(sum, o); x ^= shfl_xor_u64(x, o); }
+    if (lane == 0) { sh_sum[wave] = sum; sh_xor[wave] = x; }
+    __syncthreads();
+    if (tid == 0) {
+        atomicAdd(&digest[0], (unsigned long long)(sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3]));
+        atomicXor(&digest[1], (unsigned long long)(sh_xor[0] ^ sh_xor[1] ^ sh_xor[2] ^ sh_xor[3]));
+    }
+}
+
+int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream)
+{
+    if (n_chunk == 0) return 0;
+    const int64_t first = row_offset / STRIPE_ROWS, last = (row_offset + n_chunk - 1) / STRIPE_ROWS;
+    hipLaunchKernelGGL(digest_rows_kernel, dim3((unsigned)(last - first + 1)), dim3(256), 0, stream, (const char *)tiled, dim / 32, first, row_offset,
+                       row_offset + n_chunk, row_base, (unsigned long long *)digest);
+    return CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------
 // query packing: [n_q, dim] row-major -> per chunk a [bn rows x 64 B] swizzled block (zero padded)
 // ------------------------------------------------------------------------------------------------
 __global__ void pack_queries_kernel(const uint4 *__restrict__ queries, int n_q, int nseg, int bn, char *__restrict__ q_tiled,

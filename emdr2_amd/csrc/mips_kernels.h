@@ -67,6 +67,9 @@ int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int
 int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream);
 int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, int64_t n_out, void *rows_rm,
                             hipStream_t stream);
+// index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
+int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
+int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
 // queries row-major fp16 [n_q, dim] -> chunk-tiled image for BN rows (zero padded) + ||q||_2 upper bounds
 int mips_launch_pack_queries(const void *queries, int n_q, int dim, int bn, void *q_tiled, float *qnorm,
                              hipStream_t stream);

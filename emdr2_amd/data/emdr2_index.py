@@ -145,13 +145,51 @@ class OpenRetreivalDataStore(object):
 FLAT_MAGIC = b'EMDR2EMB'
 
 
+# ---- row digest (include/emdr2_mips.h: emdr2_mips_digest_rows states it in full; this is its numpy restatement) -------------------
+_U64 = np.uint64
+_DIGEST_BLOCK_ROWS = 1 << 16
+
+
+def _digest_mix(z):
+    z = (z ^ (z >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> _U64(27))) * _U64(0x94D049BB133111EB)
+    return z ^ (z >> _U64(31))
+
+
+def digest_rows(rows, first_row_number=0):
+    """(sum, xor) over the rows of fp16 `rows` [n, dim] of g(r), row i numbered `first_row_number + i`; Python ints below 2^64.  Bits are
+    hashed, not values.  numpy on the host: an offline and test instrument (seconds per 2^18 x 768 rows), never a load path."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.float16 or rows.ndim != 2 or rows.shape[1] % 2:
+        raise ValueError("rows must be float16 [n, even dim]")
+    total, x = _U64(0), _U64(0)
+    tags = np.arange(1, rows.shape[1] // 2 + 1, dtype=_U64) << _U64(32)
+    with np.errstate(over='ignore'):
+        for lo in range(0, rows.shape[0], _DIGEST_BLOCK_ROWS):
+            block = np.ascontiguousarray(rows[lo:lo + _DIGEST_BLOCK_ROWS])
+            acc = _digest_mix(block.view('<u4').astype(_U64) | tags).sum(axis=1, dtype=_U64)
+            number = np.arange(first_row_number + lo + 1, first_row_number + lo + 1 + block.shape[0], dtype=np.int64).astype(_U64)
+            g = _digest_mix(acc ^ (number * _U64(0x9E3779B97F4A7C15)))
+            total = total + g.sum(dtype=_U64)
+            x = x ^ np.bitwise_xor.reduce(g)
+    return int(total), int(x)
+
+
+def combine_digests(pairs):
+    """Digests of disjoint row sets -> the digest of their union: sums add mod 2^64, xors xor."""
+    total, x = 0, 0
+    for s, v in pairs:
+        total, x = (total + int(s)) & (2 ** 64 - 1), x ^ int(v)
+    return total, x
+
+
 class FlatEmbeddingFile(object):
     """`[N, D]` fp16 rows + int32 doc ids in one memory-mappable file, as an alternative to the reference's pickle of N tiny arrays
     (32 GB, minutes to unpickle per reload).  Layout: 8-byte magic | u32 version = 1 | u32 D | u64 N | int32 ids[N] | pad to 4096 |
     fp16 rows[N, D].  Row order = the pickle's dict order, so an index built from either file is identical; `from_store` / `to_store`
     convert in both directions so `--embedding-path` artefacts interoperate with the reference."""
 
-    def __init__(self, path):
+    def __init__(self, path, mode='r'):
         import struct
         self.path = path
         with open(path, 'rb') as f:
@@ -162,8 +200,38 @@ class FlatEmbeddingFile(object):
                 raise ValueError("unsupported flat embedding file version %d" % version)
         self._ids_off = 24
         self._rows_off = (self._ids_off + 4 * self.n + 4095) // 4096 * 4096
-        self.ids = np.memmap(path, dtype=np.int32, mode='r', offset=self._ids_off, shape=(self.n,))
-        self.rows = np.memmap(path, dtype=np.float16, mode='r', offset=self._rows_off, shape=(self.n, self.dim))
+        if os.path.getsize(path) < self._rows_off + 2 * self.n * self.dim:
+            raise ValueError("flat embedding file is shorter than its header says: %s" % path)
+        # (numpy cannot map zero bytes: an empty file gets plain empty arrays)
+        self.ids = np.memmap(path, dtype=np.int32, mode=mode, offset=self._ids_off, shape=(self.n,)) if self.n else np.empty((0,), np.int32)
+        self.rows = (np.memmap(path, dtype=np.float16, mode=mode, offset=self._rows_off, shape=(self.n, self.dim)) if self.n * self.dim
+                     else np.empty((self.n, self.dim), np.float16))
+
+    @classmethod
+    def create(cls, path, n, dim):
+        """Header + a file of full size (zeros, sparse where the file system allows), opened WRITABLE: `ids` and `rows` are `r+` memory
+        maps, so several processes -- each through its own `FlatEmbeddingFile(path, mode='r+')` -- can fill disjoint row slices.  Layout
+        and version are those of `write`."""
+        import struct
+        n, dim = int(n), int(dim)
+        with open(path, 'wb') as f:
+            f.write(FLAT_MAGIC)
+            f.write(struct.pack('<IIQ', 1, dim, n))
+            f.truncate((24 + 4 * n + 4095) // 4096 * 4096 + 2 * n * dim)
+        return cls(path, mode='r+')
+
+    def flush(self):
+        for a in (self.ids, self.rows):
+            if isinstance(a, np.memmap):
+                a.flush()
+
+    def digest(self, lo=0, hi=None, row_base=None):
+        """(sum, xor) digest of rows [lo, hi) as the device computes it (`HipIndexShard.digest`, emdr2_mips_digest_rows): row r of the
+        file is numbered `row_base + r` (row_base None: 0, the file holds the whole index from its first row).  Blocks of 2^16 rows."""
+        hi = self.n if hi is None else hi
+        if not (0 <= lo <= hi <= self.n):
+            raise ValueError("rows [%d, %d) are not in [0, %d]" % (lo, hi, self.n))
+        return digest_rows(self.rows[lo:hi], (row_base or 0) + lo)
 
     @staticmethod
     def write(path, ids, rows):
@@ -629,6 +697,48 @@ class HipIndexShard(object):
                                                       out.data_ptr(), _native.stream_ptr()), "unpack_rows")
         return out
 
+    # -- snapshots: the way out of HBM (emdr2_mips_export_rows / _digest_rows) ---------------------------------------------------------
+    def _check_range(self, local_row, n):
+        if self._filled != self.n_rows:
+            raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
+        if local_row < 0 or n < 0 or local_row + n > self.n_rows:
+            raise ValueError("rows [%d, %d) are not in this shard's [0, %d)" % (local_row, local_row + n, self.n_rows))
+
+    def export_rows(self, local_row, n, out=None):
+        """Rows [local_row, local_row + n) of the LIVE image as row-major CUDA fp16 [n, dim], enqueued on the current stream -- the inverse
+        of `append_rows` for a contiguous range, without a row-id array.  `out`: a contiguous CUDA fp16 buffer of at least n rows to
+        write into (its first n rows are returned)."""
+        local_row, n = int(local_row), int(n)
+        self._check_range(local_row, n)
+        if out is None:
+            out = torch.empty((n, self.dim), dtype=torch.float16, device=self.device)
+        elif out.dtype != torch.float16 or out.dim() != 2 or out.shape[1] != self.dim or out.shape[0] < n or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA float16 [>= %d, %d] tensor" % (n, self.dim))
+        out = out[:n]
+        if n:
+            _native.check(self.lib.emdr2_mips_export_rows(self.tiled.data_ptr(), self.n_rows, self.dim, local_row, n, out.data_ptr(),
+                                                          _native.stream_ptr()), "export_rows")
+        return out
+
+    def digest_into(self, acc, local_row=0, n=None):
+        """Fold the digest of rows [local_row, local_row + n) into `acc` (CUDA int64 [2], zeroed by the caller: the bit patterns of the
+        uint64 sum and xor) on the current stream; no readback.  Rows are numbered `row_base + local row`."""
+        n = self.n_rows - local_row if n is None else int(n)
+        self._check_range(int(local_row), n)
+        if acc.dtype != torch.int64 or acc.numel() != 2 or not acc.is_cuda or not acc.is_contiguous():
+            raise ValueError("acc must be a contiguous CUDA int64 [2] tensor")
+        if n:
+            _native.check(self.lib.emdr2_mips_digest_rows(self.tiled.data_ptr(), self.n_rows, self.dim, int(local_row), n, self.row_base,
+                                                          acc.data_ptr(), _native.stream_ptr()), "digest_rows")
+        return acc
+
+    def digest(self, local_row=0, n=None):
+        """(sum, xor) digest of rows [local_row, local_row + n) of the live image (default: the whole shard) as Python ints; equals
+        `FlatEmbeddingFile.digest` of the same rows under the same numbering.  One readback."""
+        acc = self.digest_into(torch.zeros(2, dtype=torch.int64, device=self.device), local_row, n)
+        s, x = acc.tolist()
+        return s & (2 ** 64 - 1), x & (2 ** 64 - 1)
+
 
 def merge_shard_results(dist, idx, row):
     """[S, Q, k] per-shard canonical lists (device) -> merged [Q, k] via the HIP merge kernel."""
@@ -762,6 +872,35 @@ class DistributedBruteForceIndex(object):
         if isinstance(flat, str):
             flat = FlatEmbeddingFile(flat)
         self.add_arrays(flat.ids, flat.rows)
+
+    # -- snapshots (data/index_snapshot.py) ----------------------------------------------------------------------------------------------
+    def save_flat_file(self, path, meta=None):
+        """Write the index as it stands in HBM to the `FlatEmbeddingFile` `path` plus `path + '.meta'` (JSON: format, n, dim, world, the
+        DEVICE digest of what was exported, ids_crc32, and the caller's `meta`: iteration / refreshes / mode).  Collective and synchronous;
+        the file appears atomically and a data file without a meta is an incomplete snapshot.  After `IndexBuilder.build_into_index` this
+        is the fast offline indexer."""
+        from emdr2_amd.data.index_snapshot import IndexSnapshotWriter
+        writer = IndexSnapshotWriter(self, chunk_rows=min(_UPLOAD_ROWS, 1 << 18))
+        writer.begin(path, meta)
+        writer.finish()
+
+    def load_flat_snapshot(self, path):
+        """Build the index from a snapshot written by `save_flat_file` at ANY world size and verify it: meta against the file's header
+        and ids, then the device digest of what now stands in HBM (combined over the ranks) against the meta's.  A mismatch raises
+        ValueError.  Returns the meta."""
+        from emdr2_amd.data import index_snapshot as snap
+        meta = snap.read_snapshot_meta(path)
+        flat = FlatEmbeddingFile(path)
+        if flat.dim != self.embed_size:
+            raise ValueError("snapshot rows have %d elements, the index %d" % (flat.dim, self.embed_size))
+        if snap.ids_crc32(flat.ids) != meta.get("ids_crc32"):
+            raise ValueError("index snapshot %s: the doc ids do not match the meta's checksum" % path)
+        self.add_flat_file(flat)
+        got = snap.index_digest(self)
+        want = (int(meta["digest_sum"], 16), int(meta["digest_xor"], 16))
+        if got != want:
+            raise ValueError("index snapshot %s: digest %016x %016x in HBM, %016x %016x in the meta" % ((path,) + got + want))
+        return meta
 
     def add_arrays(self, ids, rows):
         if rows.dtype != np.float16 or rows.shape[1] != self.embed_size:

@@ -136,3 +136,10 @@ class IndexBuilder(object):
         torch.cuda.current_stream().synchronize()
         self._barrier()
         index.commit_refresh()
+
+    def build_and_save_snapshot(self, index, path, in_place=False):
+        """The fast offline indexer (all ranks call it): `build_into_index`, then the index goes from HBM to ONE flat file + meta
+        (`DistributedBruteForceIndex.save_flat_file`; `FlatEmbeddingFile.to_store` turns it into the reference's pickle) -- where
+        `build_and_save_index` pickles 21 M small arrays per full index."""
+        self.build_into_index(index, in_place=in_place)
+        index.save_flat_file(path, meta={'mode': 'build'})

@@ -50,10 +50,48 @@ class PreComputedEvidenceDocsRetriever(object):
             self.get_evidence_embedding(self.args.embedding_path)
         else:
             self.evidence_embedder_obj = embed_data
+        if embed_data is None and self._resume_from_snapshot():
+            return
         self.mips_index = DistributedBruteForceIndex(embed_size=self.embedding_size, embed_data=self.evidence_embedder_obj,
                                                      use_gpu=getattr(self.args, "faiss_use_gpu", True),
                                                      process_group=self.process_group)
         self._barrier()
+
+    def _resume_from_snapshot(self):
+        """--save-index-snapshot with --load: build the index from `<load>/evidence_index.flat` -- the index the checkpointed run was
+        searching -- when its meta is valid, fits the evidence and is not newer than the checkpoint.  Every rank reads the same files and
+        the digest check is combined over the ranks, so all decide alike.  Returns False (after one log line saying why) when
+        `--embedding-path` is to be loaded as without the flag."""
+        import os
+        from emdr2_amd import checkpointing
+        from emdr2_amd.data.index_snapshot import SNAPSHOT_NAME, read_snapshot_meta
+        args = self.args
+        if not getattr(args, "save_index_snapshot", False) or not getattr(args, "load", None):
+            return False
+        path = os.path.join(args.load, SNAPSHOT_NAME)
+        rank0 = not (torch.distributed.is_available() and torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
+        say = (lambda msg: print(msg, flush=True)) if rank0 else (lambda msg: None)
+        index = None
+        try:
+            meta = read_snapshot_meta(path)
+            iteration = checkpointing.read_tracker(args.load)[0]
+            n_docs = getattr(self.arena, "n_docs", None)
+            if meta["dim"] != self.embedding_size or (n_docs is not None and meta["n"] != n_docs):
+                raise ValueError("it holds %d x %d rows, the evidence needs %s x %d" % (meta["n"], meta["dim"], n_docs, self.embedding_size))
+            if int(meta.get("iteration", 0)) > iteration:
+                raise ValueError("it was taken at iteration %d, the checkpoint at %d" % (int(meta.get("iteration", 0)), iteration))
+            index = DistributedBruteForceIndex(embed_size=self.embedding_size, embed_data=None, use_gpu=getattr(args, "faiss_use_gpu", True),
+                                               process_group=self.process_group)
+            index.load_flat_snapshot(path)
+        except (OSError, ValueError) as exc:
+            say("index snapshot %s not used (%s): loading %s" % (path, exc, args.embedding_path))
+            return False
+        index.embed_data = self.evidence_embedder_obj           # (`update_index()` still reloads --embedding-path, like the reference)
+        self.mips_index = index
+        say("index snapshot %s loaded: the index of iteration %s (%s mode, digest %s %s)"
+            % (path, meta.get("iteration"), meta.get("mode"), meta["digest_sum"], meta["digest_xor"]))
+        self._barrier()
+        return True
 
     def update_evidence_embedding(self, from_refresh=False):
         """Swap in new evidence embeddings after an indexer job (emdr2_model.py:426-432): reload --embedding-path like the reference, or

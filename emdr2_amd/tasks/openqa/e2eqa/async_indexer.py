@@ -19,6 +19,11 @@ Rolling mode (`in_place=True`, --index-refresh-in-place; not in the reference): 
 the image that is being searched at the next step boundary (`index.update_rows`), so the index costs its own size in HBM instead of twice
 that, and a row serves weights that are on average one pass old instead of one and a half.  Searches then see a mix of two embedding
 generations: a choice of semantics, which is why the atomic swap stays the default.
+
+Snapshots (`--save-index-snapshot`, not in the reference): the reference's indexer group leaves every refreshed index on disk; here it
+would exist in HBM only.  With a `snapshot_writer` (data/index_snapshot.IndexSnapshotWriter, driven by train_e2eqa._train) the index just
+committed is exported to one flat file, a chunk per step boundary.  A snapshot still open when the next swap is due is finished first
+(`maybe_swap`): the image it reads becomes the spare at the swap, and the next pass clears the spare.
 """
 import copy
 
@@ -45,6 +50,8 @@ class AsyncIndexBuilder(IndexBuilder):
         self.in_place = bool(in_place)
         self._queued = []                                       # rolling mode: (first global row, staging rows, event) not yet applied
         self.passes = 0                                         # rolling mode: completed passes over the shard
+        self.snapshot_writer = None                             # --save-index-snapshot: an IndexSnapshotWriter over `index` (train_e2eqa._train)
+        self.log = lambda msg: print(msg, flush=True) if self.is_main_builder else None
         self.index_reload_interval = index_reload_interval
         lo, hi = index.local_rows()
         n_batches = (hi - lo + batch_size - 1) // batch_size
@@ -162,6 +169,12 @@ class AsyncIndexBuilder(IndexBuilder):
         if int(flag.item()) == 0:
             return False
         torch.cuda.current_stream().wait_event(self.done_event)        # searches after this point see the finished image
+        writer = self.snapshot_writer
+        if writer is not None and writer.active:
+            # (rank-uniform: a snapshot begins and ends in collectives.)  The image being exported becomes the spare at the swap and the
+            # next pass clears it: what is left of the snapshot is written now, at the cost of one slow step
+            self.log("Training Group: finishing the open index snapshot before the swap at iteration {}".format(iteration))
+            writer.finish()
         self.index.commit_refresh()
         self.refreshes += 1
         self.last_reload_iteration = iteration

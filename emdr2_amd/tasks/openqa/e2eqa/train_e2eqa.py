@@ -1,5 +1,6 @@
 """Training-step driver of the QA task (reference: tasks/openqa/e2eqa/train_e2eqa.py:28-41,126-181 and
 megatron/training.py:165-230).  Same forward-step contract: forward_step(batch_or_iter, model) -> (loss, {'lm_loss', 'retriever_loss'})."""
+import os
 import time
 
 import torch
@@ -220,6 +221,15 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
         guard = RetentionGuard(model, optimizer, keep=keep, reader=sel[0], context=sel[1], query=sel[2],
                                forward_progress=(lambda: getattr(retr, "searches", 0)) if retr is not None else None, log=print_rank_0,
                                micro=micro, batch=args.batch_size, on_micro_change=set_micro)
+    snapshots = None
+    if indexer is not None and getattr(args, "save_index_snapshot", False) and args.save:
+        # --save-index-snapshot: the index just committed goes to <save>/evidence_index.flat, a chunk per step boundary, paced to cover the
+        # shard in half a reload interval (data/index_snapshot.py)
+        from emdr2_amd.data.index_snapshot import SNAPSHOT_NAME, IndexSnapshotWriter
+        lo, hi = indexer.index.local_rows()
+        snapshots = indexer.snapshot_writer = IndexSnapshotWriter(
+            indexer.index, chunk_rows=IndexSnapshotWriter.paced_chunk_rows(hi - lo, args.index_reload_interval), log=print_rank_0)
+        snapshot_path = os.path.join(args.save, SNAPSHOT_NAME)
     start_epoch = args.iteration // args.train_iters_per_epoch
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
@@ -239,6 +249,15 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 print_rank_0("Training Group: MIPS Index Updated at iteration {}".format(iteration))
                 if args.save:
                     _save(iteration, model, optimizer, lr_scheduler)                          # the reference checkpoints at every reload
+                if snapshots is not None:
+                    if snapshots.active:        # (rolling mode; before a swap, maybe_swap has finished it)
+                        print_rank_0("Training Group: finishing the open index snapshot before the next at iteration {}".format(iteration))
+                        snapshots.finish()
+                    snapshots.begin(snapshot_path, {"iteration": iteration, "refreshes": indexer.refreshes,
+                                                    "mode": "rolling" if indexer.in_place else "swap"})
+            if snapshots is not None:
+                snapshots.pump()
+                snapshots.maybe_finalize(iteration)
             for k, v in losses.items():
                 sums[k] = sums.get(k, 0.0) + v
             if iteration % args.log_interval == 0:
@@ -259,9 +278,13 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 print_rank_0('exiting the program at iteration {}'.format(iteration))
                 if args.save:
                     _save(iteration, model, optimizer, lr_scheduler)
+                if snapshots is not None:
+                    snapshots.finish()
                 return iteration
         if args.save:
             _save(iteration, model, optimizer, lr_scheduler)
+        if snapshots is not None:
+            snapshots.finish()                        # (a no-op when none is open)
         if end_of_epoch_callback is not None:
             end_of_epoch_callback(model, epoch + 1)
             end_of_epoch_callback2(model, epoch + 1)

@@ -72,6 +72,27 @@ int emdr2_mips_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t 
 int emdr2_mips_unpack_rows(const void *tiled, int64_t n_rows_total, int dim, const int64_t *row_ids,
                            int64_t n_out, void *rows_rm, emdr2_stream_t stream);
 
+/*
+ * Index snapshots: a contiguous row range of a shard image back out of HBM, and its digest.
+ *   _export_rows  the inverse of _pack_rows for image rows [row_offset, row_offset + n_chunk): rows_rm (device fp16 [n_chunk, dim],
+ *                 row-major) receives them.  No row-id array, nothing allocated.
+ *   _digest_rows  adds into digest[0] (wrap-around sum) and XORs into digest[1] the 64-bit hash g(r) of every row r of the range
+ *                 (device uint64[2], zeroed by the caller before the first range).  All arithmetic on uint64, mod 2^64:
+ *                     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *                     w[j]   = the j-th little-endian 32-bit word of the row's dim * 2 bytes (element 2j in the low half), j < dim / 2
+ *                     acc(r) = sum over j of mix( w[j] | ((j + 1) << 32) )
+ *                     g(r)   = mix( acc(r) ^ ((row_base + r + 1) * 0x9E3779B97F4A7C15) )
+ *                 Bits are hashed, not values.  A sum and an XOR over rows: the digest of a shard does not depend on how it is cut into
+ *                 ranges or ranks (row_base = the global number of image row 0), and integer atomics give the same bits in any order.
+ *                 The zero padding past n_rows_total never enters.
+ * Both: n_chunk == 0 is a no-op returning 0; EMDR2_E_BADARG for null pointers, a dim outside the layout's envelope, or a range outside
+ * [0, n_rows_total].
+ */
+int emdr2_mips_export_rows(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm,
+                           emdr2_stream_t stream);
+int emdr2_mips_digest_rows(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                           uint64_t *digest, emdr2_stream_t stream);
+
 /* Workspace bytes for emdr2_mips_search with up to n_q queries (per call) and this k. */
 int emdr2_mips_workspace_bytes(int n_q, int dim, int k, size_t *bytes);
 
