@@ -405,77 +405,71 @@ int emdr2_mips_pack_records(const void *dist, const int32_t *idx, const int64_t 
     return mips_launch_pack_records(dist, idx, row, sel, n_sel, k, f32 ? 1 : 0, (uint4 *)records, (hipStream_t)stream);
 }
 
-int emdr2_mips_exact_workspace_bytes_f32(int64_t n_rows, int n_sel, size_t *bytes)
+// the all-exact fallback and the array merge, once for both score formats: the ordered keys of a pass take 2 (fp16) or 4 (fp32) bytes per row
+static int exact_workspace_impl(int64_t n_rows, int n_sel, size_t *bytes, size_t key_bytes)
 {
     if (!bytes || n_rows < 1 || n_sel < 0) return EMDR2_E_BADARG;
-    *bytes = align_up((size_t)8 * (size_t)n_rows * sizeof(uint32_t), 256);
+    *bytes = align_up((size_t)8 * (size_t)n_rows * key_bytes, 256);
     return EMDR2_OK;
+}
+
+static int search_exact_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const void *queries, int n_q, const int32_t *sel,
+                             int n_sel, int k, const int32_t *ids, void *out_dist, int32_t *out_idx, int64_t *out_row, uint32_t *out_flags,
+                             void *workspace, size_t workspace_bytes, emdr2_stream_t stream_, int f32)
+{
+    if (!tiled || !queries || !sel || !out_dist || !out_idx || !out_row || !out_flags || !workspace) return EMDR2_E_BADARG;
+    if (n_q < 1 || n_sel < 0 || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(n_rows, dim) || n_rows < 1) return EMDR2_E_BADARG;
+    if (workspace_bytes < (size_t)8 * (size_t)n_rows * (f32 ? sizeof(uint32_t) : sizeof(uint16_t))) return EMDR2_E_WORKSPACE;
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int b = 0; b < n_sel; b += 8) {
+        const int nb = (n_sel - b) < 8 ? (n_sel - b) : 8;
+        int rc;
+        if ((rc = mips_launch_exact_scores((const char *)tiled, n_rows, dim, (const uint16_t *)queries, sel + b, nb, f32, workspace, stream))) return rc;
+        if ((rc = mips_launch_exact_select(workspace, n_rows, row_base, sel + b, nb, k, ids, f32, out_dist, out_idx, out_row, out_flags, stream)))
+            return rc;
+    }
+    return EMDR2_OK;
+}
+
+static int merge_impl(const void *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k, void *out_dist,
+                      int32_t *out_idx, int64_t *out_row, emdr2_stream_t stream, int f32)
+{
+    if (!dist_in || !idx_in || !row_in || !out_dist || !out_idx || !out_row || n_shards < 1 || n_q < 1 || k < 1) return EMDR2_E_BADARG;
+    return mips_launch_merge(dist_in, idx_in, row_in, n_shards, n_q, k, f32, out_dist, out_idx, out_row, (hipStream_t)stream);
+}
+
+int emdr2_mips_exact_workspace_bytes(int64_t n_rows, int n_sel, size_t *bytes) { return exact_workspace_impl(n_rows, n_sel, bytes, sizeof(uint16_t)); }
+
+int emdr2_mips_exact_workspace_bytes_f32(int64_t n_rows, int n_sel, size_t *bytes) { return exact_workspace_impl(n_rows, n_sel, bytes, sizeof(uint32_t)); }
+
+int emdr2_mips_search_exact(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const void *queries,
+                            int n_q, const int32_t *sel, int n_sel, int k, const int32_t *ids, void *out_dist,
+                            int32_t *out_idx, int64_t *out_row, uint32_t *out_flags, void *workspace,
+                            size_t workspace_bytes, emdr2_stream_t stream)
+{
+    return search_exact_impl(tiled, n_rows, dim, row_base, queries, n_q, sel, n_sel, k, ids, out_dist, out_idx, out_row, out_flags, workspace,
+                             workspace_bytes, stream, 0);
 }
 
 int emdr2_mips_search_exact_f32(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const void *queries,
                                 int n_q, const int32_t *sel, int n_sel, int k, const int32_t *ids, float *out_dist,
                                 int32_t *out_idx, int64_t *out_row, uint32_t *out_flags, void *workspace,
-                                size_t workspace_bytes, emdr2_stream_t stream_)
+                                size_t workspace_bytes, emdr2_stream_t stream)
 {
-    if (!tiled || !queries || !sel || !out_dist || !out_idx || !out_row || !out_flags || !workspace) return EMDR2_E_BADARG;
-    if (n_q < 1 || n_sel < 0 || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(n_rows, dim) || n_rows < 1) return EMDR2_E_BADARG;
-    if (workspace_bytes < (size_t)8 * (size_t)n_rows * sizeof(uint32_t)) return EMDR2_E_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    for (int b = 0; b < n_sel; b += 8) {
-        const int nb = (n_sel - b) < 8 ? (n_sel - b) : 8;
-        int rc;
-        if ((rc = mips_launch_exact_scores_f32((const char *)tiled, n_rows, dim, (const uint16_t *)queries, sel + b, nb,
-                                               (uint32_t *)workspace, stream)))
-            return rc;
-        if ((rc = mips_launch_exact_select_f32((const uint32_t *)workspace, n_rows, row_base, sel + b, nb, k, ids, out_dist, out_idx,
-                                               out_row, out_flags, stream)))
-            return rc;
-    }
-    return EMDR2_OK;
-}
-
-int emdr2_mips_merge_f32(const float *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k,
-                         float *out_dist, int32_t *out_idx, int64_t *out_row, emdr2_stream_t stream)
-{
-    if (!dist_in || !idx_in || !row_in || !out_dist || !out_idx || !out_row || n_shards < 1 || n_q < 1 || k < 1) return EMDR2_E_BADARG;
-    return mips_launch_merge_f32(dist_in, idx_in, row_in, n_shards, n_q, k, out_dist, out_idx, out_row, (hipStream_t)stream);
-}
-
-int emdr2_mips_exact_workspace_bytes(int64_t n_rows, int n_sel, size_t *bytes)
-{
-    if (!bytes || n_rows < 1 || n_sel < 0) return EMDR2_E_BADARG;
-    *bytes = align_up((size_t)8 * (size_t)n_rows * sizeof(uint16_t), 256);
-    return EMDR2_OK;
-}
-
-int emdr2_mips_search_exact(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const void *queries,
-                            int n_q, const int32_t *sel, int n_sel, int k, const int32_t *ids, void *out_dist,
-                            int32_t *out_idx, int64_t *out_row, uint32_t *out_flags, void *workspace,
-                            size_t workspace_bytes, emdr2_stream_t stream_)
-{
-    if (!tiled || !queries || !sel || !out_dist || !out_idx || !out_row || !out_flags || !workspace) return EMDR2_E_BADARG;
-    if (n_q < 1 || n_sel < 0 || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(n_rows, dim) || n_rows < 1) return EMDR2_E_BADARG;
-    if (workspace_bytes < (size_t)8 * (size_t)n_rows * sizeof(uint16_t)) return EMDR2_E_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    for (int b = 0; b < n_sel; b += 8) {
-        const int nb = (n_sel - b) < 8 ? (n_sel - b) : 8;
-        int rc;
-        if ((rc = mips_launch_exact_scores((const char *)tiled, n_rows, dim, (const uint16_t *)queries, sel + b, nb,
-                                           (uint16_t *)workspace, stream)))
-            return rc;
-        if ((rc = mips_launch_exact_select((const uint16_t *)workspace, n_rows, row_base, sel + b, nb, k, ids,
-                                           (uint16_t *)out_dist, out_idx, out_row, out_flags, stream)))
-            return rc;
-    }
-    return EMDR2_OK;
+    return search_exact_impl(tiled, n_rows, dim, row_base, queries, n_q, sel, n_sel, k, ids, out_dist, out_idx, out_row, out_flags, workspace,
+                             workspace_bytes, stream, 1);
 }
 
 int emdr2_mips_merge(const void *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k,
                      void *out_dist, int32_t *out_idx, int64_t *out_row, emdr2_stream_t stream)
 {
-    if (!dist_in || !idx_in || !row_in || !out_dist || !out_idx || !out_row || n_shards < 1 || n_q < 1 || k < 1) return EMDR2_E_BADARG;
-    return mips_launch_merge((const uint16_t *)dist_in, idx_in, row_in, n_shards, n_q, k, (uint16_t *)out_dist, out_idx,
-                             out_row, (hipStream_t)stream);
+    return merge_impl(dist_in, idx_in, row_in, n_shards, n_q, k, out_dist, out_idx, out_row, stream, 0);
+}
+
+int emdr2_mips_merge_f32(const float *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k,
+                         float *out_dist, int32_t *out_idx, int64_t *out_row, emdr2_stream_t stream)
+{
+    return merge_impl(dist_in, idx_in, row_in, n_shards, n_q, k, out_dist, out_idx, out_row, stream, 1);
 }
 
 int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const void *queries, int n_q,

@@ -640,8 +640,29 @@ int mips_launch_finalize(const FinalizeParams &p, bool select_first, hipStream_t
 // shard merge: [S, n_q, k] per-shard canonical lists -> [n_q, k], (score desc, global row asc)
 // ------------------------------------------------------------------------------------------------
 #define MERGE_MAX 4096
-__global__ void __launch_bounds__(256) merge_kernel(const uint16_t *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards,
-                                                    int n_q, int k, uint16_t *out_dist, int32_t *out_idx, int64_t *out_row)
+// Where the per-shard lists come from: three arrays, or the gathered 16-byte records (FinalizeParams::out_rec) -- what a sharded search
+// exchanges in its ONE all-gather is the finalize kernel's own output, and the merge reads the gathered buffer as it arrives, no casts /
+// stacks between.  Same keys, same order, same outputs from both.
+template <class Fmt>
+struct SlotArrays {
+    const typename Fmt::stored_t *dist;
+    const int32_t *idx;
+    const int64_t *rows;
+    __device__ __forceinline__ int64_t row(size_t i) const { return rows[i]; }
+    __device__ __forceinline__ typename Fmt::stored_t score(size_t i) const { return dist[i]; }
+    __device__ __forceinline__ int32_t id(size_t i) const { return idx[i]; }
+};
+template <class Fmt>
+struct SlotRecords {
+    const uint4 *rec;
+    __device__ __forceinline__ int64_t row(size_t i) const { const uint4 r = rec[i]; return (int64_t)(((uint64_t)r.y << 32) | r.x); }
+    __device__ __forceinline__ typename Fmt::stored_t score(size_t i) const { return Fmt::from_bits(rec[i].w); }
+    __device__ __forceinline__ int32_t id(size_t i) const { return (int32_t)rec[i].z; }
+};
+
+template <class Fmt, class Source>
+__global__ void __launch_bounds__(256) merge_kernel(Source in, int n_shards, int n_q, int k, typename Fmt::stored_t *out_dist, int32_t *out_idx,
+                                                    int64_t *out_row)
 {
     __shared__ uint64_t key[MERGE_MAX];
     __shared__ unsigned nvalid;
@@ -652,10 +673,10 @@ __global__ void __launch_bounds__(256) merge_kernel(const uint16_t *dist_in, con
     for (int i = tid; i < n; i += 256) {
         const int s = i / k, j = i - s * k;
         const size_t src = ((size_t)s * n_q + q) * k + j;
-        const int64_t row = row_in[src];
+        const int64_t row = in.row(src);
         uint64_t kv = 0;
         if (row >= 0) {
-            kv = ((uint64_t)h16_order(dist_in[src]) << 48) | (0xffffffffffffull - (uint64_t)row);
+            kv = Fmt::merge_key(in.score(src), row);
             atomicAdd(&nvalid, 1u);
         }
         key[i] = kv;
@@ -670,126 +691,36 @@ __global__ void __launch_bounds__(256) merge_kernel(const uint16_t *dist_in, con
         if (rank < (unsigned)k) {
             const int s = i / k, j = i - s * k;
             const size_t src = ((size_t)s * n_q + q) * k + j, o = (size_t)q * k + rank;
-            out_dist[o] = dist_in[src]; out_idx[o] = idx_in[src]; out_row[o] = row_in[src];
+            out_dist[o] = in.score(src); out_idx[o] = in.id(src); out_row[o] = in.row(src);
         }
     }
     for (unsigned j = nv + tid; j < (unsigned)k; j += 256) {
         const size_t o = (size_t)q * k + j;
-        out_dist[o] = 0xfc00; out_idx[o] = -1; out_row[o] = -1;
+        out_dist[o] = Fmt::pad(); out_idx[o] = -1; out_row[o] = -1;
     }
 }
 
-int mips_launch_merge(const uint16_t *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q,
-                      int k, uint16_t *out_dist, int32_t *out_idx, int64_t *out_row, hipStream_t stream)
+template <class Fmt, class Source>
+static int launch_merge(Source in, int n_shards, int n_q, int k, void *out_dist, int32_t *out_idx, int64_t *out_row, hipStream_t stream)
 {
     if (n_shards * k > MERGE_MAX) return -4;
-    hipLaunchKernelGGL(merge_kernel, dim3(n_q), dim3(256), 0, stream, dist_in, idx_in, row_in, n_shards, n_q, k, out_dist, out_idx,
+    hipLaunchKernelGGL((merge_kernel<Fmt, Source>), dim3(n_q), dim3(256), 0, stream, in, n_shards, n_q, k, (typename Fmt::stored_t *)out_dist, out_idx,
                        out_row);
     return CHECK_LAUNCH();
 }
 
-// fp32-score twin: key = (f32 order : 32 | ~row : 32); global rows < 2^32
-__global__ void __launch_bounds__(256) merge_f32_kernel(const float *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q,
-                                                        int k, float *out_dist, int32_t *out_idx, int64_t *out_row)
+int mips_launch_merge(const void *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k, int f32, void *out_dist,
+                      int32_t *out_idx, int64_t *out_row, hipStream_t stream)
 {
-    __shared__ uint64_t key[MERGE_MAX];
-    __shared__ unsigned nvalid;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int n = n_shards * k;
-    if (tid == 0) nvalid = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-        const int s = i / k, j = i - s * k;
-        const size_t src = ((size_t)s * n_q + q) * k + j;
-        const int64_t row = row_in[src];
-        uint64_t kv = 0;
-        if (row >= 0) {
-            kv = ((uint64_t)f32_order(dist_in[src]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row);
-            atomicAdd(&nvalid, 1u);
-        }
-        key[i] = kv;
-    }
-    __syncthreads();
-    const unsigned nv = nvalid;
-    for (int i = tid; i < n; i += 256) {
-        const uint64_t mine = key[i];
-        if (mine == 0) continue;
-        unsigned rank = 0;
-        for (int t = 0; t < n; ++t) rank += (key[t] > mine);
-        if (rank < (unsigned)k) {
-            const int s = i / k, j = i - s * k;
-            const size_t src = ((size_t)s * n_q + q) * k + j, o = (size_t)q * k + rank;
-            out_dist[o] = dist_in[src]; out_idx[o] = idx_in[src]; out_row[o] = row_in[src];
-        }
-    }
-    for (unsigned j = nv + tid; j < (unsigned)k; j += 256) {
-        const size_t o = (size_t)q * k + j;
-        out_dist[o] = -INFINITY; out_idx[o] = -1; out_row[o] = -1;
-    }
-}
-
-int mips_launch_merge_f32(const float *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k, float *out_dist,
-                          int32_t *out_idx, int64_t *out_row, hipStream_t stream)
-{
-    if (n_shards * k > MERGE_MAX) return -4;
-    hipLaunchKernelGGL(merge_f32_kernel, dim3(n_q), dim3(256), 0, stream, dist_in, idx_in, row_in, n_shards, n_q, k, out_dist, out_idx, out_row);
-    return CHECK_LAUNCH();
-}
-
-// the merge over gathered 16-byte records [n_shards, n_q, k] (FinalizeParams::out_rec): what a sharded search exchanges in its ONE
-// all-gather is the finalize kernel's own output, and this kernel reads the gathered buffer as it arrives -- no casts / stacks between.
-// Same keys, same order, same outputs as merge_kernel / merge_f32_kernel.
-template <bool F32>
-__global__ void __launch_bounds__(256) merge_records_kernel(const uint4 *rec_in, int n_shards, int n_q, int k, void *out_dist, int32_t *out_idx,
-                                                            int64_t *out_row)
-{
-    __shared__ uint64_t key[MERGE_MAX];
-    __shared__ unsigned nvalid;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int n = n_shards * k;
-    if (tid == 0) nvalid = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-        const int s = i / k, j = i - s * k;
-        const uint4 r = rec_in[((size_t)s * n_q + q) * k + j];
-        const int64_t row = (int64_t)(((uint64_t)r.y << 32) | r.x);
-        uint64_t kv = 0;
-        if (row >= 0) {
-            kv = F32 ? (((uint64_t)f32_order(__uint_as_float(r.w)) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row))
-                     : (((uint64_t)h16_order((uint16_t)r.w) << 48) | (0xffffffffffffull - (uint64_t)row));
-            atomicAdd(&nvalid, 1u);
-        }
-        key[i] = kv;
-    }
-    __syncthreads();
-    const unsigned nv = nvalid;
-    for (int i = tid; i < n; i += 256) {
-        const uint64_t mine = key[i];
-        if (mine == 0) continue;
-        unsigned rank = 0;
-        for (int t = 0; t < n; ++t) rank += (key[t] > mine);
-        if (rank < (unsigned)k) {
-            const int s = i / k, j = i - s * k;
-            const uint4 r = rec_in[((size_t)s * n_q + q) * k + j];
-            const size_t o = (size_t)q * k + rank;
-            if (F32) ((float *)out_dist)[o] = __uint_as_float(r.w); else ((uint16_t *)out_dist)[o] = (uint16_t)r.w;
-            out_idx[o] = (int32_t)r.z; out_row[o] = (int64_t)(((uint64_t)r.y << 32) | r.x);
-        }
-    }
-    for (unsigned j = nv + tid; j < (unsigned)k; j += 256) {
-        const size_t o = (size_t)q * k + j;
-        if (F32) ((float *)out_dist)[o] = -INFINITY; else ((uint16_t *)out_dist)[o] = 0xfc00;
-        out_idx[o] = -1; out_row[o] = -1;
-    }
+    if (f32) return launch_merge<ScoreF32>(SlotArrays<ScoreF32>{(const float *)dist_in, idx_in, row_in}, n_shards, n_q, k, out_dist, out_idx, out_row, stream);
+    return launch_merge<ScoreH16>(SlotArrays<ScoreH16>{(const uint16_t *)dist_in, idx_in, row_in}, n_shards, n_q, k, out_dist, out_idx, out_row, stream);
 }
 
 int mips_launch_merge_records(const uint4 *rec_in, int n_shards, int n_q, int k, int f32, void *out_dist, int32_t *out_idx, int64_t *out_row,
                               hipStream_t stream)
 {
-    if (n_shards * k > MERGE_MAX) return -4;
-    if (f32) hipLaunchKernelGGL(merge_records_kernel<true>, dim3(n_q), dim3(256), 0, stream, rec_in, n_shards, n_q, k, out_dist, out_idx, out_row);
-    else hipLaunchKernelGGL(merge_records_kernel<false>, dim3(n_q), dim3(256), 0, stream, rec_in, n_shards, n_q, k, out_dist, out_idx, out_row);
-    return CHECK_LAUNCH();
+    if (f32) return launch_merge<ScoreF32>(SlotRecords<ScoreF32>{rec_in}, n_shards, n_q, k, out_dist, out_idx, out_row, stream);
+    return launch_merge<ScoreH16>(SlotRecords<ScoreH16>{rec_in}, n_shards, n_q, k, out_dist, out_idx, out_row, stream);
 }
 
 __global__ void __launch_bounds__(128) pack_records_kernel(const void *dist, const int32_t *idx, const int64_t *row, const int32_t *sel, int k,
@@ -799,7 +730,7 @@ __global__ void __launch_bounds__(128) pack_records_kernel(const void *dist, con
     for (int j = threadIdx.x; j < k; j += 128) {
         const size_t o = (size_t)q * k + j;
         const int64_t r = row[o];
-        const uint32_t bits = f32 ? __float_as_uint(((const float *)dist)[o]) : (uint32_t)((const uint16_t *)dist)[o];
+        const uint32_t bits = f32 ? ScoreF32::bits(((const float *)dist)[o]) : ScoreH16::bits(((const uint16_t *)dist)[o]);
         rec[o] = make_uint4((uint32_t)r, (uint32_t)((uint64_t)r >> 32), (uint32_t)idx[o], bits);
     }
 }
@@ -813,13 +744,15 @@ int mips_launch_pack_records(const void *dist, const int32_t *idx, const int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
-// all-exact fallback: canonical fp16 keys for EVERY row in integer arithmetic, then a two-level
-// radix threshold + ordered collection (first rows win ties).  Up to 8 queries per index pass.
+// all-exact fallback: canonical ordered keys for EVERY row in integer arithmetic, then a radix
+// threshold (one level per key byte) + ordered collection (first rows win ties).  Up to 8 queries
+// per index pass.
 // ------------------------------------------------------------------------------------------------
 #define XQ 8
+template <class Fmt>
 __global__ void __launch_bounds__(256) exact_scores_kernel(const char *__restrict__ e_tiled, int64_t n_rows, int dim,
                                                            const uint16_t *__restrict__ queries, const int32_t *__restrict__ sel,
-                                                           int n_sel, uint16_t *__restrict__ hkeys)
+                                                           int n_sel, typename Fmt::key_t *__restrict__ keys)
 {
     extern __shared__ int qfix[]; // [n_sel][dim] packed (mant << 8) | shift
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -856,54 +789,66 @@ __global__ void __launch_bounds__(256) exact_scores_kernel(const char *__restric
         for (int f = 0; f < XQ; ++f) {
             if (f < n_sel) {
                 const int64_t l = wave_sum_i64(lo[f]), h = wave_sum_i64(hi[f]);
-                if (lane == 0) hkeys[(size_t)f * n_rows + row] = (uint16_t)h16_order(fixed_to_half(l, h));
+                if (lane == 0) keys[(size_t)f * n_rows + row] = Fmt::fixed_key(l, h);
             }
         }
     }
 }
 
-int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel,
-                             int n_sel, uint16_t *hkeys, hipStream_t stream)
+template <class Fmt>
+static int launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel, void *keys,
+                               hipStream_t stream)
 {
     if (n_sel > XQ) return -1;
     int64_t nb = (n_rows + 3) / 4;
     if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(exact_scores_kernel, dim3((unsigned)nb), dim3(256), (size_t)n_sel * dim * sizeof(int), stream, e_tiled, n_rows, dim,
-                       queries, sel, n_sel, hkeys);
+    hipLaunchKernelGGL(exact_scores_kernel<Fmt>, dim3((unsigned)nb), dim3(256), (size_t)n_sel * dim * sizeof(int), stream, e_tiled, n_rows, dim,
+                       queries, sel, n_sel, (typename Fmt::key_t *)keys);
     return CHECK_LAUNCH();
+}
+
+int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel, int f32, void *keys,
+                             hipStream_t stream)
+{
+    return f32 ? launch_exact_scores<ScoreF32>(e_tiled, n_rows, dim, queries, sel, n_sel, keys, stream)
+               : launch_exact_scores<ScoreH16>(e_tiled, n_rows, dim, queries, sel, n_sel, keys, stream);
 }
 
 #define XS_THREADS 1024
 #define XS_R 8
-__global__ void __launch_bounds__(XS_THREADS) exact_select_kernel(const uint16_t *__restrict__ hkeys, int64_t n_rows, int64_t row_base,
+template <class Fmt>
+__global__ void __launch_bounds__(XS_THREADS) exact_select_kernel(const typename Fmt::key_t *__restrict__ keys, int64_t n_rows, int64_t row_base,
                                                                   const int32_t *__restrict__ sel, int k, const int32_t *__restrict__ ids,
-                                                                  uint16_t *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags)
+                                                                  typename Fmt::stored_t *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags)
 {
     __shared__ unsigned hist[256];
     __shared__ unsigned sh_digit, sh_need, sh_above, sh_wsum[XS_THREADS / 64];
     __shared__ uint64_t okey[128];
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint16_t *hk = hkeys + (size_t)f * n_rows;
+    const typename Fmt::key_t *hk = keys + (size_t)f * n_rows;
     const unsigned keff = (int64_t)k < n_rows ? (unsigned)k : (unsigned)n_rows;
 
-    // level 1: high byte
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < n_rows; i += XS_THREADS) atomicAdd(&hist[hk[i] >> 8], 1u);
-    __syncthreads();
-    if (tid < 64) pick_digit(hist, keff, &sh_digit, &sh_need);
-    __syncthreads();
-    const unsigned bhi = sh_digit, need1 = sh_need;
-    __syncthreads();
-    // level 2: low byte inside the boundary high-byte bucket
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < n_rows; i += XS_THREADS) { const unsigned v = hk[i]; if ((v >> 8) == bhi) atomicAdd(&hist[v & 255u], 1u); }
-    __syncthreads();
-    if (tid < 64) pick_digit(hist, need1, &sh_digit, &sh_need);
-    __syncthreads();
-    const unsigned T = (bhi << 8) | sh_digit;   // k-th canonical key
-    const unsigned need_eq = sh_need;           // how many rows with key == T belong to the top-k
+    // radix threshold, one level per key byte, most significant first: after a level the k-th key is known to start with `prefix`
+    constexpr int TOP = 8 * (int)sizeof(typename Fmt::key_t) - 8;
+    uint32_t prefix = 0;
+    unsigned need = keff;
+#pragma unroll
+    for (int sh = TOP; sh >= 0; sh -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (int64_t i = tid; i < n_rows; i += XS_THREADS) {
+            const uint32_t v = hk[i];
+            if (sh == TOP || (v >> (sh + 8)) == (prefix >> (sh + 8))) atomicAdd(&hist[(v >> sh) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid < 64) pick_digit(hist, need, &sh_digit, &sh_need);
+        __syncthreads();
+        prefix |= sh_digit << sh;
+        need = sh_need;
+        __syncthreads();
+    }
+    const uint32_t T = prefix;                  // k-th canonical key
+    const unsigned need_eq = need;              // how many rows with key == T belong to the top-k
     const unsigned n_above = keff - need_eq;
     if (tid == 0) sh_above = 0;
     __syncthreads();
@@ -913,13 +858,12 @@ __global__ void __launch_bounds__(XS_THREADS) exact_select_kernel(const uint16_t
     for (int64_t base = 0; base < n_rows; base += (int64_t)XS_THREADS * XS_R) {
         const int64_t r0 = base + (int64_t)tid * XS_R;
         unsigned eqm = 0, mycnt = 0;
-        uint16_t v[XS_R];
 #pragma unroll
         for (int j = 0; j < XS_R; ++j) {
             const int64_t r = r0 + j;
-            v[j] = r < n_rows ? hk[r] : 0;
-            if (r < n_rows && v[j] > T) { const unsigned s = atomicAdd(&sh_above, 1u); okey[s] = ((uint64_t)v[j] << 32) | (uint64_t)(0xffffffffu - (uint32_t)r); }
-            if (r < n_rows && v[j] == T) { eqm |= 1u << j; ++mycnt; }
+            const uint32_t v = r < n_rows ? hk[r] : 0;
+            if (r < n_rows && v > T) { const unsigned s = atomicAdd(&sh_above, 1u); okey[s] = ((uint64_t)v << 32) | (uint64_t)(0xffffffffu - (uint32_t)r); }
+            if (r < n_rows && v == T) { eqm |= 1u << j; ++mycnt; }
         }
         // block exclusive scan of mycnt in thread (= row) order
         unsigned incl = mycnt;
@@ -944,168 +888,29 @@ __global__ void __launch_bounds__(XS_THREADS) exact_select_kernel(const uint16_t
         for (unsigned i = 0; i < keff; ++i) rank += (okey[i] > mine);
         const uint32_t row = 0xffffffffu - (uint32_t)mine;
         const size_t o = (size_t)qi * k + rank;
-        out_dist[o] = h16_unorder((uint32_t)(mine >> 32));
+        out_dist[o] = Fmt::unorder((uint32_t)(mine >> 32));
         out_row[o] = row_base + (int64_t)row;
         out_idx[o] = ids ? ids[row] : (int32_t)(row_base + (int64_t)row);
     }
     for (unsigned j = keff + tid; j < (unsigned)k; j += XS_THREADS) {
         const size_t o = (size_t)qi * k + j;
-        out_dist[o] = 0xfc00; out_row[o] = -1; out_idx[o] = -1;
+        out_dist[o] = Fmt::pad(); out_row[o] = -1; out_idx[o] = -1;
     }
     if (tid == 0) flags[qi] = 0;
 }
 
-int mips_launch_exact_select(const uint16_t *hkeys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel,
-                             int k, const int32_t *ids, uint16_t *out_dist, int32_t *out_idx, int64_t *out_row,
-                             unsigned *flags, hipStream_t stream)
+template <class Fmt>
+static int launch_exact_select(const void *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k, const int32_t *ids,
+                               void *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream)
 {
-    hipLaunchKernelGGL(exact_select_kernel, dim3(n_sel), dim3(XS_THREADS), 0, stream, hkeys, n_rows, row_base, sel, k, ids, out_dist,
-                       out_idx, out_row, flags);
+    hipLaunchKernelGGL(exact_select_kernel<Fmt>, dim3(n_sel), dim3(XS_THREADS), 0, stream, (const typename Fmt::key_t *)keys, n_rows, row_base, sel, k,
+                       ids, (typename Fmt::stored_t *)out_dist, out_idx, out_row, flags);
     return CHECK_LAUNCH();
 }
 
-// ------------------------------------------------------------------------------------------------
-// all-exact fallback, fp32-score mode: 32-bit ordered keys, four-level radix threshold, same ordered collection
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) exact_scores_f32_kernel(const char *__restrict__ e_tiled, int64_t n_rows, int dim,
-                                                               const uint16_t *__restrict__ queries, const int32_t *__restrict__ sel, int n_sel,
-                                                               uint32_t *__restrict__ keys)
+int mips_launch_exact_select(const void *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k, const int32_t *ids, int f32,
+                             void *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream)
 {
-    extern __shared__ int qfix[]; // [n_sel][dim] packed (mant << 8) | shift
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < n_sel * dim; i += 256) {
-        const int f = i / dim, d = i - f * dim;
-        const HalfFix hf = half_fix(queries[(size_t)sel[f] * dim + d]);
-        qfix[i] = (hf.mant << 8) | hf.shift;
-    }
-    __syncthreads();
-    const int nseg = dim / 8;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < n_rows; row += (int64_t)gridDim.x * 4) {
-        int64_t lo[XQ], hi[XQ];
-#pragma unroll
-        for (int f = 0; f < XQ; ++f) { lo[f] = 0; hi[f] = 0; }
-        for (int seg = lane; seg < nseg; seg += 64) {
-            const uint4 ev = *(const uint4 *)(e_tiled + tiled_seg_offset(row, seg, nseg >> 2));
-            const uint32_t ew[4] = {ev.x, ev.y, ev.z, ev.w};
-            HalfFix ef[8];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { ef[2 * j] = half_fix((uint16_t)(ew[j] & 0xffff)); ef[2 * j + 1] = half_fix((uint16_t)(ew[j] >> 16)); }
-#pragma unroll
-            for (int f = 0; f < XQ; ++f) {
-                if (f < n_sel) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int pq = qfix[f * dim + seg * 8 + j];
-                        HalfFix qf; qf.mant = pq >> 8; qf.shift = pq & 0xff;
-                        exact_mac(lo[f], hi[f], ef[j], qf);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < XQ; ++f) {
-            if (f < n_sel) {
-                const int64_t l = wave_sum_i64(lo[f]), h = wave_sum_i64(hi[f]);
-                if (lane == 0) keys[(size_t)f * n_rows + row] = f32_order(fixed_to_float(l, h));
-            }
-        }
-    }
-}
-
-int mips_launch_exact_scores_f32(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel,
-                                 uint32_t *keys, hipStream_t stream)
-{
-    if (n_sel > XQ) return -1;
-    int64_t nb = (n_rows + 3) / 4;
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(exact_scores_f32_kernel, dim3((unsigned)nb), dim3(256), (size_t)n_sel * dim * sizeof(int), stream, e_tiled, n_rows, dim,
-                       queries, sel, n_sel, keys);
-    return CHECK_LAUNCH();
-}
-
-__global__ void __launch_bounds__(XS_THREADS) exact_select_f32_kernel(const uint32_t *__restrict__ keys, int64_t n_rows, int64_t row_base,
-                                                                      const int32_t *__restrict__ sel, int k, const int32_t *__restrict__ ids,
-                                                                      float *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags)
-{
-    __shared__ unsigned hist[256];
-    __shared__ unsigned sh_digit, sh_need, sh_above, sh_wsum[XS_THREADS / 64];
-    __shared__ uint64_t okey[128];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t *hk = keys + (size_t)f * n_rows;
-    const unsigned keff = (int64_t)k < n_rows ? (unsigned)k : (unsigned)n_rows;
-
-    // radix threshold, most significant byte first: after level L the k-th key is known to start with `prefix`
-    uint32_t prefix = 0;
-    unsigned need = keff;
-    for (int level = 3; level >= 0; --level) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const int sh = level * 8;
-        for (int64_t i = tid; i < n_rows; i += XS_THREADS) {
-            const uint32_t v = hk[i];
-            if (level == 3 || (v >> (sh + 8)) == (prefix >> (sh + 8))) atomicAdd(&hist[(v >> sh) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) pick_digit(hist, need, &sh_digit, &sh_need);
-        __syncthreads();
-        prefix |= sh_digit << sh;
-        need = sh_need;
-        __syncthreads();
-    }
-    const uint32_t T = prefix;                  // k-th key
-    const unsigned need_eq = need;              // how many rows with key == T belong to the top-k
-    const unsigned n_above = keff - need_eq;
-    if (tid == 0) sh_above = 0;
-    __syncthreads();
-
-    unsigned eq_done = 0;
-    for (int64_t base = 0; base < n_rows; base += (int64_t)XS_THREADS * XS_R) {
-        const int64_t r0 = base + (int64_t)tid * XS_R;
-        unsigned eqm = 0, mycnt = 0;
-#pragma unroll
-        for (int j = 0; j < XS_R; ++j) {
-            const int64_t r = r0 + j;
-            const uint32_t v = r < n_rows ? hk[r] : 0;
-            if (r < n_rows && v > T) { const unsigned s = atomicAdd(&sh_above, 1u); okey[s] = ((uint64_t)v << 32) | (uint64_t)(0xffffffffu - (uint32_t)r); }
-            if (r < n_rows && v == T) { eqm |= 1u << j; ++mycnt; }
-        }
-        unsigned incl = mycnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-        if (lane == 63) sh_wsum[wave] = incl;
-        __syncthreads();
-        unsigned woff = 0, total = 0;
-        for (int w = 0; w < XS_THREADS / 64; ++w) { const unsigned s = sh_wsum[w]; if (w < wave) woff += s; total += s; }
-        unsigned rank = eq_done + woff + incl - mycnt;
-#pragma unroll
-        for (int j = 0; j < XS_R; ++j)
-            if (eqm & (1u << j)) { if (rank < need_eq) okey[n_above + rank] = ((uint64_t)T << 32) | (uint64_t)(0xffffffffu - (uint32_t)(r0 + j)); ++rank; }
-        eq_done += total;
-        __syncthreads();
-    }
-    __syncthreads();
-    const int qi = sel[f];
-    if ((unsigned)tid < keff) {
-        const uint64_t mine = okey[tid];
-        unsigned rank = 0;
-        for (unsigned i = 0; i < keff; ++i) rank += (okey[i] > mine);
-        const uint32_t row = 0xffffffffu - (uint32_t)mine;
-        const size_t o = (size_t)qi * k + rank;
-        out_dist[o] = f32_unorder((uint32_t)(mine >> 32));
-        out_row[o] = row_base + (int64_t)row;
-        out_idx[o] = ids ? ids[row] : (int32_t)(row_base + (int64_t)row);
-    }
-    for (unsigned j = keff + tid; j < (unsigned)k; j += XS_THREADS) {
-        const size_t o = (size_t)qi * k + j;
-        out_dist[o] = -INFINITY; out_row[o] = -1; out_idx[o] = -1;
-    }
-    if (tid == 0) flags[qi] = 0;
-}
-
-int mips_launch_exact_select_f32(const uint32_t *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k,
-                                 const int32_t *ids, float *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream)
-{
-    hipLaunchKernelGGL(exact_select_f32_kernel, dim3(n_sel), dim3(XS_THREADS), 0, stream, keys, n_rows, row_base, sel, k, ids, out_dist,
-                       out_idx, out_row, flags);
-    return CHECK_LAUNCH();
+    return f32 ? launch_exact_select<ScoreF32>(keys, n_rows, row_base, sel, n_sel, k, ids, out_dist, out_idx, out_row, flags, stream)
+               : launch_exact_select<ScoreH16>(keys, n_rows, row_base, sel, n_sel, k, ids, out_dist, out_idx, out_row, flags, stream);
 }

@@ -140,3 +140,31 @@ __device__ __forceinline__ uint16_t f32_to_h16_roundup(float f)
     }
     return __builtin_bit_cast(uint16_t, h);
 }
+
+// ---- score formats ------------------------------------------------------------------------------
+// The two canonical result formats, stated once for the kernels behind the scan's candidates: the shard merge and
+// the all-exact fallback are templates over these.  stored_t is what the caller's score array holds, key_t its ordered form (larger key
+// <=> larger score); a record carries the stored bits in its last word.  merge_key orders (score desc, global row asc): fp16 keeps 48
+// bits of ~row, fp32 32 (global rows < 2^32); 0 is no valid slot's key.
+struct ScoreH16 {
+    typedef uint16_t stored_t;                                  // fp16 bits
+    typedef uint16_t key_t;
+    static __device__ __forceinline__ key_t order(stored_t s) { return (key_t)h16_order(s); }
+    static __device__ __forceinline__ stored_t unorder(uint32_t o) { return h16_unorder(o); }
+    static __device__ __forceinline__ key_t fixed_key(int64_t lo, int64_t hi) { return order(fixed_to_half(lo, hi)); }
+    static __device__ __forceinline__ stored_t pad() { return 0xfc00; }
+    static __device__ __forceinline__ uint64_t merge_key(stored_t s, int64_t row) { return ((uint64_t)order(s) << 48) | (0xffffffffffffull - (uint64_t)row); }
+    static __device__ __forceinline__ uint32_t bits(stored_t s) { return s; }
+    static __device__ __forceinline__ stored_t from_bits(uint32_t b) { return (uint16_t)b; }
+};
+struct ScoreF32 {
+    typedef float stored_t;                                     // RNE_fp32(exact dot)
+    typedef uint32_t key_t;
+    static __device__ __forceinline__ key_t order(stored_t s) { return f32_order(s); }
+    static __device__ __forceinline__ stored_t unorder(uint32_t o) { return f32_unorder(o); }
+    static __device__ __forceinline__ key_t fixed_key(int64_t lo, int64_t hi) { return order(fixed_to_float(lo, hi)); }
+    static __device__ __forceinline__ stored_t pad() { return -INFINITY; }
+    static __device__ __forceinline__ uint64_t merge_key(stored_t s, int64_t row) { return ((uint64_t)order(s) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row); }
+    static __device__ __forceinline__ uint32_t bits(stored_t s) { return __float_as_uint(s); }
+    static __device__ __forceinline__ stored_t from_bits(uint32_t b) { return __uint_as_float(b); }
+};

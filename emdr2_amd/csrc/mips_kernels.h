@@ -102,27 +102,19 @@ struct FinalizeParams {
                              // (fp16 in the low half, or fp32)} -- written straight into the all-gather send buffer of a sharded search
 };
 int mips_launch_finalize(const FinalizeParams &p, bool select_first, hipStream_t stream);      // select_first: run the select of the last scan segment in the same launch
-int mips_launch_merge_f32(const float *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k,
-                          float *out_dist, int32_t *out_idx, int64_t *out_row, hipStream_t stream);
-// the same merges over gathered 16-byte records [n_shards, n_q, k] (FinalizeParams::out_rec)
+// k-way merge of [n_shards, n_q, k] per-shard canonical lists (f32: float scores, else fp16 bits); -4 = n_shards * k too large
+int mips_launch_merge(const void *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k, int f32, void *out_dist,
+                      int32_t *out_idx, int64_t *out_row, hipStream_t stream);
+// the same merge over gathered 16-byte records [n_shards, n_q, k] (FinalizeParams::out_rec)
 int mips_launch_merge_records(const uint4 *rec_in, int n_shards, int n_q, int k, int f32, void *out_dist, int32_t *out_idx, int64_t *out_row,
                               hipStream_t stream);
 // (dist, idx, row) rows sel[i] -> records rows sel[i] (queries re-done by the all-exact path)
 int mips_launch_pack_records(const void *dist, const int32_t *idx, const int64_t *row, const int32_t *sel, int n_sel, int k, int f32, uint4 *rec,
                              hipStream_t stream);
-int mips_launch_merge(const uint16_t *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q,
-                      int k, uint16_t *out_dist, int32_t *out_idx, int64_t *out_row, hipStream_t stream);
 
-// all-exact fallback
-int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries,
-                             const int32_t *sel, int n_sel, uint16_t *hkeys /* [n_sel][n_rows] ordered keys */,
+// all-exact fallback: ordered keys [n_sel][n_rows] of <= 8 selected queries (uint16 of the fp16 score, or uint32 of the fp32 one when f32),
+// then their canonical top-k
+int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel, int f32, void *keys,
                              hipStream_t stream);
-int mips_launch_exact_select(const uint16_t *hkeys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel,
-                             int k, const int32_t *ids, uint16_t *out_dist, int32_t *out_idx, int64_t *out_row,
-                             unsigned *flags, hipStream_t stream);
-
-// fp32-score twins of the all-exact fallback (32-bit ordered keys)
-int mips_launch_exact_scores_f32(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel,
-                                 uint32_t *keys /* [n_sel][n_rows] */, hipStream_t stream);
-int mips_launch_exact_select_f32(const uint32_t *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k,
-                                 const int32_t *ids, float *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream);
+int mips_launch_exact_select(const void *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k, const int32_t *ids, int f32,
+                             void *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream);

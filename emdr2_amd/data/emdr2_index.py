@@ -15,6 +15,7 @@ of DESIGN.md section 3: score = RNE_fp16(exact dot), order (score desc, row asc)
 
 There is no CPU path here: without the HIP library / a GPU the index raises.
 """
+import ctypes
 import os
 import pickle
 import shutil
@@ -384,7 +385,6 @@ class HipIndexShard(object):
             raise _native.NativeError("HipIndexShard needs a GPU; there is no CPU fallback")
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.dim, self.n_rows, self.row_base = int(dim), int(n_rows), int(row_base)
-        import ctypes
         nbytes = ctypes.c_size_t()
         _native.check(self.lib.emdr2_mips_layout_bytes(max(self.n_rows, 1), self.dim, ctypes.byref(nbytes)), "layout_bytes")
         self.tiled = torch.zeros(nbytes.value, dtype=torch.uint8, device=self.device)
@@ -407,7 +407,6 @@ class HipIndexShard(object):
         non-finite row)."""
         if not self._want_shadow:
             return None, None
-        import ctypes
         if into is None:
             ib, tb = ctypes.c_size_t(), ctypes.c_size_t()
             _native.check(self.lib.emdr2_mips_shadow_bytes(self.n_rows, self.dim, ctypes.byref(ib), ctypes.byref(tb)), "shadow_bytes")
@@ -501,7 +500,6 @@ class HipIndexShard(object):
             raise RuntimeError("a swap refresh is in progress (begin_refresh without commit_refresh): its commit would discard the update")
         if n == 0:
             return
-        import ctypes
         if self._block_norms is None:
             nbytes = ctypes.c_size_t()
             _native.check(self.lib.emdr2_mips_block_norm_bytes(self.n_rows, ctypes.byref(nbytes)), "block_norm_bytes")
@@ -527,15 +525,16 @@ class HipIndexShard(object):
         self.ids = ids.to(self.device).contiguous()
 
     def _workspace(self, k):
-        import ctypes
         if self._ws is None:
             nbytes = ctypes.c_size_t()
             _native.check(self.lib.emdr2_mips_workspace_bytes(512, self.dim, k, ctypes.byref(nbytes)), "workspace_bytes")
             self._ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def search(self, queries, k, exact_fallback=True):
-        """queries fp16 [Q, dim] on this device -> (dist fp16 [Q,k], idx int32, row int64, flags uint32-as-int32)."""
+    def _search(self, queries, k, f32, rec, exact_fallback=True, out=None):
+        """The one search.  `rec` False: the fast path into three arrays (dist fp16, or fp32 when `f32`) -> (dist, idx, row, flags).
+        `rec` True: into a records buffer (`out`, or a new one) -> (records, flags).  Then the all-exact path for the queries the fast
+        path flagged (one host sync, like the reference's .item() loop), their records re-packed."""
         if self._filled != self.n_rows:
             raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
         if queries.dtype != torch.float16 or queries.dim() != 2 or queries.shape[1] != self.dim or not queries.is_cuda:
@@ -544,143 +543,79 @@ class HipIndexShard(object):
             raise ValueError("top_k must be in [1, %d]" % _native.MAX_TOPK)
         q = queries.contiguous()
         nq = q.shape[0]
-        dist = torch.empty((nq, k), dtype=torch.float16, device=self.device)
-        idx = torch.empty((nq, k), dtype=torch.int32, device=self.device)
-        row = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        rec = (out if out is not None else torch.empty((nq, k, 16), dtype=torch.uint8, device=self.device)) if rec else None
+        if rec is not None and (rec.shape != (nq, k, 16) or rec.dtype != torch.uint8 or not rec.is_contiguous()):
+            raise ValueError("records buffer must be a contiguous uint8 [Q, k, 16] tensor")
+
+        def arrays():
+            return (torch.empty((nq, k), dtype=torch.float32 if f32 else torch.float16, device=self.device),
+                    torch.empty((nq, k), dtype=torch.int32, device=self.device), torch.empty((nq, k), dtype=torch.int64, device=self.device))
+        dist, idx, row = arrays() if rec is None else (None, None, None)
         # (the search's init launch clears the flags of all nq queries: no fill launch of their own)
         flags = torch.empty((nq,), dtype=torch.int32, device=self.device)
         if self.n_rows == 0:
             flags.zero_()
-            dist.fill_(float('-inf')); idx.fill_(-1); row.fill_(-1)
-            return dist, idx, row, flags
+            if rec is None:
+                dist.fill_(float('-inf')); idx.fill_(-1); row.fill_(-1)
+            else:
+                rec.view(torch.int32).copy_(torch.tensor([-1, -1, -1, 0xff800000 - (1 << 32) if f32 else 0xfc00], dtype=torch.int32, device=self.device))
+            return (dist, idx, row, flags) if rec is None else (rec, flags)
         ws = self._workspace(k)
-        ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        if self._shadow is not None:
-            self._search_shadow(q, k, ids_ptr, False, dist, idx, row, None, flags, ws)
-        else:
-            _native.check(self.lib.emdr2_mips_search(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base,
-                                                     self.emax_sq.data_ptr(), q.data_ptr(), nq, k, ids_ptr,
-                                                     dist.data_ptr(), idx.data_ptr(), row.data_ptr(), flags.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search")
-        if exact_fallback:
-            sel = torch.nonzero(flags).to(torch.int32).flatten()     # one host sync, like the reference's .item() loop
-            if sel.numel():
-                self.search_exact(q, sel, k, dist, idx, row, flags)
-        return dist, idx, row, flags
-
-    def _search_shadow(self, q, k, ids_ptr, f32, dist, idx, row, rec, flags, ws):
-        """emdr2_mips_search / _search_f32 / _search_records with the long filter segments on the sealed int8 shadow image."""
         ptr = lambda t: None if t is None else t.data_ptr()
-        _native.check(self.lib.emdr2_mips_search_shadow(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
-                                                        self._shadow[0].data_ptr(), self._shadow[1].data_ptr(), self.shadow_min_rows,
-                                                        q.data_ptr(), q.shape[0], k, ids_ptr, int(bool(f32)), ptr(dist), ptr(idx), ptr(row),
-                                                        ptr(rec), flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()),
-                      "mips_search_shadow")
+        head = (self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr())
+        tail = (flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr())
+        if self._shadow is not None:                                # the long filter segments on the sealed int8 shadow image
+            _native.check(self.lib.emdr2_mips_search_shadow(*head, self._shadow[0].data_ptr(), self._shadow[1].data_ptr(), self.shadow_min_rows,
+                                                            q.data_ptr(), nq, k, ptr(self.ids), int(f32), ptr(dist), ptr(idx), ptr(row), ptr(rec),
+                                                            *tail), "mips_search_shadow")
+        elif rec is not None:
+            _native.check(self.lib.emdr2_mips_search_records(*head, q.data_ptr(), nq, k, ptr(self.ids), int(f32), rec.data_ptr(), *tail),
+                          "mips_search_records")
+        else:
+            fn, what = (self.lib.emdr2_mips_search_f32, "mips_search_f32") if f32 else (self.lib.emdr2_mips_search, "mips_search")
+            _native.check(fn(*head, q.data_ptr(), nq, k, ptr(self.ids), dist.data_ptr(), idx.data_ptr(), row.data_ptr(), *tail), what)
+        if exact_fallback:
+            sel = torch.nonzero(flags).to(torch.int32).flatten()
+            if sel.numel():
+                sel = sel.contiguous()
+                if rec is not None:
+                    dist, idx, row = arrays()
+                self.search_exact(q, sel, k, dist, idx, row, flags, f32)
+                if rec is not None:
+                    _native.check(self.lib.emdr2_mips_pack_records(dist.data_ptr(), idx.data_ptr(), row.data_ptr(), sel.data_ptr(), int(sel.numel()),
+                                                                   k, int(f32), rec.data_ptr(), _native.stream_ptr()), "mips_pack_records")
+        return (dist, idx, row, flags) if rec is None else (rec, flags)
+
+    def search(self, queries, k, exact_fallback=True):
+        """queries fp16 [Q, dim] on this device -> (dist fp16 [Q,k], idx int32, row int64, flags uint32-as-int32)."""
+        return self._search(queries, k, False, False, exact_fallback)
+
+    def search_f32(self, queries, k, exact_fallback=True):
+        """FaissMIPSIndex-style scores: queries fp16 [Q, dim] -> (dist fp32 [Q,k] = RNE_fp32(exact dot), idx int32, row int64, flags),
+        order (fp32 score desc, row asc)."""
+        return self._search(queries, k, True, False, exact_fallback)
 
     def search_records(self, queries, k, f32=False, out=None, exact_fallback=True):
         """The shard's canonical top-k as ONE uint8 [Q, k, 16] tensor of packed records {int64 global row | int32 doc id | score bits}
         (include/emdr2_mips.h) -- what a sharded search puts into its all-gather: `out` may be the send buffer itself.  Queries the fast
         path flags are re-done by the all-exact path and their records overwritten (one host sync, as in `search`).  -> (records, flags)."""
-        if self._filled != self.n_rows:
-            raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
-        if queries.dtype != torch.float16 or queries.dim() != 2 or queries.shape[1] != self.dim or not queries.is_cuda:
-            raise ValueError("queries must be a CUDA float16 [Q, %d] tensor" % self.dim)
-        if not (1 <= k <= _native.MAX_TOPK):
-            raise ValueError("top_k must be in [1, %d]" % _native.MAX_TOPK)
-        q = queries.contiguous()
-        nq = q.shape[0]
-        rec = out if out is not None else torch.empty((nq, k, 16), dtype=torch.uint8, device=self.device)
-        if rec.shape != (nq, k, 16) or rec.dtype != torch.uint8 or not rec.is_contiguous():
-            raise ValueError("records buffer must be a contiguous uint8 [Q, k, 16] tensor")
-        # (the search's init launch clears the flags of all nq queries: no fill launch of their own)
-        flags = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        if self.n_rows == 0:
-            flags.zero_()
-            rec.view(torch.int32).copy_(torch.tensor([-1, -1, -1, 0xff800000 - (1 << 32) if f32 else 0xfc00], dtype=torch.int32, device=self.device))
-            return rec, flags
-        ws = self._workspace(k)
-        ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        if self._shadow is not None:
-            self._search_shadow(q, k, ids_ptr, f32, None, None, None, rec, flags, ws)
-        else:
-            _native.check(self.lib.emdr2_mips_search_records(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
-                                                             q.data_ptr(), nq, k, ids_ptr, int(bool(f32)), rec.data_ptr(), flags.data_ptr(),
-                                                             ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_records")
-        if exact_fallback:
-            sel = torch.nonzero(flags).to(torch.int32).flatten()     # one host sync, like the reference's .item() loop
-            if sel.numel():
-                sel = sel.contiguous()
-                dist = torch.empty((nq, k), dtype=torch.float32 if f32 else torch.float16, device=self.device)
-                idx = torch.empty((nq, k), dtype=torch.int32, device=self.device)
-                row = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-                if f32:
-                    self._search_exact_f32(q, sel, k, dist, idx, row, flags)
-                else:
-                    self.search_exact(q, sel, k, dist, idx, row, flags)
-                _native.check(self.lib.emdr2_mips_pack_records(dist.data_ptr(), idx.data_ptr(), row.data_ptr(), sel.data_ptr(), int(sel.numel()), k,
-                                                               int(bool(f32)), rec.data_ptr(), _native.stream_ptr()), "mips_pack_records")
-        return rec, flags
+        return self._search(queries, k, bool(f32), True, exact_fallback, out)
 
-    def _search_exact_f32(self, q, sel, k, dist, idx, row, flags):
-        import ctypes
+    def search_exact(self, q, sel, k, dist, idx, row, flags, f32=False):
+        """The all-exact path for queries sel (int32 indices into q): their rows of dist (fp16, or fp32 when `f32`) / idx / row are
+        overwritten with the canonical top-k and their flags cleared."""
+        suffix = "_f32" if f32 else ""
         nbytes = ctypes.c_size_t()
-        _native.check(self.lib.emdr2_mips_exact_workspace_bytes_f32(self.n_rows, int(sel.numel()), ctypes.byref(nbytes)), "exact_ws_f32")
-        if self._xws is None or self._xws.numel() < nbytes.value:
-            self._xws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        _native.check(self.lib.emdr2_mips_search_exact_f32(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, q.data_ptr(), q.shape[0],
-                                                           sel.data_ptr(), int(sel.numel()), k, ids_ptr, dist.data_ptr(), idx.data_ptr(),
-                                                           row.data_ptr(), flags.data_ptr(), self._xws.data_ptr(), self._xws.numel(),
-                                                           _native.stream_ptr()), "mips_search_exact_f32")
-
-    def search_f32(self, queries, k, exact_fallback=True):
-        """FaissMIPSIndex-style scores: queries fp16 [Q, dim] -> (dist fp32 [Q,k] = RNE_fp32(exact dot), idx int32, row int64, flags),
-        order (fp32 score desc, row asc)."""
-        if self._filled != self.n_rows:
-            raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
-        if queries.dtype != torch.float16 or queries.dim() != 2 or queries.shape[1] != self.dim or not queries.is_cuda:
-            raise ValueError("queries must be a CUDA float16 [Q, %d] tensor" % self.dim)
-        if not (1 <= k <= _native.MAX_TOPK):
-            raise ValueError("top_k must be in [1, %d]" % _native.MAX_TOPK)
-        import ctypes
-        q = queries.contiguous()
-        nq = q.shape[0]
-        dist = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        idx = torch.empty((nq, k), dtype=torch.int32, device=self.device)
-        row = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        # (the search's init launch clears the flags of all nq queries: no fill launch of their own)
-        flags = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        if self.n_rows == 0:
-            flags.zero_()
-            dist.fill_(float('-inf')); idx.fill_(-1); row.fill_(-1)
-            return dist, idx, row, flags
-        ws = self._workspace(k)
-        ids_ptr = self.ids.data_ptr() if self.ids is not None else None
-        if self._shadow is not None:
-            self._search_shadow(q, k, ids_ptr, True, dist, idx, row, None, flags, ws)
-        else:
-            _native.check(self.lib.emdr2_mips_search_f32(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
-                                                         q.data_ptr(), nq, k, ids_ptr, dist.data_ptr(), idx.data_ptr(), row.data_ptr(),
-                                                         flags.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()), "mips_search_f32")
-        if exact_fallback:
-            sel = torch.nonzero(flags).to(torch.int32).flatten()
-            if sel.numel():
-                self._search_exact_f32(q, sel.contiguous(), k, dist, idx, row, flags)
-        return dist, idx, row, flags
-
-    def search_exact(self, q, sel, k, dist, idx, row, flags):
-        import ctypes
-        nbytes = ctypes.c_size_t()
-        _native.check(self.lib.emdr2_mips_exact_workspace_bytes(self.n_rows, int(sel.numel()), ctypes.byref(nbytes)), "exact_workspace_bytes")
+        _native.check(getattr(self.lib, "emdr2_mips_exact_workspace_bytes" + suffix)(self.n_rows, int(sel.numel()), ctypes.byref(nbytes)),
+                      "exact_workspace_bytes" + suffix)
         if self._xws is None or self._xws.numel() < nbytes.value:
             self._xws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         ids_ptr = self.ids.data_ptr() if self.ids is not None else None
         sel = sel.contiguous()
-        _native.check(self.lib.emdr2_mips_search_exact(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base,
-                                                       q.data_ptr(), q.shape[0], sel.data_ptr(), int(sel.numel()), k, ids_ptr,
-                                                       dist.data_ptr(), idx.data_ptr(), row.data_ptr(), flags.data_ptr(),
-                                                       self._xws.data_ptr(), self._xws.numel(), _native.stream_ptr()),
-                      "mips_search_exact")
+        _native.check(getattr(self.lib, "emdr2_mips_search_exact" + suffix)(
+            self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, q.data_ptr(), q.shape[0], sel.data_ptr(), int(sel.numel()), k, ids_ptr,
+            dist.data_ptr(), idx.data_ptr(), row.data_ptr(), flags.data_ptr(), self._xws.data_ptr(), self._xws.numel(), _native.stream_ptr()),
+            "mips_search_exact" + suffix)
 
     def debug_scores(self, queries):
         q = queries.contiguous()
@@ -741,15 +676,23 @@ class HipIndexShard(object):
 
 
 def merge_shard_results(dist, idx, row):
-    """[S, Q, k] per-shard canonical lists (device) -> merged [Q, k] via the HIP merge kernel."""
+    """[S, Q, k] per-shard canonical lists (device; dist fp16, or fp32 for the FaissMIPSIndex-style scores) -> merged [Q, k] via the HIP
+    merge kernel."""
     lib = _native.lib()
     s, nq, k = dist.shape
-    od = torch.empty((nq, k), dtype=torch.float16, device=dist.device)
+    f32 = dist.dtype == torch.float32
+    if not f32 and dist.dtype != torch.float16:
+        raise ValueError("dist must be float16 or float32")
+    od = torch.empty((nq, k), dtype=dist.dtype, device=dist.device)
     oi = torch.empty((nq, k), dtype=torch.int32, device=dist.device)
     orow = torch.empty((nq, k), dtype=torch.int64, device=dist.device)
-    _native.check(lib.emdr2_mips_merge(dist.contiguous().data_ptr(), idx.contiguous().data_ptr(), row.contiguous().data_ptr(),
-                                       s, nq, k, od.data_ptr(), oi.data_ptr(), orow.data_ptr(), _native.stream_ptr()), "mips_merge")
+    _native.check((lib.emdr2_mips_merge_f32 if f32 else lib.emdr2_mips_merge)(
+        dist.contiguous().data_ptr(), idx.contiguous().data_ptr(), row.contiguous().data_ptr(), s, nq, k, od.data_ptr(), oi.data_ptr(),
+        orow.data_ptr(), _native.stream_ptr()), "mips_merge_f32" if f32 else "mips_merge")
     return od, oi, orow
+
+
+merge_shard_results_f32 = merge_shard_results
 
 
 def merge_shard_records(records, f32=False):
@@ -764,18 +707,6 @@ def merge_shard_records(records, f32=False):
     orow = torch.empty((nq, k), dtype=torch.int64, device=records.device)
     _native.check(lib.emdr2_mips_merge_records(records.data_ptr(), s, nq, k, int(bool(f32)), od.data_ptr(), oi.data_ptr(), orow.data_ptr(),
                                                _native.stream_ptr()), "mips_merge_records")
-    return od, oi, orow
-
-
-def merge_shard_results_f32(dist, idx, row):
-    """fp32-score twin of merge_shard_results."""
-    lib = _native.lib()
-    s, nq, k = dist.shape
-    od = torch.empty((nq, k), dtype=torch.float32, device=dist.device)
-    oi = torch.empty((nq, k), dtype=torch.int32, device=dist.device)
-    orow = torch.empty((nq, k), dtype=torch.int64, device=dist.device)
-    _native.check(lib.emdr2_mips_merge_f32(dist.contiguous().data_ptr(), idx.contiguous().data_ptr(), row.contiguous().data_ptr(),
-                                           s, nq, k, od.data_ptr(), oi.data_ptr(), orow.data_ptr(), _native.stream_ptr()), "mips_merge_f32")
     return od, oi, orow
 
 
