@@ -46,6 +46,8 @@ SIGNATURES = {
     "emdr2_mips_block_norm_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
     "emdr2_mips_block_norms": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp]),
     "emdr2_mips_update_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emdr2_mips_scatter_workspace_bytes": (_i32, [_i64, _i64, ctypes.POINTER(_sz)]),
+    "emdr2_mips_update_rows_scattered": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_debug_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "emdr2_mips_set_timing": (_i32, [_i32]),
     "emdr2_mips_timing_collect": (_i32, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i64), _i32, ctypes.POINTER(_i32)]),

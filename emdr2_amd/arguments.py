@@ -117,6 +117,16 @@ def get_parser():
                         'semantics, not a tuning knob: searches then see a MIX of two embedding generations -- rows already re-embedded in '
                         'the current pass next to rows of the pass before -- where the default, the reference\'s update_index, replaces '
                         'the whole index atomically')
+    g.add_argument('--index-writeback', action='store_true',
+                   help='(not in the reference; needs --disable-retriever-dropout) at every step boundary write the embeddings the step has '
+                        'just computed with the LIVE context encoder for the batch-size x topk passages it retrieved into the index rows they '
+                        'were retrieved from (with several ranks: two all-gathers per step, every rank updates its own shard).  No encoder '
+                        'work is added.  A row holds whatever was written LAST: a passage retrieved by several questions keeps the last '
+                        'one\'s embedding, and the rolling refresher (--async-indexer --index-refresh-in-place) will later overwrite a '
+                        'written-back row with its older snapshot\'s embedding when its pass comes round.  A choice of semantics, not a '
+                        'tuning knob: the index holds a mix of embedding generations, the retrieved rows being the freshest.  Allowed '
+                        'without --async-indexer; with --async-indexer it needs --index-refresh-in-place (in swap mode every write would '
+                        'be discarded at the next swap)')
     g.add_argument('--save-index-snapshot', action='store_true',
                    help='(not in the reference; needs --save) with --async-indexer: after every index update write the index just committed '
                         'to the one file <save>/evidence_index.flat (+ .meta), overwritten atomically like the reference\'s embedding file, a '
@@ -154,6 +164,11 @@ def parse_args(argv=None):
         raise ValueError("--load and --ict-load are exclusive (indexer_emdr2.py:47)")
     if args.save_index_snapshot and not args.save:
         raise ValueError("--save-index-snapshot needs --save (the snapshot lives next to the checkpoints)")
+    if args.index_writeback and not args.disable_retriever_dropout:
+        raise ValueError("--index-writeback needs --disable-retriever-dropout (a training-mode context tower would write dropout noise into the index)")
+    if args.index_writeback and args.async_indexer and not args.index_refresh_in_place:
+        raise ValueError("--index-writeback with --async-indexer needs --index-refresh-in-place (in swap mode a refresh is always in progress: "
+                         "the index refuses in-place updates, and the next swap would discard them anyway)")
     args.iteration = 0
     # the reference's --fp16 (fp16 activations, fp32 masters inside FP16_Optimizer, dynamic loss scaling) maps to this build's ONLY
     # precision mode: bf16 activations and working weights, fp32 master weights and gradients, no loss scaling.  Said once, recorded in args.

@@ -378,6 +378,45 @@ int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_
     return EMDR2_OK;
 }
 
+// workspace of a scattered update: one claim word per 256-row block of the padded image, the touched-block counter (a 16-byte slot), then
+// the touched-block list, min(n_upd, table blocks) entries
+static size_t scatter_claim_bytes(int64_t table_blocks) { return ((size_t)table_blocks * sizeof(unsigned) + 15) / 16 * 16; }
+static bool bad_scatter_shape(int64_t n_rows_total, int64_t n_upd) { return bad_shape(n_rows_total, 64) || n_upd < 0 || n_upd >= ((int64_t)1 << 31) - 1024; }
+
+int emdr2_mips_scatter_workspace_bytes(int64_t n_rows_total, int64_t n_upd, size_t *bytes)
+{
+    if (!bytes || bad_scatter_shape(n_rows_total, n_upd)) return EMDR2_E_BADARG;
+    const int64_t table_blocks = (n_rows_total + 511) / 512 * 2;
+    *bytes = scatter_claim_bytes(table_blocks) + 16 + (size_t)(n_upd < table_blocks ? n_upd : table_blocks) * sizeof(unsigned);
+    return EMDR2_OK;
+}
+
+int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled,
+                                     float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, void *workspace,
+                                     size_t workspace_bytes, emdr2_stream_t stream_)
+{
+    if (!rows_rm || !row_ids || !tiled || !block_norm_sq || !emax_sq || !workspace || ((uintptr_t)workspace & 15) || bad_shape(n_rows_total, dim) ||
+        bad_scatter_shape(n_rows_total, n_upd))
+        return EMDR2_E_BADARG;
+    if (shadow && (!table || !nonfinite || ((uintptr_t)table & 15) || (dim % 256) != 0)) return EMDR2_E_BADARG;
+    if (n_upd == 0) return EMDR2_OK;
+    size_t need;
+    emdr2_mips_scatter_workspace_bytes(n_rows_total, n_upd, &need);
+    if (workspace_bytes < need) return EMDR2_E_WORKSPACE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t table_blocks = (n_rows_total + 511) / 512 * 2;
+    const unsigned cap = (unsigned)(n_upd < table_blocks ? n_upd : table_blocks);      // no more distinct blocks than rows, or than there are
+    const size_t claim_bytes = scatter_claim_bytes(table_blocks);
+    unsigned *claimed = (unsigned *)workspace, *n_touched = (unsigned *)((char *)workspace + claim_bytes), *touched = n_touched + 4;
+    if (hipMemsetAsync(workspace, 0, claim_bytes + 16, stream) != hipSuccess) return EMDR2_E_LAUNCH;
+    int rc;
+    if ((rc = mips_launch_write_rows_at(rows_rm, row_ids, n_upd, dim, n_rows_total, tiled, claimed, n_touched, touched, cap, stream))) return rc;
+    if ((rc = mips_launch_block_norms_list(tiled, dim, touched, n_touched, cap, block_norm_sq, stream))) return rc;
+    if ((rc = mips_launch_table_max(block_norm_sq, table_blocks, emax_sq, stream))) return rc;
+    if (shadow) return mips_launch_seal_shadow_list(tiled, dim, touched, n_touched, cap, shadow, (float *)table, nonfinite, stream);
+    return EMDR2_OK;
+}
+
 int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const void *shadow,
                              const void *table, int64_t shadow_min_rows, const void *queries, int n_q, int k, const int32_t *ids, int f32,
                              void *out_dist, int32_t *out_idx, int64_t *out_row, void *out_records, uint32_t *out_flags, void *workspace,

@@ -59,13 +59,16 @@ __global__ void row_norm_max_kernel(const uint4 *__restrict__ rows_rm, int64_t n
     if (lane == 0 && best > 0.f) atomicMax((unsigned *)emax_sq, __float_as_uint(best)); // non-negative floats order as uints
 }
 
-// In-place row updates (emdr2_mips_update_rows): block_norm_sq[b] = max over the 256 rows of block b of ||E[r]||^2, read from the tiled
-// image (rows past the end of the shard are zero there, the image is padded to 512 rows).  One workgroup per block, 64 rows per wave.
-__global__ void __launch_bounds__(256) block_norms_kernel(const char *__restrict__ tiled, int nseg, int64_t first_block, float *__restrict__ block_norm_sq)
+// In-place row updates (emdr2_mips_update_rows, _update_rows_scattered): block_norm_sq[b] = max over the 256 rows of block b of ||E[r]||^2,
+// read from the tiled image (rows past the end of the shard are zero there, the image is padded to 512 rows).  One workgroup per block, 64
+// rows per wave.  The block comes from a range or from the list of touched blocks (mips_device.h); the arithmetic is this one routine.
+template <class Blocks>
+__global__ void __launch_bounds__(256) block_norms_kernel(const char *__restrict__ tiled, int nseg, Blocks blocks, float *__restrict__ block_norm_sq)
 {
     __shared__ float sh[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t block = first_block + blockIdx.x;
+    int64_t block;
+    if (!blocks.get(block)) return;
     float best = 0.f;
 #pragma unroll 4                                                 // (four rows' loads in flight; each row's own arithmetic is untouched)
     for (int i = 0; i < 64; ++i) best = fmaxf(best, row_norm_sq_wave(TiledRow{tiled, block * 256 + wave * 64 + i, nseg >> 2}, nseg, lane));
@@ -94,7 +97,18 @@ __global__ void __launch_bounds__(1024) table_max_kernel(const float *__restrict
 int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq, hipStream_t stream)
 {
     if (n_blocks == 0) return 0;
-    hipLaunchKernelGGL(block_norms_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 8, first_block, block_norm_sq);
+    hipLaunchKernelGGL(block_norms_kernel<BlockRange>, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 8, BlockRange{first_block},
+                       block_norm_sq);
+    return CHECK_LAUNCH();
+}
+
+// the same over the touched-block list of a scattered update: `grid` workgroups, those not below *n_touched exit
+int mips_launch_block_norms_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, float *block_norm_sq,
+                                 hipStream_t stream)
+{
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL(block_norms_kernel<BlockList>, dim3(grid), dim3(256), 0, stream, (const char *)tiled, dim / 8, BlockList{touched, n_touched},
+                       block_norm_sq);
     return CHECK_LAUNCH();
 }
 
@@ -112,6 +126,44 @@ int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_
     if (total == 0) return 0;
     hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg,
                        row_offset, (char *)tiled);
+    return CHECK_LAUNCH();
+}
+
+// Scattered in-place updates (emdr2_mips_update_rows_scattered): pack_rows_kernel with the destination row read from row_ids.  Entries whose
+// id is outside [0, n_rows_total) are skipped, so nothing is ever written into the zero padding or past the image.  The thread that moves
+// a row's first segment also claims the row's 256-row block: an atomic exchange on the block's flag word (zeroed per call), and whoever
+// finds it 0 appends the block to `touched` through the counter -- once per block however many rows of the call fall into it.  Both are
+// device-scope atomics on words nobody reads in this launch; the list and its count are read by LATER launches on the same stream.  At most
+// min(n_upd, table blocks) = `cap` distinct blocks can be claimed, which is the list's length.
+__global__ void pack_rows_at_kernel(const uint4 *__restrict__ rows_rm, const int64_t *__restrict__ row_ids, int64_t n_upd, int nseg, int64_t n_rows_total,
+                                    char *__restrict__ tiled, unsigned *__restrict__ claimed, unsigned *__restrict__ n_touched,
+                                    unsigned *__restrict__ touched, unsigned cap)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_upd * nseg) return;
+    const int64_t r = i / nseg;
+    const int seg = (int)(i - r * nseg);
+    const int64_t row = row_ids[r];
+    if (row < 0 || row >= n_rows_total) return;
+    *(uint4 *)(tiled + tiled_seg_offset(row, seg, nseg >> 2)) = rows_rm[i];
+    if (seg == 0) {
+        const unsigned b = (unsigned)(row >> 8);
+        if (atomicExch(&claimed[b], 1u) == 0u) {
+            const unsigned slot = atomicAdd(n_touched, 1u);
+            if (slot < cap) touched[slot] = b;
+        }
+    }
+}
+
+int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled, unsigned *claimed,
+                              unsigned *n_touched, unsigned *touched, unsigned cap, hipStream_t stream)
+{
+    const int nseg = dim / 8;
+    const int64_t total = n_upd * nseg;
+    if (total == 0) return 0;
+    if ((total + 255) / 256 > 0x7fffffff) return -4;
+    hipLaunchKernelGGL(pack_rows_at_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4 *)rows_rm, row_ids, n_upd, nseg,
+                       n_rows_total, (char *)tiled, claimed, n_touched, touched, cap);
     return CHECK_LAUNCH();
 }
 

@@ -26,6 +26,24 @@ __device__ __forceinline__ size_t tiled_seg_offset(int64_t row, int seg /* k/8 *
     return ((size_t)(stripe * nch + c) * 512 + (size_t)(ri * 4 + sp)) * 16;
 }
 
+// Which 256-row block a workgroup of the block-norm / seal kernels works on.  A contiguous range (a fresh build, emdr2_mips_update_rows):
+// workgroup i takes block first + i.  A list (emdr2_mips_update_rows_scattered): workgroup i takes list[i] if i < *count, else it has
+// nothing to do -- list and count were written by an EARLIER launch on the same stream, so plain loads see them.  The answer is uniform
+// over the workgroup.  The kernels' arithmetic is one routine that takes the block number, whichever of the two named it.
+struct BlockRange {
+    int64_t first;
+    __device__ __forceinline__ bool get(int64_t &block) const { block = first + blockIdx.x; return true; }
+};
+struct BlockList {
+    const unsigned *list, *count;
+    __device__ __forceinline__ bool get(int64_t &block) const
+    {
+        if (blockIdx.x >= *count) return false;
+        block = (int64_t)list[blockIdx.x];
+        return true;
+    }
+};
+
 // monotone maps: larger unsigned <=> larger value
 __device__ __forceinline__ uint32_t f32_order(float f)
 {

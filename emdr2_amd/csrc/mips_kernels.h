@@ -38,6 +38,9 @@ int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t ro
 // Seals the 256-row blocks [first_block, first_block + n_blocks); the whole shard is [0, ceil(n_rows / 256)).
 int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, void *e8, float *blk, unsigned *nonfinite,
                             hipStream_t stream);
+// the same seal over a device list of blocks (a scattered row update): `grid` workgroups, workgroup i seals touched[i] if i < *n_touched
+int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, void *e8, float *blk,
+                                 unsigned *nonfinite, hipStream_t stream);
 // int8 query image [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -}
 int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream);
 // mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_triage has run
@@ -65,6 +68,13 @@ int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t
 int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, hipStream_t stream);
 int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq, hipStream_t stream);
 int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream);
+// scattered row updates: rows_rm[i] into image row row_ids[i] (ids outside [0, n_rows_total) skipped); every touched 256-row block is
+// claimed once through claimed[table blocks] (zeroed by the caller) and appended to touched[cap] through *n_touched (zeroed too);
+// then the block norms of exactly the listed blocks
+int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled, unsigned *claimed,
+                              unsigned *n_touched, unsigned *touched, unsigned cap, hipStream_t stream);
+int mips_launch_block_norms_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, float *block_norm_sq,
+                                 hipStream_t stream);
 int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, int64_t n_out, void *rows_rm,
                             hipStream_t stream);
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]

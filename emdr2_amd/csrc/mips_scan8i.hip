@@ -109,12 +109,15 @@ __device__ __forceinline__ int quant8(float x, float inv)
 // One workgroup per 256-row block, one thread per row.  Pass 1: max |e| and max ||e_r||^2 of the block; pass 2 (the block is in L2 now):
 // quantise with the block's scale, write the int8 rows, measure ||e_r - s_b e8_r||.  Rows past the end of the shard are zero in the fp16
 // image and stay zero here.  Workgroup i seals block first_block + i and reads or writes nothing of any other block: a full seal is the range
-// [0, n_blocks), an in-place row update (emdr2_mips_update_rows) re-seals the blocks it touched with the very same code.
-__global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict__ tiled, int nch, int64_t first_block, char *__restrict__ e8,
+// [0, n_blocks), an in-place row update re-seals the blocks it touched with the very same code: a range (emdr2_mips_update_rows) or the
+// touched-block list of a scattered update (emdr2_mips_update_rows_scattered), see BlockRange / BlockList in mips_device.h.
+template <class Blocks>
+__global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict__ tiled, int nch, Blocks blocks, char *__restrict__ e8,
                                                           float4 *__restrict__ blk, unsigned *__restrict__ nonfinite)
 {
     __shared__ float sh[4];
-    const int64_t block = first_block + blockIdx.x;
+    int64_t block;
+    if (!blocks.get(block)) return;
     const int64_t row = block * 256 + threadIdx.x;
     const int nseg = nch * 4;
     float amax = 0.f, n2 = 0.f;
@@ -392,8 +395,17 @@ int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int
                             hipStream_t stream)
 {
     if (n_blocks == 0) return 0;
-    hipLaunchKernelGGL(seal_shadow_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 32, first_block, (char *)e8,
-                       (float4 *)blk, nonfinite);
+    hipLaunchKernelGGL(seal_shadow_kernel<BlockRange>, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 32, BlockRange{first_block},
+                       (char *)e8, (float4 *)blk, nonfinite);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, void *e8, float *blk,
+                                 unsigned *nonfinite, hipStream_t stream)
+{
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL(seal_shadow_kernel<BlockList>, dim3(grid), dim3(256), 0, stream, (const char *)tiled, dim / 32, BlockList{touched, n_touched},
+                       (char *)e8, (float4 *)blk, nonfinite);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -369,6 +369,18 @@ def shard_bounds(num_rows, world_size):
     return [(min(r * chunk, num_rows), min((r + 1) * chunk, num_rows)) for r in range(world_size)]
 
 
+def resolve_duplicate_rows(row_ids):
+    """int64 [n] row numbers -> a copy in which, of every value that occurs more than once, all occurrences but the LAST are -1 (which
+    `HipIndexShard.update_rows_at` skips): later entries of an update list win.  Static shapes and no host read, so it runs on the
+    device inside a training step; on CPU tensors too.  A stable sort keeps equal values in list order, so an element that equals its
+    successor is not the last of its value; those positions receive -1 through the sort's own permutation."""
+    order = torch.argsort(row_ids, stable=True)
+    s = row_ids[order]
+    loses = torch.zeros_like(s, dtype=torch.bool)
+    loses[:-1] = s[:-1] == s[1:]
+    return torch.empty_like(row_ids).scatter_(0, order, torch.where(loses, torch.full_like(s, -1), s))
+
+
 class HipIndexShard(object):
     """One contiguous row shard resident in this process's GPU, stripe-tiled for the HIP scan.
 
@@ -400,6 +412,7 @@ class HipIndexShard(object):
         self._spare = None                                         # the second fp16 image of a swap refresh (begin_refresh)
         self._refreshing = False                                   # between begin_refresh and commit_refresh
         self._block_norms = None                                   # max ||row||^2 per 256-row block of self.tiled (update_rows), built on first use
+        self._scatter_ws = None                                    # workspace of update_rows_at (claim words + touched-block list), grown on demand
 
     def _seal(self, tiled, into):
         """Build the int8 shadow of the finished fp16 image `tiled` (on the current stream) into the buffers `into` (allocated on first
@@ -489,17 +502,57 @@ class HipIndexShard(object):
         image) and again after a `commit_refresh`.  If an updated block holds an inf / NaN the shard stops using its shadow until the
         next full seal, like a shard freshly built from such rows; that flag is read back with one `.item()` per call on a shard with a
         sealed shadow (a host synchronisation on the current stream -- the search that follows does one of its own)."""
-        if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_cuda:
-            raise ValueError("rows must be a CUDA float16 [n, %d] tensor" % self.dim)
+        self._check_update_rows(rows)
         n = rows.shape[0]
         if local_row < 0 or local_row + n > self.n_rows:
             raise ValueError("update rows out of range")
+        self._check_updatable()
+        if n == 0:
+            return
+        rows = rows.contiguous()
+        self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows(
+            rows.data_ptr(), n, self.dim, local_row, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow, image, bad,
+            _native.stream_ptr()), "update_rows"))
+
+    def update_rows_at(self, local_rows, rows):
+        """`update_rows` addressed by a list: rows fp16 [n, dim] and local_rows int64 [n], both on this device; entry i goes to row
+        local_rows[i] of the LIVE image (csrc: emdr2_mips_update_rows_scattered).  Entries outside [0, n_rows) are skipped, so a list
+        that also names rows of other shards needs no compaction.  Where a row is named more than once the LAST occurrence wins
+        (`resolve_duplicate_rows`, on the device, no host read).  Same preconditions, same result and same non-finite read-back as
+        `update_rows`: afterwards the shard is byte for byte a fresh build of the same rows."""
+        self._check_update_rows(rows)
+        if local_rows.dtype != torch.int64 or local_rows.dim() != 1 or not local_rows.is_cuda:
+            raise ValueError("local_rows must be a CUDA int64 [n] tensor")
+        n = rows.shape[0]
+        if local_rows.shape[0] != n:
+            raise ValueError("%d row numbers for %d rows" % (local_rows.shape[0], n))
+        self._check_updatable()
+        if n == 0:
+            return
+        rows = rows.contiguous()
+        ids = resolve_duplicate_rows(local_rows.contiguous())
+        nbytes = ctypes.c_size_t()
+        _native.check(self.lib.emdr2_mips_scatter_workspace_bytes(self.n_rows, n, ctypes.byref(nbytes)), "scatter_workspace_bytes")
+        if self._scatter_ws is None or self._scatter_ws.numel() < nbytes.value:
+            self._scatter_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        ws = self._scatter_ws
+        self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows_scattered(
+            rows.data_ptr(), ids.data_ptr(), n, self.dim, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow, image,
+            bad, ws.data_ptr(), ws.numel(), _native.stream_ptr()), "update_rows_scattered"))
+
+    def _check_update_rows(self, rows):
+        if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_cuda:
+            raise ValueError("rows must be a CUDA float16 [n, %d] tensor" % self.dim)
+
+    def _check_updatable(self):
         if self._filled != self.n_rows:
             raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
         if self._refreshing:
             raise RuntimeError("a swap refresh is in progress (begin_refresh without commit_refresh): its commit would discard the update")
-        if n == 0:
-            return
+
+    def _run_update(self, call):
+        """What both in-place updates share: the block-norm table (built on first use), the sealed shadow's pointers and the read-back of
+        the non-finite flag.  call(table, shadow image ptr, shadow table ptr, flag ptr) enqueues the update itself."""
         if self._block_norms is None:
             nbytes = ctypes.c_size_t()
             _native.check(self.lib.emdr2_mips_block_norm_bytes(self.n_rows, ctypes.byref(nbytes)), "block_norm_bytes")
@@ -507,15 +560,13 @@ class HipIndexShard(object):
             _native.check(self.lib.emdr2_mips_block_norms(self.tiled.data_ptr(), self.n_rows, self.dim, 0, table.numel(), table.data_ptr(),
                                                           _native.stream_ptr()), "block_norms")
             self._block_norms = table
-        rows = rows.contiguous()
         shadow = self._shadow
-        bad = torch.zeros(1, dtype=torch.int32, device=self.device) if shadow is not None else None
-        _native.check(self.lib.emdr2_mips_update_rows(rows.data_ptr(), n, self.dim, local_row, self.n_rows, self.tiled.data_ptr(),
-                                                      self._block_norms.data_ptr(), self.emax_sq.data_ptr(),
-                                                      shadow[0].data_ptr() if shadow is not None else None,
-                                                      shadow[1].data_ptr() if shadow is not None else None,
-                                                      bad.data_ptr() if shadow is not None else None, _native.stream_ptr()), "update_rows")
-        if shadow is not None and int(bad.item()) != 0:
+        if shadow is None:
+            call(self._block_norms, None, None, None)
+            return
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        call(self._block_norms, shadow[0].data_ptr(), shadow[1].data_ptr(), bad.data_ptr())
+        if int(bad.item()) != 0:
             self._shadow = None
 
     def set_ids(self, ids):
@@ -725,6 +776,7 @@ class DistributedBruteForceIndex(object):
         self.process_group = process_group
         self.shard = None
         self.num_rows = 0
+        self.last_search_rows = None                               # global rows int64 [Q, k] of the last search_mips_index (-1 in empty slots)
         self._set_mips_index()
 
     # -- distributed helpers (overridable in CPU tests) ---------------------------------------------
@@ -789,6 +841,12 @@ class DistributedBruteForceIndex(object):
         if global_row < lo or global_row + rows.shape[0] > hi:
             raise ValueError("rows [%d, %d) are not all in this rank's shard [%d, %d)" % (global_row, global_row + rows.shape[0], lo, hi))
         self.shard.update_rows(global_row - lo, rows)
+
+    def update_rows_at(self, global_rows, rows):
+        """rows fp16 [n, dim], global_rows int64 [n] (both on the device) -> those rows of the image this rank is searching
+        (HipIndexShard.update_rows_at).  Rows of other ranks' shards, and -1, fall out of the shard's range and are skipped: every rank can
+        be handed the same gathered list.  Where a row is named twice the last occurrence wins."""
+        self.shard.update_rows_at(global_rows - self.shard.row_base, rows)
 
     def add_embed_data(self, all_embed_data):
         """Upload this rank's row shard (reference: emdr2_index.py:241-266; there: rank 0 uploads
@@ -855,9 +913,9 @@ class DistributedBruteForceIndex(object):
             q = q.to(torch.float16)   # reference queries are fp16 under FP16_Module; bf16/fp32 are rounded once
         rank, world = self._world()
         if world == 1:
-            dist, idx, _, _ = self.shard.search(q.contiguous(), top_k)
+            dist, idx, self.last_search_rows, _ = self.shard.search(q.contiguous(), top_k)
             return dist, idx
-        dist, idx, _ = self._search_exchange_merge(q.contiguous(), top_k, rank, world, f32=False)
+        dist, idx, self.last_search_rows = self._search_exchange_merge(q.contiguous(), top_k, rank, world, f32=False)
         return dist, idx
 
     def _search_exchange_merge(self, q, top_k, rank, world, f32):

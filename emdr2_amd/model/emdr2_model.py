@@ -125,6 +125,8 @@ class PreComputedEvidenceDocsRetriever(object):
         distance, topkindex = self.mips_index.search_mips_index(allq, top_k=self.topk, reconstruct=False)
         sl = slice(rank * local_bsize, (rank + 1) * local_bsize)
         self.searches = getattr(self, "searches", 0) + 1        # (the forward's collectives are behind us: bench_e2e's out-of-memory recovery asks)
+        rows = getattr(self.mips_index, "last_search_rows", None)  # global index rows [Q, k] behind topkindex (--index-writeback)
+        self.last_search_rows = rows[sl] if rows is not None else None
         return distance[sl], topkindex[sl]
 
     def get_topk(self, query_tensor):
@@ -145,7 +147,19 @@ class PreComputedEvidenceDocsRetriever(object):
         distance, topkindex = self._search(query_tensor)
         out = self.arena.assemble(topkindex, self.args.topk_retrievals, query_uid, query_ids_t5, query_ids_t5_len,
                                   self.args.seq_length_ret, self.args.seq_length, cls_id, sep_id, pad_id)
+        self.last_kept_rows = None
+        if getattr(self, "track_rows", False) and self.last_search_rows is not None:
+            self.last_kept_rows = kept_rows(out[4], topkindex, self.last_search_rows)
         return out + (distance,)
+
+
+def kept_rows(kept_ids, searched_ids, searched_rows):
+    """The index rows [b, K] of the doc ids `assemble` kept [b, K], found among the question's own searched (doc id [b, k], row [b, k])
+    pairs, k = K or K + 1: doc ids are unique per index, so a kept id matches exactly one searched slot (the slot dropped as trivial, or
+    as the surplus one, matches none and is never named).  Empty slots (-1) stay -1.  Static shapes, no host read."""
+    match = kept_ids.unsqueeze(2) == searched_ids.unsqueeze(1)                               # [b, K, k]
+    rows = searched_rows.gather(1, match.to(torch.int8).argmax(2))
+    return torch.where((kept_ids >= 0) & match.any(2), rows, torch.full_like(rows, -1))
 
 
 # =====================================================================================================================
@@ -220,6 +234,10 @@ class EMDR2Model(torch.nn.Module):
         self.no_query_embedder_training = no_query_embedder_training              # emdr2_model.py:103-104
         self.no_context_embedder_training = no_context_embedder_training          # emdr2_model.py:130-131
         self.fuse_lm_head_loss = True          # one-context pass: LM head + log-softmax + gather in one GEMM (OneContextLogits); False = reference tensor
+        # --index-writeback: in training mode keep the step's fresh context embeddings and the index rows they belong to, for
+        # `take_writeback` at the step boundary.  Off: nothing is kept and the retriever does not track rows.
+        self.index_writeback = False
+        self._writeback_rows, self._writeback_embeds = None, []
 
     def retriever_embedder(self, tokens, mask, types, embedder_type, disable_dropout=False):
         tower = self.retriever_model.query_model if embedder_type == "query" else self.retriever_model.context_model
@@ -236,13 +254,36 @@ class EMDR2Model(torch.nn.Module):
         if all_query_context_hidden_states is not None:
             lm_logits = self.language_model.decode(dec_ids, all_query_context_hidden_states, all_query_context_ids_unflat)
             return lm_logits, topk_log_probs, all_query_context_hidden_states, all_query_context_ids_unflat
+        self._begin_writeback()
         query_logits = self.retriever_embedder(query_ids_bert, None, query_types, "query", self.disable_retriever_dropout)
         if self.no_query_embedder_training:
             query_logits = query_logits.detach()
         with torch.no_grad():                                            # emdr2_model.py:107-115 on the device
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
+        self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
         return self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids)
+
+    def _keeps_writeback(self):
+        return self.index_writeback and self.training
+
+    def _begin_writeback(self):
+        """Start of a step's forward: drop what an earlier (possibly failed and now re-run) step kept, tell the retriever whether to
+        track the rows of what it retrieves."""
+        self._writeback_rows, self._writeback_embeds = None, []
+        if self.index_writeback:
+            self.evidence_retriever.track_rows = self.training
+
+    def take_writeback(self):
+        """(index rows int64 [B * K], fresh embeddings fp16 [B * K, H]) of the passages the last training step embedded, in question /
+        slot order across the step's groups, and forget them; rows of empty slots are -1.  None when nothing (complete) is kept: the
+        flag is off, the step ran in eval mode, or its forward did not finish.  The cast is `IndexBuilder.embed`'s."""
+        rows, embeds = self._writeback_rows, self._writeback_embeds
+        self._writeback_rows, self._writeback_embeds = None, []
+        if rows is None or sum(e.shape[0] for e in embeds) != rows.shape[0]:
+            return None
+        emb = torch.cat(embeds, dim=0) if len(embeds) > 1 else embeds[0]
+        return rows.reshape(-1).to(torch.int64), emb.reshape(-1, emb.shape[-1]).to(torch.float16)
 
     def forward_assembled(self, query_logits, ctx_ids, ctx_types, qext, qone, dec_ids):
         B, Kk = ctx_ids.shape[:2]
@@ -251,6 +292,8 @@ class EMDR2Model(torch.nn.Module):
                                              self.disable_retriever_dropout).reshape(B, Kk, H)
         if self.no_context_embedder_training:
             ctx_logits = ctx_logits.detach()
+        if self._writeback_rows is not None and self._keeps_writeback():
+            self._writeback_embeds.append(ctx_logits.detach())          # [b, K, H] of this call's questions (--index-writeback)
         # fresh retriever scores -> prior over the K passages (emdr2_model.py:134-145): fp32 dot products, /sqrt(H), log-softmax, one HIP kernel
         topk_log_probs = K.retriever_prior(query_logits, ctx_logits, 1.0 / math.sqrt(H) if self.retriever_score_scaling else 1.0)
 
@@ -315,12 +358,14 @@ class EMDR2Model(torch.nn.Module):
         if not self.training:
             raise ValueError("forward_backward is a training-mode call")
         totals = loss_totals(labels, loss_mask, eos_id)
+        self._begin_writeback()
         query_logits = self.retriever_embedder(query_ids_bert, None, query_types, "query", self.disable_retriever_dropout)
         if self.no_query_embedder_training:
             query_logits = query_logits.detach()
         with torch.no_grad():                                            # ONE search + device-side fetch / assembly for all B questions
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
+        self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
         Kk = ctx_ids.shape[1]
         q_leaf = query_logits.detach().requires_grad_(query_logits.requires_grad)
         bounds = question_group_bounds(B, m)

@@ -203,6 +203,34 @@ def _save(iteration, model, optimizer, lr_scheduler):
                                   barrier=torch.distributed.barrier if world > 1 else None, args=args)
 
 
+def index_writeback(model, batch_size, topk):
+    """--index-writeback, at a step boundary: the embeddings the step has just computed for the passages it retrieved
+    (`EMDR2Model.take_writeback`) go into the index rows they were retrieved from (`update_rows_at`).  The list always has
+    batch_size * topk entries, padded with row -1 (skipped): the short last batch of an epoch under --keep-last, empty retrieval slots,
+    a step that kept nothing.  With more than one rank every rank gathers all ranks' lists -- ONE all-gather of the row numbers and ONE
+    of the fp16 rows over the retriever's group, issued by every rank at every boundary so that the collective sequence stays static
+    -- and applies the gathered list to its own shard: rows of other shards fall out of range there.  A passage retrieved by several
+    questions holds the embedding of the last (rank, question, slot) that names it, the same on every rank."""
+    retriever = model.evidence_retriever
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n = int(batch_size) * int(topk)
+    rows = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    embeds = torch.zeros((n, model.hidden_size), dtype=torch.float16, device=dev)
+    kept = model.take_writeback()
+    if kept is not None:
+        rows[:kept[0].shape[0]] = kept[0]
+        embeds[:kept[1].shape[0]] = kept[1]
+    rank, world = retriever._world()
+    if world > 1:
+        all_rows = torch.empty((world * n,), dtype=rows.dtype, device=dev)
+        all_embeds = torch.empty((world * n, embeds.shape[1]), dtype=embeds.dtype, device=dev)
+        torch.distributed.all_gather_into_tensor(all_rows, rows, group=retriever.process_group)
+        # (as bytes: a gather moves bits, and not every transport knows fp16)
+        torch.distributed.all_gather_into_tensor(all_embeds.view(torch.uint8), embeds.view(torch.uint8), group=retriever.process_group)
+        rows, embeds = all_rows, all_embeds
+    retriever.mips_index.update_rows_at(rows, embeds)
+
+
 def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_of_epoch_callback, end_of_epoch_callback2, eos_id, indexer=None):
     """train_e2eqa.py:413-552.  `indexer`: an AsyncIndexBuilder when --async-indexer (re-indexing on a side stream; the swap at a step
     boundary replaces the NEW_INDEX_READY / NEW_CHKPT_READY handshake and the reload from disk)."""
@@ -255,6 +283,9 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                         snapshots.finish()
                     snapshots.begin(snapshot_path, {"iteration": iteration, "refreshes": indexer.refreshes,
                                                     "mode": "rolling" if indexer.in_place else "swap"})
+            if getattr(args, "index_writeback", False):
+                # after the refresher's rows of this boundary (they come from an older snapshot of the weights): the write-back goes last and wins
+                index_writeback(model, args.batch_size, args.topk_retrievals)
             if snapshots is not None:
                 snapshots.pump()
                 snapshots.maybe_finalize(iteration)

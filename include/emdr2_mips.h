@@ -206,12 +206,33 @@ int emdr2_mips_shadow_launches(void);
  *                      of _seal_shadow, OR-ing 1 into *nonfinite (device uint32) if one of them holds an inf / NaN.  A few small launches
  *                      on `stream`; nothing allocated, no host synchronisation.  The caller orders it against searches of the shard.
  *                      n_chunk == 0 is a no-op.  shadow == NULL: table and nonfinite are ignored.
+ *   _update_rows_scattered  the same update addressed by a LIST of rows (add_block_data takes a list of ids, not a range): rows_rm is device
+ *                      fp16 [n_upd, dim], row_ids device int64 [n_upd], local rows in any order; entry i writes rows_rm[i] into image row
+ *                      row_ids[i].  An entry whose id is outside [0, n_rows_total) is SKIPPED -- negative ids, ids past the end, ids that
+ *                      fall into the zero padding up to the next multiple of 512 -- so a rank can be handed a gathered list that also names
+ *                      rows of other shards without compacting it on the host.  The valid ids must be distinct; that is the caller's duty,
+ *                      as ordering against searches is.  Otherwise the row holds a mix of the 16-byte segments of its sources (each segment
+ *                      is one store of one source; which source wins a segment is not defined), and the derived structures describe
+ *                      whatever mix was stored.  Afterwards the image, the touched entries of block_norm_sq, *emax_sq (the maximum of the
+ *                      whole table, so it can fall) and, with shadow != NULL, the touched 256-row blocks of the int8 image and its table
+ *                      are bit for bit what _pack_rows + _seal_shadow leave after a fresh build of the same rows; *nonfinite gets 1 OR-ed in
+ *                      if a touched block holds an inf / NaN.  The norm and seal arithmetic is that of _update_rows, run over a device-side
+ *                      list of the touched blocks instead of a range.  Nothing is allocated, no host synchronisation; one memset and at
+ *                      most four launches on `stream`, whatever the list holds.  workspace: device memory, 16-byte aligned, at least
+ *                      _scatter_workspace_bytes(n_rows_total, n_upd) bytes (one claim word per 256-row block of the padded image, a
+ *                      counter, a block list of min(n_upd, blocks) entries); its contents need not be kept between calls.
+ *                      n_upd == 0 is a no-op returning 0.  EMDR2_E_BADARG: null pointers, a bad dim, a misaligned table or workspace,
+ *                      shadow without table / nonfinite; EMDR2_E_WORKSPACE: workspace_bytes too small.
  */
 int emdr2_mips_block_norm_bytes(int64_t n_rows, size_t *bytes);
 int emdr2_mips_block_norms(const void *tiled, int64_t n_rows, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq,
                            emdr2_stream_t stream);
 int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
                            float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream);
+int emdr2_mips_scatter_workspace_bytes(int64_t n_rows_total, int64_t n_upd, size_t *bytes);
+int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total,
+                                     void *tiled, float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite,
+                                     void *workspace, size_t workspace_bytes, emdr2_stream_t stream);
 
 /* Diagnostics for tests: fp32 MFMA scores S~[n_q, n_rows] (row-major float) of the scan kernel's
  * arithmetic, for measuring |S~ - exact| against the bound used by the validity check. */

@@ -245,7 +245,7 @@ def index_and_recall(tmp, vocab, ev, dual_encoder, name, ks=(1, 5, 20)):
     return acc, emb
 
 
-def argv(tmp, vocab, ev, emb, dpr, t5, epochs, batch=16, topk=16, lr=1e-3, update_retriever=True, reload_interval=25, extra=()):
+def argv(tmp, vocab, ev, emb, dpr, t5, epochs, batch=16, topk=16, lr=1e-3, update_retriever=True, reload_interval=25, extra=(), refresher=True):
     a = ["--task", "OPENQA", "--num-layers", str(LAYERS), "--hidden-size", str(HIDDEN), "--num-attention-heads", str(HEADS), "--kv-channels",
          str(HIDDEN // HEADS), "--ffn-hidden-size", str(FFN), "--model-parallel-size", "1", "--train-data", os.path.join(tmp, "train.tsv"),
          "--valid-data", os.path.join(tmp, "valid.tsv"), "--evidence-data-path", ev, "--indexed-evidence-data-path", os.path.join(tmp, "text"),
@@ -255,7 +255,7 @@ def argv(tmp, vocab, ev, emb, dpr, t5, epochs, batch=16, topk=16, lr=1e-3, updat
          "--distributed-backend", "nccl", "--tokenizer-type", "BertWordPieceLowerCase", "--epochs", str(epochs), "--sample-rate", "1.0",
          "--batch-size", str(batch), "--eval-batch-size", "50", "--beam-size", "1", "--lr", str(lr), "--warmup", "0.05", "--DDP-impl", "local",
          "--lr-decay-style", "linear", "--max-training-rank", "1", "--faiss-use-gpu", "--topk-retrievals", str(topk), "--emdr2-training",
-         "--retriever-score-scaling", "--allow-trivial-doc", "--async-indexer", "--index-reload-interval", str(reload_interval),
+         "--retriever-score-scaling", "--allow-trivial-doc"] + (["--async-indexer", "--index-reload-interval", str(reload_interval)] if refresher else []) + [
          "--indexer-batch-size", "128", "--init-method-std", str(INIT_STD), "--hidden-dropout", "0.0", "--attention-dropout", "0.0", "--clip-grad", "1.0"]
     if update_retriever:
         a.append("--update-retriever")
@@ -271,14 +271,15 @@ def prepare(tmp, n_docs=2000, topk=8, seed=0, retriever_steps=3, reader_steps=40
     return dict(vocab=vocab, ev=ev, dpr=dpr, t5=t5, emb=emb, recall_before=before, n_docs=n_docs, topk=topk)
 
 
-def train(tmp, world, steps=300, update_retriever=True, batch=16, lr=2e-4, extra=()):
-    """`emdr2_amd.tasks.run` for `steps` steps from the prepared world -> dict(recall_before, recall_after, em, questions, steps)."""
+def train(tmp, world, steps=300, update_retriever=True, batch=16, lr=2e-4, extra=(), refresher=True):
+    """`emdr2_amd.tasks.run` for `steps` steps from the prepared world -> dict(recall_before, recall_after, em, questions, steps).
+    `refresher=False`: without --async-indexer, the index keeps the initial embeddings unless `extra` brings a writer of its own."""
     from emdr2_amd.tasks import run as task_run
     vocab, ev, dpr, t5, emb, before, n_docs, topk = (world[k] for k in ("vocab", "ev", "dpr", "t5", "emb", "recall_before", "n_docs", "topk"))
     iters_per_epoch = n_docs // batch
     epochs = max(1, (steps + iters_per_epoch - 1) // iters_per_epoch)
     a = argv(tmp, vocab, ev, emb, dpr, t5, epochs, batch=batch, topk=topk, lr=lr, update_retriever=update_retriever,
-             extra=["--exit-interval", str(steps)] + list(extra))
+             extra=["--exit-interval", str(steps)] + list(extra), refresher=refresher)
     model, results = task_run.main(a)
     stats, total = results["validation"]
     after, _ = index_and_recall(tmp, vocab, ev, model.retriever_model, "emb_final_%d" % int(update_retriever))
@@ -326,7 +327,17 @@ if __name__ == "__main__":
     ap.add_argument("--reader-steps", type=int, default=400)
     ap.add_argument("--no-update-retriever", action="store_true")
     ap.add_argument("--both", action="store_true", help="the run AND its control from the same prepared world")
+    ap.add_argument("--writeback-arms", metavar="JSONL", default=None,
+                    help="instead: two runs WITHOUT the refresher from the same prepared world, the second with --index-writeback; one JSON "
+                         "line per arm (recall@1/5/20 before and after, EM) is also appended to this file")
     o = ap.parse_args()
     w = prepare(o.dir, o.docs, o.topk, 0, o.retriever_steps, o.reader_steps)
+    if o.writeback_arms:
+        for arm, extra in (("no refresher", []), ("no refresher, --index-writeback", ["--index-writeback", "--disable-retriever-dropout"])):
+            res = dict(train(o.dir, w, o.steps, True, o.batch, o.lr, extra=extra, refresher=False), arm=arm)
+            print(json.dumps(res), flush=True)
+            with open(o.writeback_arms, "a") as fh:
+                fh.write(json.dumps(res) + "\n")
+        sys.exit(0)
     for upd in ((True, False) if o.both else (not o.no_update_retriever,)):
         print(json.dumps(train(o.dir, w, o.steps, upd, o.batch, o.lr)), flush=True)
