@@ -11,7 +11,8 @@
 // Row max / row sum need one exchange between the two half-waves (lanes q and q+32 share a query).
 // Masks come from token ids (pad id 0) + optional history mask; masked scores are REPLACED by -10000 like the reference.
 // Optional dropout on the probabilities (after normalisation), counter-based: keep(seed, ((b*np+n)*sq+q)*sk+key).
-// Inputs: q [b, sq, np, 64], k, v [b, sk, np, 64] strided views (last dim contiguous).
+// Inputs: q [b, sq, np, 64], k, v [b, sk, np, 64] strided views (last dim contiguous), or packed rows (attention_common.h: AttnOperands, with
+// the sequence extents, the split-key ranges and the K / V block staging this kernel shares with attention_bwd.hip's dq kernel).
 // Outputs: o [b, sq, np, 64] contiguous, m / l (row max, row sum of exp; fp32 [b, np, sq]) for the backward.
 #include "../../include/emdr2_ops.h"
 #include <hip/hip_runtime.h>
@@ -24,28 +25,10 @@
 
 namespace {
 
-struct AttnParams {
-    const char *q, *k, *v;
+struct AttnParams : AttnOperands {
     char *o;
-    const long long *ids_q, *ids_k;
     float *m, *l;
-    long long q_sb, q_ss, q_sn;   // element strides of q: batch, sequence, head
-    long long k_sb, k_ss, k_sn, v_sb, v_ss, v_sn;
-    int heads, sq, sk, causal, batch;
-    float scale, drop_p;
-    uint32_t seed;
-    // packed ("varlen") operands: sequence b owns rows [cu[b], cu[b+1]) of a [rows, heads, 64] tensor (no batch stride, no padding rows);
-    // NULL = the dense [batch, s] layout.  With cu_q the row statistics are laid out [heads, tq]; sq / sk are then the LONGEST sequence.
-    const int *cu_q, *cu_k;
-    long long tq;
-    // split keys (few queries, very many keys: the FiD decoder's 32 positions over the ~20,000 packed keys of a question's K passages, where
-    // one workgroup per (question, head) walking all key blocks leaves most of the chip idle): the key blocks of a (batch, head, query block)
-    // are dealt to `ksplit` workgroups, each leaves its UNNORMALISED partial (O fp32, m in log2 units, l) in the workspace and
-    // attention_combine_kernel folds them.  ksplit == 1: none of this.
-    int ksplit;
-    unsigned base_grid;           // workgroups of one split (attn_grid)
-    float *part_o, *part_m, *part_l;   // [ksplit][stat_n][64], [ksplit][stat_n] x 2
-    long long stat_n;
+    float *part_o, *part_m, *part_l;   // split keys: UNNORMALISED partials (O fp32, m in log2 units, l), [ksplit][stat_n][64], [ksplit][stat_n] x 2
 };
 
 // exchange between lane i and lane i + 32 (the two halves of a wave hold the two key subsets of one query): v_permlane32_swap with the value
@@ -61,11 +44,10 @@ __device__ __forceinline__ float half_sum(float x)
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-#define KB 64   // keys per block
-#define KSPLIT_BLOCKS 32   // key blocks (2,048 keys) per workgroup of a split-key launch: a sequence's ranges depend on ITS key count only
 #define QW 32   // queries per wave
 #define NW 4    // waves per workgroup
 #define QB (NW * QW)  // queries per workgroup
+static_assert(QB == QBLOCK, "attention_common.h sizes the launch grids by QBLOCK");
 
 // DROP / CAUSAL are compile-time: the instances without them carry neither the hash nor the history-mask arithmetic.  The kernel is VALU-bound
 // (rocprofv3: ~35 VALU instructions per MFMA, VALU busy 4.6x the matrix pipe), so what matters is keeping the VALU issuing: a 64-key block is
@@ -88,13 +70,9 @@ __global__ void __launch_bounds__(NW * 64, (DROP && CAUSAL) ? 3 : 4) attention_f
     int qblk, b, n;
     const int split = p.ksplit > 1 ? (int)(blockIdx.x / p.base_grid) : 0;
     if (!attn_decode(p.ksplit > 1 ? (int)(blockIdx.x - split * p.base_grid) : (int)blockIdx.x, (p.sq + QB - 1) / QB, p.batch * p.heads, p.heads, qblk, b, n)) return;
-    // this sequence's extent: dense = [b * s, b * s + s) with a batch stride; packed = rows [cu[b], cu[b+1])
-    int sq = p.sq, sk = p.sk;
-    long long qrow0 = (long long)b * p.sq, krow0 = (long long)b * p.sk;            // first row of the sequence in ids / o / (k)
-    long long q_off = (long long)b * p.q_sb, k_off = (long long)b * p.k_sb, v_off = (long long)b * p.v_sb;
-    long long stat0 = ((long long)b * p.heads + n) * p.sq;
-    if (p.cu_q) { const int c0 = p.cu_q[b]; sq = p.cu_q[b + 1] - c0; qrow0 = c0; q_off = (long long)c0 * p.q_ss; stat0 = (long long)n * p.tq + c0; }
-    if (p.cu_k) { const int c0 = p.cu_k[b]; sk = p.cu_k[b + 1] - c0; krow0 = c0; k_off = (long long)c0 * p.k_ss; v_off = (long long)c0 * p.v_ss; }
+    const SeqExtent ex = seq_extent(p, b, n);
+    const int sq = ex.sq, sk = ex.sk;
+    const long long qrow0 = ex.qrow0, stat0 = ex.stat0;
     if (qblk * QB >= sq) return;                                                  // (packed: a block past the end of a short sequence)
     if (sk < 1) {
         // a key sequence without keys: the unsplit launch leaves o / m / l untouched.  A split launch's combine kernel reads EVERY split's
@@ -116,31 +94,19 @@ __global__ void __launch_bounds__(NW * 64, (DROP && CAUSAL) ? 3 : 4) attention_f
     const int qc = qvalid ? qi : sq - 1;
     const bool wave_live = q0 < sq;                 // a wave past the end of its sequence only helps to stage K / V (decoder: sq = 32 of 128)
 
-    // LDS-DMA: per block 16 pieces of 1 KiB (8 for K, 8 for V); wave w moves pieces w, w + NW, .. of each: 8 rows x 128 B,
-    // lane -> (row = 8 piece + lane>>3, LDS granule = lane&7), source granule = granule ^ tile_swz(row) (tile_swz looks at row bits 1..3: period 16, and a wave's pieces are 32 rows apart)
+    // LDS-DMA of the K / V blocks (attention_common.h: stage_kv_block): this lane's piece row and source granule
     const int prow = wave * 8 + (lane >> 3), pslot = (lane & 7) ^ tile_swz(wave * 8 + (lane >> 3));
-    const char *k_src = p.k + (k_off + (long long)n * p.k_sn) * 2 + pslot * 16;        // + key * k_ss * 2
-    const char *v_src = p.v + (v_off + (long long)n * p.v_sn) * 2 + pslot * 16;
-    const int nblk_all = (sk + KB - 1) / KB;
-    // this workgroup's key blocks [blk_lo, nblk): all of them, or its share of a split launch (possibly none: more splits than blocks)
-    const int blk_lo = p.ksplit > 1 ? min(split * KSPLIT_BLOCKS, nblk_all) : 0;
-    const int nblk = p.ksplit > 1 ? min((split + 1) * KSPLIT_BLOCKS, nblk_all) : nblk_all;
-    auto issue = [&](int blk, int stage) {                                     // dense: sk % 32 == 0 (checked on the host); packed: any sk
-        char *sb = smem + stage * 16384;
-#pragma unroll
-        for (int i = 0; i < 8 / NW; ++i) {
-            long long key = blk * KB + prow + 8 * NW * i;
-            if (key >= sk) key = sk - 1;                                           // keys past sk: re-read the last row, masked below (kmask bit 0)
-            __builtin_amdgcn_global_load_lds((gptr_t *)(k_src + key * p.k_ss * 2), (lptr_t *)(sb + (wave + NW * i) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t *)(v_src + key * p.v_ss * 2), (lptr_t *)(sb + 8192 + (wave + NW * i) * 1024), 16, 0, 0);
-        }
-    };
+    const char *k_src = p.k + (ex.k_off + (long long)n * p.k_sn) * 2 + pslot * 16;        // + key * k_ss * 2
+    const char *v_src = p.v + (ex.v_off + (long long)n * p.v_sn) * 2 + pslot * 16;
+    int blk_lo, nblk;                                                           // this workgroup's key blocks
+    split_block_range(p.ksplit, split, sk, blk_lo, nblk);
+    auto issue = [&](int blk, int stage) { stage_kv_block<NW>(smem + stage * 16384, k_src, v_src, p.k_ss, p.v_ss, blk, sk, wave, prow); };
     // the first K / V block goes out before anything else touches global memory: short (packed) sequences have only 2 - 4 blocks per
     // workgroup, and a prologue that first waits for its Q rows and key ids and only then starts the DMA pays the memory latency twice
     if (blk_lo < nblk) issue(blk_lo, 0);
 
     // Q fragments (B operand of S^T = K Q^T): for k-step t the lane holds d = 16t + 8*half .. +8
-    const char *qrow = p.q + (q_off + (long long)qc * p.q_ss + (long long)n * p.q_sn) * 2;
+    const char *qrow = p.q + (ex.q_off + (long long)qc * p.q_ss + (long long)n * p.q_sn) * 2;
     bf16x8 qf[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) qf[t] = *(const bf16x8 *)(qrow + (16 * t + 8 * hi) * 2);
@@ -149,11 +115,7 @@ __global__ void __launch_bounds__(NW * 64, (DROP && CAUSAL) ? 3 : 4) attention_f
     uint32_t vtr[2][2], kra[4];
     tr_addresses((uint32_t)(uintptr_t)smem + 8192, lane, vtr);
     row_frag_addresses((uint32_t)(uintptr_t)smem, lane, kra);
-    for (int blk = blk_lo + wave; blk < nblk; blk += NW) {
-        const int key = blk * KB + lane;
-        const unsigned long long w = __builtin_amdgcn_ballot_w64(key < sk && p.ids_k[krow0 + (key < sk ? key : sk - 1)] != 0);
-        if (lane == 0) kmask_s[blk] = w;
-    }
+    build_key_masks<NW>(kmask_s, p.ids_k, ex.krow0, sk, blk_lo, nblk, wave, lane);
 
     floatx16 oacc[2];
 #pragma unroll
@@ -305,12 +267,7 @@ __global__ void __launch_bounds__(NW * 64, (DROP && CAUSAL) ? 3 : 4) attention_f
         // partial of this key range: unnormalised O, reference point m (log2 units), sum l -- (-3e38, 0, 0) when the range was empty
         if (qvalid) {
             const long long si = (long long)split * p.stat_n + stat0 + qi;
-            float *orow = p.part_o + si * 64;
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4 *)(orow + j * 32 + 8 * g + 4 * hi) = make_float4(oacc[j][4 * g], oacc[j][4 * g + 1], oacc[j][4 * g + 2], oacc[j][4 * g + 3]);
+            store_row_partial(p.part_o + si * 64, oacc, hi);
             if (hi == 0) { p.part_m[si] = mrun; p.part_l[si] = lrun; }
         }
         return;
@@ -318,16 +275,7 @@ __global__ void __launch_bounds__(NW * 64, (DROP && CAUSAL) ? 3 : 4) attention_f
     // ---- normalise and store O[q, d]: lane q holds d = j*32 + (r&3) + 8(r>>2) + 4*half --------------------------------------
     if (qvalid) {
         const float inv = ik / lrun;                                 // survivors of the attention dropout are scaled here, once
-        uint16_t *orow = (uint16_t *)p.o + ((qrow0 + qi) * p.heads + n) * 64;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = j * 32 + 8 * g + 4 * hi;
-                const uint32_t w0 = pack_bf16(oacc[j][4 * g] * inv, oacc[j][4 * g + 1] * inv);
-                const uint32_t w1 = pack_bf16(oacc[j][4 * g + 2] * inv, oacc[j][4 * g + 3] * inv);
-                *(uint2 *)(orow + d) = make_uint2(w0, w1);
-            }
+        store_row_bf16((uint16_t *)p.o + ((qrow0 + qi) * p.heads + n) * 64, oacc, inv, hi);
         if (hi == 0 && p.m) {
             const long long si = stat0 + qi;
             p.m[si] = mrun * 0.6931471805599453f; p.l[si] = lrun;        // back to natural-log units
@@ -360,51 +308,34 @@ __global__ void __launch_bounds__(256) attention_combine_kernel(AttnParams p, fl
 
 } // namespace
 
-// Whether (and how many ways) a launch splits its keys: ONE query block (<= 128 dense queries) over sequences of 4,096 keys or more, in
-// ranges of KSPLIT_BLOCKS blocks.  A function of the launch's query / key EXTENTS only, never of the batch: the same question gives the same
-// bits whether it runs alone, in a group of 8 or in a batch of 64 (question micro-batching relies on it), and short-key launches -- every
-// shape the bf16-faithful oracle walks step by step -- never split.
-static int attention_ksplit(int max_sq, int max_sk)
-{
-    if (max_sq > QB || max_sk < 4096) return 1;
-    const int nblk = (max_sk + KB - 1) / KB;
-    return (nblk + KSPLIT_BLOCKS - 1) / KSPLIT_BLOCKS;                            // <= 32 (sk <= 65,536)
-}
+struct FwdArgs : AttnArgs { void *o; float *m, *l; };
 
-static int attention_fwd_launch(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
-                                const void *v, int64_t v_sb, int64_t v_ss, int64_t v_sn, void *o, const int64_t *ids_q, const int64_t *ids_k, int batch, int heads, int sq, int sk,
-                                int head_dim, int causal, float scale, float drop_p, uint32_t seed, float *m, float *l, const int32_t *cu_q, const int32_t *cu_k,
-                                int64_t total_q, double pairs, void *stream, int ksplit = 1, void *ws = nullptr, size_t ws_bytes = 0)
+// The forward splits only by its own policy (attention_ksplit: <= 128 dense queries over >= 4,096 keys).
+static int attention_fwd_launch(const FwdArgs &a)
 {
-    if (!q || !k || !v || !o || !ids_q || !ids_k || batch < 1 || heads < 1 || sq < 1) return -1;
-    if (ksplit < 1 || ksplit > 64 || (ksplit > 1 && (cu_q || !ws || ((uintptr_t)ws & 15) || ksplit != attention_ksplit(sq, sk)))) return -1;
-    if (head_dim != 64 || sk < 1 || sk > 65536 || (q_ss & 7) || (k_ss & 7) || (q_sn & 7) || (k_sn & 7) || (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (v_ss & 7) || (v_sn & 7)) return -4;
-    if (!cu_k && (sk < 32 || (sk & 31))) return -4;                                  // dense keys: whole 32-key steps (padded queries average over exactly sk keys)
-    if (cu_q && total_q < 1) return -1;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)o & 7) || drop_p < 0.f || drop_p >= 1.f) return -1;
+    if (!a.required() || !a.o) return -1;
+    if (!a.split_args(a.ksplit == attention_ksplit(a.sq, a.sk))) return -1;
+    if (!a.shape_ok() || !a.strides_ok()) return -4;
+    if (!a.packed_ok() || !a.inputs_ok() || ((uintptr_t)a.o & 7)) return -1;
     AttnParams p;
-    p.q = (const char *)q; p.k = (const char *)k; p.v = (const char *)v; p.o = (char *)o;
-    p.ids_q = (const long long *)ids_q; p.ids_k = (const long long *)ids_k; p.m = m; p.l = l;
-    p.q_sb = q_sb; p.q_ss = q_ss; p.q_sn = q_sn; p.k_sb = k_sb; p.k_ss = k_ss; p.k_sn = k_sn; p.v_sb = v_sb; p.v_ss = v_ss; p.v_sn = v_sn;
-    p.heads = heads; p.sq = sq; p.sk = sk; p.causal = causal; p.scale = scale; p.drop_p = drop_p; p.seed = seed;
-    p.batch = batch; p.cu_q = cu_q; p.cu_k = cu_k; p.tq = total_q;
-    p.ksplit = ksplit; p.base_grid = attn_grid((sq + QB - 1) / QB, batch * heads, heads);
-    p.stat_n = (long long)batch * heads * sq;
+    a.fill(p);
+    p.o = (char *)a.o; p.m = a.m; p.l = a.l;
     p.part_o = p.part_m = p.part_l = nullptr;
+    const int ksplit = a.ksplit;
     if (ksplit > 1) {
-        if (ws_bytes < (size_t)ksplit * p.stat_n * 66 * sizeof(float)) return -2;
-        p.part_o = (float *)ws; p.part_m = p.part_o + (size_t)ksplit * p.stat_n * 64; p.part_l = p.part_m + (size_t)ksplit * p.stat_n;
+        if (a.ws_bytes < (size_t)ksplit * p.stat_n * 66 * sizeof(float)) return -2;
+        p.part_o = (float *)a.ws; p.part_m = p.part_o + (size_t)ksplit * p.stat_n * 64; p.part_l = p.part_m + (size_t)ksplit * p.stat_n;
     }
-    dim3 grid(p.base_grid * (unsigned)ksplit);
-    const size_t lds = 2 * 16384 + (size_t)((sk + KB - 1) / KB) * 8;            // <= 40 KiB (sk <= 65536)
-    OpsTimer timer(OPS_ATTN_FWD, 4.0 * heads * pairs * 64, (hipStream_t)stream);
-    if (drop_p > 0.f && causal) hipLaunchKernelGGL((attention_fwd_kernel<true, true>), grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
-    else if (drop_p > 0.f) hipLaunchKernelGGL((attention_fwd_kernel<true, false>), grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
-    else if (causal) hipLaunchKernelGGL((attention_fwd_kernel<false, true>), grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((attention_fwd_kernel<false, false>), grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
+    const dim3 grid(p.base_grid * (unsigned)ksplit);
+    const size_t lds = 2 * 16384 + (size_t)((a.sk + KB - 1) / KB) * 8;          // <= 40 KiB (sk <= 65536)
+    const hipStream_t stream = (hipStream_t)a.stream;
+    OpsTimer timer(OPS_ATTN_FWD, 4.0 * a.heads * a.pairs * 64, stream);
+    attn_instance(a.drop_p > 0.f, a.causal, [&](auto drop, auto causal) {
+        hipLaunchKernelGGL((attention_fwd_kernel<decltype(drop)::value, decltype(causal)::value>), grid, dim3(NW * 64), lds, stream, p);
+    });
     if (ksplit > 1)
-        hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)((p.stat_n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p,
-                           drop_p > 0.f ? emdr2_keep_scale(drop_p) : 1.f);
+        hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)((p.stat_n + 3) / 4)), dim3(256), 0, stream, p,
+                           a.drop_p > 0.f ? emdr2_keep_scale(a.drop_p) : 1.f);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -412,8 +343,9 @@ extern "C" int emdr2_attention_fwd(const void *q, int64_t q_sb, int64_t q_ss, in
                                    const void *v, int64_t v_sb, int64_t v_ss, int64_t v_sn, void *o, const int64_t *ids_q, const int64_t *ids_k, int batch, int heads, int sq, int sk,
                                    int head_dim, int causal, float scale, float drop_p, uint32_t seed, float *m, float *l, void *stream)
 {
-    return attention_fwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, ids_q, ids_k, batch, heads, sq, sk, head_dim, causal, scale, drop_p,
-                                seed, m, l, nullptr, nullptr, 0, (double)batch * sq * sk, stream);
+    FwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, sq, sk, head_dim, causal, scale, drop_p, seed, stream}, o, m, l};
+    a.pairs = (double)batch * sq * sk;
+    return attention_fwd_launch(a);
 }
 
 // Split-key plan of a launch with DENSE queries [batch, max_sq] over up to max_sk keys per sequence: number of splits (1 = do not split) and
@@ -435,8 +367,9 @@ extern "C" int emdr2_attention_fwd_splitkv(const void *q, int64_t q_sb, int64_t 
                                                   int head_dim, int causal, float scale, float drop_p, uint32_t seed, float *m, float *l, int ksplit, void *ws,
                                                   size_t ws_bytes, void *stream)
 {
-    return attention_fwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, ids_q, ids_k, batch, heads, sq, max_sk, head_dim, causal, scale,
-                                drop_p, seed, m, l, nullptr, cu_k, 0, (double)pairs, stream, ksplit, ws, ws_bytes);
+    FwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, sq, max_sk, head_dim, causal, scale, drop_p, seed, stream}, o, m, l};
+    a.cu_k = cu_k; a.pairs = (double)pairs; a.ksplit = ksplit; a.ws = ws; a.ws_bytes = ws_bytes;
+    return attention_fwd_launch(a);
 }
 
 extern "C" int emdr2_attention_varlen_fwd(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
@@ -445,6 +378,7 @@ extern "C" int emdr2_attention_varlen_fwd(const void *q, int64_t q_sb, int64_t q
                                           int head_dim, int causal, float scale, float drop_p, uint32_t seed, float *m, float *l, void *stream)
 {
     if (!cu_q && !cu_k) return -1;
-    return attention_fwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, ids_q, ids_k, batch, heads, max_sq, max_sk, head_dim, causal, scale,
-                                drop_p, seed, m, l, cu_q, cu_k, total_q, (double)pairs, stream);
+    FwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, max_sq, max_sk, head_dim, causal, scale, drop_p, seed, stream}, o, m, l};
+    a.cu_q = cu_q; a.cu_k = cu_k; a.total_q = total_q; a.pairs = (double)pairs;
+    return attention_fwd_launch(a);
 }

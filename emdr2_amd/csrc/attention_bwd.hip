@@ -12,9 +12,9 @@
 //       S = Q K^T, dP = dO V^T              MFMA A = Q / dO rows, B = K / V fragments held in registers
 //       dV^T += dO^T P_dropped, dK^T += Q^T dS     A = dO^T / Q^T by transpose reads of the same tiles
 //
-// Tiles are [64 rows][64 d] bf16 (128-B rows of eight 16-B granules), granule index XOR f(row) with
-// f(row) = (((row >> 1) & 1) << 2) | ((row >> 2) & 3): conflict-free for the row reads (16 consecutive rows, one granule) and for the
-// transpose reads (4 rows x 4 granules per 32-lane service group).  Masks from token ids (pad id 0) + optional history mask; masked
+// attention_common.h holds what this file shares with attention.hip: the swizzled tile layout and fragment reads, the launch's operands
+// (AttnOperands, AttnArgs and their checks), seq_extent(), the split-key ranges and the K / V block staging of the dq kernel (the dk / dv
+// kernel stages its own 32 rows with 32-bit lane offsets).  Masks from token ids (pad id 0) + optional history mask; masked
 // positions get dS = 0 (masked_fill cuts the dependence on the score) while their (normally zero) probability still feeds dV, like
 // the reference.  Dropout bits are regenerated from (seed, row, key) -- csrc/rng.h -- never stored.
 #include "../../include/emdr2_ops.h"
@@ -28,61 +28,25 @@
 
 namespace {
 
-struct BwdParams {
-    const char *q, *k, *v, *o, *dout;
+struct BwdParams : AttnOperands {
+    const char *o, *dout;
     char *dq, *dk, *dv;
-    const long long *ids_q, *ids_k;
     const float *m, *l;
     float *dstat;                  // per-query statistics the dq kernel leaves for the dk/dv kernel, [4][stat_n] (stat index as m / l):
                                    //   exp2 offset pm = m log2(e) + log2(l) | D (1 - p), D = rowsum(dO o O) | dropout row hash (bits) | 1 = real token (bits)
-    long long stat_n;              // batch * heads * sq (dense) or heads * total_q (packed)
-    long long q_sb, q_ss, q_sn;    // element strides of q (batch, sequence, head); k and v share k_*
-    long long k_sb, k_ss, k_sn, v_sb, v_ss, v_sn;
     long long dq_sb, dq_ss, dkv_sb, dkv_ss;   // element strides (batch, sequence) of the gradient outputs; heads are 64 apart
-    int heads, sq, sk, causal, batch;
-    float scale, drop_p;
-    uint32_t seed;
     float keep_scale, inv_keep_scale, scale2;      // 1 / (1 - p) of the surviving probabilities (and its inverse); scale * log2(e): host-computed -> SGPRs
     uint32_t drop_thr;
-    // packed operands (attention.hip: AttnParams): sequence b owns rows [cu[b], cu[b+1]); statistics [heads, tq] when cu_q is given
-    const int *cu_q, *cu_k;
-    long long tq;
-    // split keys (attention.hip: AttnParams): the dq kernel's key blocks dealt to `ksplit` workgroups, fp32 partial dQ [ksplit][stat_n][64]
-    // folded by attention_dq_combine_kernel; the dk / dv kernel is parallel over keys already
-    int ksplit;
-    unsigned base_grid;
+    // split keys: the dq kernel's key blocks dealt to `ksplit` workgroups, fp32 partial dQ [ksplit][stat_n][64] folded by
+    // attention_dq_combine_kernel; the dk / dv kernel is parallel over keys already
     float *part_dq;
 };
-
-// the sequence's extent and operand offsets, dense or packed (see attention.hip)
-struct SeqExtent {
-    int sq, sk;
-    long long qrow0, krow0, q_off, k_off, v_off, dq_off, dkv_off, stat0;
-};
-__device__ __forceinline__ SeqExtent seq_extent(const BwdParams &p, int b, int n)
-{
-    SeqExtent e;
-    e.sq = p.sq; e.sk = p.sk;
-    e.qrow0 = (long long)b * p.sq; e.krow0 = (long long)b * p.sk;
-    e.q_off = (long long)b * p.q_sb; e.k_off = (long long)b * p.k_sb; e.v_off = (long long)b * p.v_sb;
-    e.dq_off = (long long)b * p.dq_sb; e.dkv_off = (long long)b * p.dkv_sb;
-    e.stat0 = ((long long)b * p.heads + n) * p.sq;
-    if (p.cu_q) {
-        const int c0 = p.cu_q[b];
-        e.sq = p.cu_q[b + 1] - c0; e.qrow0 = c0; e.q_off = (long long)c0 * p.q_ss; e.dq_off = (long long)c0 * p.dq_ss; e.stat0 = (long long)n * p.tq + c0;
-    }
-    if (p.cu_k) {
-        const int c0 = p.cu_k[b];
-        e.sk = p.cu_k[b + 1] - c0; e.krow0 = c0; e.k_off = (long long)c0 * p.k_ss; e.v_off = (long long)c0 * p.v_ss; e.dkv_off = (long long)c0 * p.dkv_ss;
-    }
-    return e;
-}
 
 // ============================================================ dq =====================================================================
 // Like the forward (attention.hip): VALU-bound, so workgroups are FOUR waves (128 queries) at <= 168 VGPRs -- three per CU, each on its own
 // barrier -- and a staged 64-key block is consumed as two 32-key steps (one S / dP accumulator pair live); DROP / CAUSAL are compile-time.
-#define KSPLIT_BLOCKS 32       // key blocks per workgroup of a split-key launch (attention.hip)
 #define BNW 4
+static_assert(BNW * 32 == QBLOCK, "attention_common.h sizes the launch grids by QBLOCK");
 #define KNW 4                  // waves (32 keys each) per workgroup of the dK / dV kernel
 template <bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(BNW * 64, 3) attention_bwd_dq_kernel(BwdParams p)
@@ -119,19 +83,9 @@ __global__ void __launch_bounds__(BNW * 64, 3) attention_bwd_dq_kernel(BwdParams
     const int prow = wave * 8 + (lane >> 3), pslot = (lane & 7) ^ tile_swz(wave * 8 + (lane >> 3));
     const char *k_src = p.k + (ex.k_off + (long long)n * p.k_sn) * 2 + pslot * 16;
     const char *v_src = p.v + (ex.v_off + (long long)n * p.v_sn) * 2 + pslot * 16;
-    const int nblk_all = (sk + 63) / 64;
-    const int blk_lo = p.ksplit > 1 ? min(split * KSPLIT_BLOCKS, nblk_all) : 0;                      // this workgroup's key blocks [blk_lo, nblk)
-    const int nblk = p.ksplit > 1 ? min((split + 1) * KSPLIT_BLOCKS, nblk_all) : nblk_all;
-    auto issue = [&](int blk, int stage) {
-        char *sb = smem + stage * 16384;
-#pragma unroll
-        for (int i = 0; i < 8 / BNW; ++i) {
-            long long key = blk * 64 + prow + 8 * BNW * i;
-            if (key >= sk) key = sk - 1;                                           // keys past sk: re-read the last row, masked below
-            __builtin_amdgcn_global_load_lds((gptr_t *)(k_src + key * p.k_ss * 2), (lptr_t *)(sb + (wave + BNW * i) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t *)(v_src + key * p.v_ss * 2), (lptr_t *)(sb + 8192 + (wave + BNW * i) * 1024), 16, 0, 0);
-        }
-    };
+    int blk_lo, nblk;                                                           // this workgroup's key blocks
+    split_block_range(p.ksplit, split, sk, blk_lo, nblk);
+    auto issue = [&](int blk, int stage) { stage_kv_block<BNW>(smem + stage * 16384, k_src, v_src, p.k_ss, p.v_ss, blk, sk, wave, prow); };
     if (blk_lo < nblk) issue(blk_lo, 0);    // before the fragment / statistics loads below: a short sequence must not pay the memory latency twice
     if (blk_lo + 1 < nblk) issue(blk_lo + 1, 1);
 
@@ -161,11 +115,7 @@ __global__ void __launch_bounds__(BNW * 64, 3) attention_bwd_dq_kernel(BwdParams
     const float sc = p.scale2;
     const float pm = p.m[si] * L2E + __log2f(p.l[si]);                  // P = exp2(s2 - pm)
 
-    for (int blk = blk_lo + wave; blk < nblk; blk += BNW) {
-        const int key = blk * 64 + lane;
-        const unsigned long long w = __builtin_amdgcn_ballot_w64(key < sk && p.ids_k[ex.krow0 + (key < sk ? key : sk - 1)] != 0);
-        if (lane == 0) kmask_s[blk] = w;
-    }
+    build_key_masks<BNW>(kmask_s, p.ids_k, ex.krow0, sk, blk_lo, nblk, wave, lane);
     uint32_t ktr[2][2], kra[4];
     tr_addresses((uint32_t)(uintptr_t)smem, lane, ktr);
     row_frag_addresses((uint32_t)(uintptr_t)smem, lane, kra);
@@ -266,28 +216,11 @@ __global__ void __launch_bounds__(BNW * 64, 3) attention_bwd_dq_kernel(BwdParams
         }
     }
     if (p.ksplit > 1) {                                                           // partial dQ of this key range (unscaled, fp32)
-        if (qvalid) {
-            float *prow = p.part_dq + ((long long)split * p.stat_n + si) * 64;
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4 *)(prow + j * 32 + 8 * g + 4 * hi) = make_float4(dqacc[j][4 * g], dqacc[j][4 * g + 1], dqacc[j][4 * g + 2], dqacc[j][4 * g + 3]);
-        }
+        if (qvalid) store_row_partial(p.part_dq + ((long long)split * p.stat_n + si) * 64, dqacc, hi);
         return;
     }
-    if (qvalid) {
-        const float qsc = p.scale * ik;
-        uint16_t *drow = (uint16_t *)p.dq + ex.dq_off + (long long)qi * p.dq_ss + n * 64;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = j * 32 + 8 * g + 4 * hi;
-                *(uint2 *)(drow + d) = make_uint2(pack_bf16(dqacc[j][4 * g] * qsc, dqacc[j][4 * g + 1] * qsc),
-                                                  pack_bf16(dqacc[j][4 * g + 2] * qsc, dqacc[j][4 * g + 3] * qsc));
-            }
-    }
+    if (qvalid)       // (packed: the sequence's first row; dense: its batch stride)
+        store_row_bf16((uint16_t *)p.dq + (p.cu_q ? ex.qrow0 * p.dq_ss : (long long)b * p.dq_sb) + (long long)qi * p.dq_ss + n * 64, dqacc, p.scale * ik, hi);
 }
 
 // dQ = (sum of the splits' partials) x scale / (1 - p): dense-q launches only; one wave per query row, lane = d, partials in split order
@@ -522,67 +455,52 @@ __global__ void __launch_bounds__(KNW * 64, 3) attention_bwd_dkv_kernel(BwdParam
 #undef st_rh
     if (kvalid) {
         const float ksc = p.scale * ik;                                // the step loop accumulated dS and the dropped P in units of 1 / keep_scale
-        uint16_t *krow = (uint16_t *)p.dk + ex.dkv_off + (long long)key * p.dkv_ss + n * 64;
-        uint16_t *vrow = (uint16_t *)p.dv + ex.dkv_off + (long long)key * p.dkv_ss + n * 64;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = j * 32 + 8 * g + 4 * hi;
-                *(uint2 *)(krow + d) = make_uint2(pack_bf16(dkacc[j][4 * g] * ksc, dkacc[j][4 * g + 1] * ksc),
-                                                  pack_bf16(dkacc[j][4 * g + 2] * ksc, dkacc[j][4 * g + 3] * ksc));
-                *(uint2 *)(vrow + d) = make_uint2(pack_bf16(dvacc[j][4 * g] * ik, dvacc[j][4 * g + 1] * ik), pack_bf16(dvacc[j][4 * g + 2] * ik, dvacc[j][4 * g + 3] * ik));
-            }
+        const long long dkv_off = (p.cu_k ? ex.krow0 * p.dkv_ss : (long long)b * p.dkv_sb) + (long long)key * p.dkv_ss + n * 64;
+        store_row_bf16((uint16_t *)p.dk + dkv_off, dkacc, ksc, hi);
+        store_row_bf16((uint16_t *)p.dv + dkv_off, dvacc, ik, hi);
     }
 }
 
 } // namespace
 
-static int attention_bwd_launch(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
-                                const void *v, int64_t v_sb, int64_t v_ss, int64_t v_sn, const void *o, const void *dout, void *dq, int64_t dq_sb,
-                                int64_t dq_ss, void *dk, void *dv, int64_t dkv_sb, int64_t dkv_ss, const int64_t *ids_q, const int64_t *ids_k, const float *m, const float *l, float *dstat, int batch,
-                                int heads, int sq, int sk, int head_dim, int causal, float scale, float drop_p, uint32_t seed, const int32_t *cu_q, const int32_t *cu_k,
-                                int64_t total_q, double pairs, void *stream, int ksplit = 1, void *ws = nullptr, size_t ws_bytes = 0)
+struct BwdArgs : AttnArgs {
+    const void *o, *dout; void *dq, *dk, *dv; int64_t dq_sb, dq_ss, dkv_sb, dkv_ss;
+    const float *m, *l; float *dstat;
+};
+
+// The backward splits whatever the forward's plan said for <= 128 dense queries: one partial per key range, without the forward's 4,096-key
+// floor.  Strides are checked after the packed row count, as they always were here (the forward checks them with the shape).
+static int attention_bwd_launch(const BwdArgs &a)
 {
-    if (!q || !k || !v || !o || !dout || !dq || !dk || !dv || !ids_q || !ids_k || !m || !l || !dstat || batch < 1 || heads < 1 || sq < 1) return -1;
-    if (ksplit < 1 || ksplit > 64 || (ksplit > 1 && (cu_q || !ws || ((uintptr_t)ws & 15) || sq > BNW * 32 || ksplit != ((sk + 63) / 64 + KSPLIT_BLOCKS - 1) / KSPLIT_BLOCKS))) return -1;
-    if (head_dim != 64 || sk < 1 || sk > 65536) return -4;
-    if (!cu_k && (sk < 32 || (sk & 31))) return -4;
-    if (cu_q && total_q < 1) return -1;
-    const int64_t strides[13] = {q_sb, q_ss, q_sn, k_sb, k_ss, k_sn, v_sb, v_ss, v_sn, dq_sb, dq_ss, dkv_sb, dkv_ss};
-    for (int i = 0; i < 13; ++i)
-        if (strides[i] & 7) return -4;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)o & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dq & 7) ||
-        ((uintptr_t)dk & 7) || ((uintptr_t)dv & 7) || drop_p < 0.f || drop_p >= 1.f)
-        return -1;
+    if (!a.required() || !a.o || !a.dout || !a.dq || !a.dk || !a.dv || !a.m || !a.l || !a.dstat) return -1;
+    if (!a.split_args(a.sq <= QBLOCK && a.ksplit == attn_key_ranges(a.sk))) return -1;
+    if (!a.shape_ok()) return -4;
+    if (!a.packed_ok()) return -1;
+    if (!a.strides_ok() || ((a.dq_sb | a.dq_ss | a.dkv_sb | a.dkv_ss) & 7)) return -4;
+    if (!a.inputs_ok() || (((uintptr_t)a.o | (uintptr_t)a.dout) & 15) || (((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 7)) return -1;
     BwdParams p;
-    p.q = (const char *)q; p.k = (const char *)k; p.v = (const char *)v; p.o = (const char *)o; p.dout = (const char *)dout;
-    p.dq = (char *)dq; p.dk = (char *)dk; p.dv = (char *)dv;
-    p.ids_q = (const long long *)ids_q; p.ids_k = (const long long *)ids_k; p.m = m; p.l = l; p.dstat = dstat;
-    p.q_sb = q_sb; p.q_ss = q_ss; p.q_sn = q_sn; p.k_sb = k_sb; p.k_ss = k_ss; p.k_sn = k_sn; p.v_sb = v_sb; p.v_ss = v_ss; p.v_sn = v_sn;
-    p.dq_sb = dq_sb; p.dq_ss = dq_ss; p.dkv_sb = dkv_sb; p.dkv_ss = dkv_ss;
-    p.heads = heads; p.sq = sq; p.sk = sk; p.causal = causal; p.scale = scale; p.drop_p = drop_p; p.seed = seed;
-    p.batch = batch; p.cu_q = cu_q; p.cu_k = cu_k; p.tq = total_q;
-    p.stat_n = cu_q ? (long long)heads * total_q : (long long)batch * heads * sq;
-    if (p.stat_n * 16 >= (1ll << 32) || q_ss >= (1 << 22) || heads >= (1 << 16)) return -4;     // 32-bit lane offsets of the dk/dv kernel's staging
-    p.keep_scale = emdr2_keep_scale(drop_p); p.inv_keep_scale = 1.f / p.keep_scale; p.scale2 = scale * L2E; p.drop_thr = emdr2_drop_thr(drop_p);
-    p.ksplit = ksplit; p.base_grid = attn_grid((sq + BNW * 32 - 1) / (BNW * 32), batch * heads, heads); p.part_dq = (float *)ws;
-    if (ksplit > 1 && ws_bytes < (size_t)ksplit * p.stat_n * 64 * sizeof(float)) return -2;
-    OpsTimer timer(OPS_ATTN_BWD, 10.0 * heads * pairs * 64, (hipStream_t)stream);
-    const dim3 dq_grid(p.base_grid * (unsigned)ksplit);
-    const size_t dq_lds = 3 * 16384 + (size_t)((sk + 63) / 64) * 8;
-    if (drop_p > 0.f && causal) hipLaunchKernelGGL((attention_bwd_dq_kernel<true, true>), dq_grid, dim3(BNW * 64), dq_lds, (hipStream_t)stream, p);
-    else if (drop_p > 0.f) hipLaunchKernelGGL((attention_bwd_dq_kernel<true, false>), dq_grid, dim3(BNW * 64), dq_lds, (hipStream_t)stream, p);
-    else if (causal) hipLaunchKernelGGL((attention_bwd_dq_kernel<false, true>), dq_grid, dim3(BNW * 64), dq_lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((attention_bwd_dq_kernel<false, false>), dq_grid, dim3(BNW * 64), dq_lds, (hipStream_t)stream, p);
-    if (ksplit > 1)
-        hipLaunchKernelGGL(attention_dq_combine_kernel, dim3((unsigned)((p.stat_n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p,
-                           scale * (drop_p > 0.f ? p.keep_scale : 1.f));
-    const dim3 kv_grid(attn_grid((sk + KNW * 32 - 1) / (KNW * 32), batch * heads, heads));
-    if (drop_p > 0.f && causal) hipLaunchKernelGGL((attention_bwd_dkv_kernel<true, true>), kv_grid, dim3(KNW * 64), 0, (hipStream_t)stream, p);
-    else if (drop_p > 0.f) hipLaunchKernelGGL((attention_bwd_dkv_kernel<true, false>), kv_grid, dim3(KNW * 64), 0, (hipStream_t)stream, p);
-    else if (causal) hipLaunchKernelGGL((attention_bwd_dkv_kernel<false, true>), kv_grid, dim3(KNW * 64), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((attention_bwd_dkv_kernel<false, false>), kv_grid, dim3(KNW * 64), 0, (hipStream_t)stream, p);
+    a.fill(p);
+    p.o = (const char *)a.o; p.dout = (const char *)a.dout; p.dq = (char *)a.dq; p.dk = (char *)a.dk; p.dv = (char *)a.dv;
+    p.m = a.m; p.l = a.l; p.dstat = a.dstat;
+    p.dq_sb = a.dq_sb; p.dq_ss = a.dq_ss; p.dkv_sb = a.dkv_sb; p.dkv_ss = a.dkv_ss;
+    if (p.stat_n * 16 >= (1ll << 32) || a.q_ss >= (1 << 22) || a.heads >= (1 << 16)) return -4;     // 32-bit lane offsets of the dk/dv kernel's staging
+    p.keep_scale = emdr2_keep_scale(a.drop_p); p.inv_keep_scale = 1.f / p.keep_scale; p.scale2 = a.scale * L2E; p.drop_thr = emdr2_drop_thr(a.drop_p);
+    p.part_dq = (float *)a.ws;
+    if (a.ksplit > 1 && a.ws_bytes < (size_t)a.ksplit * p.stat_n * 64 * sizeof(float)) return -2;
+    const hipStream_t stream = (hipStream_t)a.stream;
+    OpsTimer timer(OPS_ATTN_BWD, 10.0 * a.heads * a.pairs * 64, stream);
+    const dim3 dq_grid(p.base_grid * (unsigned)a.ksplit);
+    const size_t dq_lds = 3 * 16384 + (size_t)((a.sk + KB - 1) / KB) * 8;
+    attn_instance(a.drop_p > 0.f, a.causal, [&](auto drop, auto causal) {
+        hipLaunchKernelGGL((attention_bwd_dq_kernel<decltype(drop)::value, decltype(causal)::value>), dq_grid, dim3(BNW * 64), dq_lds, stream, p);
+    });
+    if (a.ksplit > 1)
+        hipLaunchKernelGGL(attention_dq_combine_kernel, dim3((unsigned)((p.stat_n + 3) / 4)), dim3(256), 0, stream, p,
+                           a.scale * (a.drop_p > 0.f ? p.keep_scale : 1.f));
+    const dim3 kv_grid(attn_grid((a.sk + KNW * 32 - 1) / (KNW * 32), a.batch * a.heads, a.heads));
+    attn_instance(a.drop_p > 0.f, a.causal, [&](auto drop, auto causal) {
+        hipLaunchKernelGGL((attention_bwd_dkv_kernel<decltype(drop)::value, decltype(causal)::value>), kv_grid, dim3(KNW * 64), 0, stream, p);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -591,8 +509,10 @@ extern "C" int emdr2_attention_bwd(const void *q, int64_t q_sb, int64_t q_ss, in
                                    int64_t dq_ss, void *dk, void *dv, int64_t dkv_sb, int64_t dkv_ss, const int64_t *ids_q, const int64_t *ids_k, const float *m, const float *l, float *dstat, int batch,
                                    int heads, int sq, int sk, int head_dim, int causal, float scale, float drop_p, uint32_t seed, void *stream)
 {
-    return attention_bwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, dout, dq, dq_sb, dq_ss, dk, dv, dkv_sb, dkv_ss, ids_q, ids_k, m, l,
-                                dstat, batch, heads, sq, sk, head_dim, causal, scale, drop_p, seed, nullptr, nullptr, 0, (double)batch * sq * sk, stream);
+    BwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, sq, sk, head_dim, causal, scale, drop_p, seed, stream},
+              o, dout, dq, dk, dv, dq_sb, dq_ss, dkv_sb, dkv_ss, m, l, dstat};
+    a.pairs = (double)batch * sq * sk;
+    return attention_bwd_launch(a);
 }
 
 extern "C" int emdr2_attention_bwd_splitkv(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
@@ -602,8 +522,10 @@ extern "C" int emdr2_attention_bwd_splitkv(const void *q, int64_t q_sb, int64_t 
                                            int batch, int heads, int sq, int max_sk, int head_dim, int causal, float scale, float drop_p, uint32_t seed,
                                            int ksplit, void *ws, size_t ws_bytes, void *stream)
 {
-    return attention_bwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, dout, dq, dq_sb, dq_ss, dk, dv, dkv_sb, dkv_ss, ids_q, ids_k, m, l,
-                                dstat, batch, heads, sq, max_sk, head_dim, causal, scale, drop_p, seed, nullptr, cu_k, 0, (double)pairs, stream, ksplit, ws, ws_bytes);
+    BwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, sq, max_sk, head_dim, causal, scale, drop_p, seed, stream},
+              o, dout, dq, dk, dv, dq_sb, dq_ss, dkv_sb, dkv_ss, m, l, dstat};
+    a.cu_k = cu_k; a.pairs = (double)pairs; a.ksplit = ksplit; a.ws = ws; a.ws_bytes = ws_bytes;
+    return attention_bwd_launch(a);
 }
 
 extern "C" int emdr2_attention_varlen_bwd(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
@@ -613,6 +535,8 @@ extern "C" int emdr2_attention_varlen_bwd(const void *q, int64_t q_sb, int64_t q
                                           int batch, int heads, int max_sq, int max_sk, int head_dim, int causal, float scale, float drop_p, uint32_t seed, void *stream)
 {
     if (!cu_q && !cu_k) return -1;
-    return attention_bwd_launch(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, o, dout, dq, dq_sb, dq_ss, dk, dv, dkv_sb, dkv_ss, ids_q, ids_k, m, l,
-                                dstat, batch, heads, max_sq, max_sk, head_dim, causal, scale, drop_p, seed, cu_q, cu_k, total_q, (double)pairs, stream);
+    BwdArgs a{{q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, v, v_sb, v_ss, v_sn, ids_q, ids_k, batch, heads, max_sq, max_sk, head_dim, causal, scale, drop_p, seed, stream},
+              o, dout, dq, dk, dv, dq_sb, dq_ss, dkv_sb, dkv_ss, m, l, dstat};
+    a.cu_q = cu_q; a.cu_k = cu_k; a.total_q = total_q; a.pairs = (double)pairs;
+    return attention_bwd_launch(a);
 }

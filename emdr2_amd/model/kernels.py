@@ -860,6 +860,8 @@ def _attn_side(x, info):
         raise TypeError("token ids must be contiguous CUDA int64 tensors (the kernels derive the masks from them)")
     if x.dim() != 4:
         raise ValueError("a dense attention operand must be [batch, s, heads, head_dim]")
+    if tuple(info.shape) != tuple(x.shape[:2]):
+        raise ValueError("token ids %s do not match the attention operand's [batch, s] = %s" % (tuple(info.shape), tuple(x.shape[:2])))
     return info, None, x.stride(0), x.stride(1), x.stride(2), x.shape[0], x.shape[1]
 
 
@@ -894,6 +896,130 @@ def _splitkv_plan(batch, heads, sq, sk):
     return plan
 
 
+def _qkv_views(src, kvsrc):
+    """(q, k, v) or (dq, dk, dv): strided slices of the packed projection outputs (or of their gradients)."""
+    if kvsrc is None:
+        return src.select(-3, 0), src.select(-3, 1), src.select(-3, 2)
+    return src, kvsrc.select(-3, 0), kvsrc.select(-3, 1)
+
+
+class _AttnLaunch(object):
+    """What one attention call launches, decided once: built in AttentionCoreFn.forward, kept on ctx, read by the backward.  The per-side
+    tuples of _attn_side, the extents, the route (fused kernels or the composed GEMM + softmax path), the split-key plan AS IT WAS AT THE
+    FORWARD with both workspace sizes, the op timer's pair count.  It keeps the token ids / PackedSeqs but no q / k / v: those are views of
+    what autograd saves (and releases after the backward), taken again where they are needed."""
+
+    def __init__(self, qsrc, kvsrc, ids_q, ids_k, causal):
+        q, k, v = _qkv_views(qsrc, kvsrc)
+        self.ids_q, self.ids_k = ids_q, ids_k
+        self.pq, self.pk = pq, pk = isinstance(ids_q, PackedSeqs), isinstance(ids_k, PackedSeqs)
+        self.side_q, self.side_k, self.side_v = _attn_side(q, ids_q), _attn_side(k, ids_k), _attn_side(v, ids_k)
+        (b, sq), (bk, sk) = self.side_q[5:], self.side_k[5:]
+        if b != bk:
+            raise ValueError("query and key batches differ")
+        heads, hn = q.shape[-2:]
+        self.b, self.sq, self.sk, self.heads, self.hn = b, sq, sk, heads, hn
+        self.causal, self.scale = int(causal), 1.0 / math.sqrt(hn)
+        # THE rule: head dim 64 runs the fused kernels (attention.hip, attention_bwd.hip; <= 65,536 keys, dense keys in whole 32-key steps)
+        self.fused = hn == 64 and sk <= 65536 and (pk or sk % 32 == 0)
+        if (pq or pk) and not self.fused:
+            raise ValueError("packed attention operands need head dim 64 (the fused kernels)")
+        # few dense queries over very many keys (the FiD decoder's cross-attention, cached decoding steps): keys dealt to several workgroups
+        self.ksplit, self.ws_fwd, self.ws_bwd = _splitkv_plan(b, heads, sq, sk) if (self.fused and not pq) else (1, 0, 0)
+        self.pairs = int(((ids_q.pairs if ids_k is ids_q else 0) if pq else (sq * ids_k.total if pk else b * sq * sk)) or 0)
+        # the composed path's extents: the GEMMs contract over whole 32-element steps (gemm.hip: K % 32 == 0) -- QK^T over the head dim, the
+        # backward's dK / dV products over the queries: other head dims and query counts run zero-padded.  Exact: a zero head column adds
+        # nothing to a score or to a gradient, a padded query row (token id 0: a uniform row nobody reads, zero upstream gradient) nothing to
+        # dK / dV.  The row statistics (and the dropout mask's rows) are then those of the padded [b, heads, sp] grid.
+        self.hp, self.sp = (hn + 31) // 32 * 32, (sq + 31) // 32 * 32
+        self.stat_shape = (heads, ids_q.rows) if pq else (b, heads, sq if self.fused else self.sp)
+
+    def qkv_args(self, q, k, v):
+        """The ctypes argument prefix every fused entry starts with: q, k, v and their (batch, sequence, head) strides."""
+        return (q.data_ptr(),) + self.side_q[2:5] + (k.data_ptr(),) + self.side_k[2:5] + (v.data_ptr(),) + self.side_v[2:5]
+
+    def call(self, direction, head, stats, tail):
+        """One fused launch, "fwd" or "bwd": `head` = the operands up to the token ids; the ABI puts the backward's (m, l, dstat) = `stats` in
+        front of the shape and (drop_p, seed[, m, l]) = `tail` behind it.  Which entry is ONE decision for both directions: split keys when
+        the forward's plan said so, varlen when a side is packed (a forced ksplit == 1 over packed keys included), dense otherwise."""
+        (iq, cq), (ik, ck) = self.side_q[:2], self.side_k[:2]
+        name, packed, split = "attention_" + direction, (), ()
+        if self.ksplit > 1:
+            nbytes = self.ws_fwd if direction == "fwd" else self.ws_bwd
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=iq.device)
+            name, packed, split = name + "_splitkv", (_ptr(ck), self.pairs), (self.ksplit, ws.data_ptr(), nbytes)
+        elif self.pq or self.pk:
+            name, packed = "attention_varlen_" + direction, (_ptr(cq), _ptr(ck), self.ids_q.rows if self.pq else 0, self.pairs)
+        shape = (self.b, self.heads, self.sq, self.sk, self.hn, self.causal, self.scale)
+        args = head + (iq.data_ptr(), ik.data_ptr()) + packed + stats + shape + tail + split + (_sp(),)
+        _native.check(getattr(_lib(), "emdr2_" + name)(*args), name)
+
+    def composed_operands(self, q, k, v):
+        """q, k, v and the query ids of the composed path: themselves, or zero-padded copies [b, sp | sk, heads, hp] / [b, sp]."""
+        return _pad_seq_head(q, self.sp, self.hp), _pad_seq_head(k, self.sk, self.hp), _pad_seq_head(v, self.sk, self.hp), _pad_ids(self.side_q[0], self.sp)
+
+
+def _composed_attention_fwd(L, q, k, v, ctxo, m, l, drop_p, seed):
+    """QK^T GEMM + softmax kernel + PV GEMM for the dense shapes the fused kernels do not take (head dims other than 64)."""
+    b, heads, sk, hp, sp = L.b, L.heads, L.sk, L.hp, L.sp
+    if sk % 32:
+        raise ValueError("dense attention operands need a key length that is a multiple of 32 (got %d: K x --seq-length; the reference's "
+                         "sequence lengths 256 / 512 are; packed layouts take any length)" % sk)
+    q, k, v, iq = L.composed_operands(q, k, v)
+    padded = hp != L.hn or sp != L.sq
+    out = torch.empty((b, sp, heads, hp), dtype=BF16, device=q.device) if padded else ctxo
+    vT = head_transpose(v, b, sk, heads, hp)
+    S = torch.empty((b, heads, sp, sk), dtype=BF16, device=q.device)
+    gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sp, sk, hp, b, q.stride(0), k.stride(0), heads * sp * sk, heads, q.stride(2),
+            k.stride(2), sp * sk, alpha=L.scale)
+    _native.check(_lib().emdr2_softmax_mask_fwd(S.data_ptr(), iq.data_ptr(), L.side_k[0].data_ptr(), b, heads, sp, sk, L.causal,
+                                                m.data_ptr(), l.data_ptr(), drop_p, seed, _sp()), "softmax_fwd")
+    gemm_nt(S, sk, vT, sk, out, heads * hp, sp, hp, sk, b, heads * sp * sk, heads * hp * sk, sp * heads * hp, heads, sp * sk, hp * sk, hp)
+    if padded:
+        ctxo.copy_(out[:, :L.sq, :, :L.hn])
+
+
+def _composed_attention_bwd(L, q, k, v, m, l, D, dctx, dq, dk, dv, drop_p, seed):
+    """The composed path's backward: both orientations recomputed by GEMMs, the softmax kernels rebuild P from (m, l); D's first
+    [b, heads, sp] is rowsum(dctx * o)."""
+    b, heads, sk, causal, scale, hn, sq = L.b, L.heads, L.sk, L.causal, L.scale, L.hp, L.sp          # the (padded) extents everything below runs at
+    q, k, v, iq = L.composed_operands(q, k, v)
+    dctx = _pad_seq_head(dctx.view(b, L.sq, heads, L.hn), sq, hn)
+    grads, padded = (dq, dk, dv), hn != L.hn or sq != L.sq
+    if padded:
+        dq, dk, dv = (torch.empty((b, s, heads, hn), dtype=BF16, device=q.device) for s in (sq, sk, sk))
+    ik, H, lib = L.side_k[0], heads * hn, _lib()
+    # main orientation: S = scale Q K^T (recomputed), dP = dctx V^T, dS = P (dP_eff - D) with P rebuilt from (m, l)
+    S = torch.empty((b, heads, sq, sk), dtype=BF16, device=q.device)
+    gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sq, sk, hn, b, q.stride(0), k.stride(0), heads * sq * sk, heads, q.stride(2), k.stride(2),
+            sq * sk, alpha=scale)
+    dP = torch.empty((b, heads, sq, sk), dtype=BF16, device=q.device)
+    gemm_nt(dctx, H, v, v.stride(1), dP, sk, sq, sk, hn, b, sq * H, v.stride(0), heads * sq * sk, heads, hn, v.stride(2), sq * sk)
+    _native.check(lib.emdr2_softmax_mask_bwd(S.data_ptr(), dP.data_ptr(), iq.data_ptr(), ik.data_ptr(), m.data_ptr(), l.data_ptr(), b,
+                                             heads, sq, sk, causal, drop_p, seed, D.data_ptr(), _sp()), "softmax_bwd")
+    del S
+    kT = head_transpose(k, b, sk, heads, hn)
+    gemm_nt(dP, sk, kT, sk, dq, dq.stride(1), sq, hn, sk, b, heads * sq * sk, heads * hn * sk, dq.stride(0), heads, sq * sk, hn * sk, hn,
+            alpha=scale)
+    del dP
+    # transposed orientation: S^T, dP^T recomputed in the layout dK / dV need (no [sq, sk] transposes)
+    St = torch.empty((b, heads, sk, sq), dtype=BF16, device=q.device)
+    gemm_nt(k, k.stride(1), q, q.stride(1), St, sq, sk, sq, hn, b, k.stride(0), q.stride(0), heads * sk * sq, heads, k.stride(2), q.stride(2),
+            sk * sq, alpha=scale)
+    dPt = torch.empty_like(St)
+    gemm_nt(v, v.stride(1), dctx, H, dPt, sq, sk, sq, hn, b, v.stride(0), sq * H, heads * sk * sq, heads, v.stride(2), hn, sk * sq)
+    _native.check(lib.emdr2_softmax_mask_t(St.data_ptr(), dPt.data_ptr(), iq.data_ptr(), ik.data_ptr(), m.data_ptr(), l.data_ptr(),
+                                           D.data_ptr(), b, heads, sq, sk, causal, drop_p, seed, _sp()), "softmax_t")
+    qT = head_transpose(q, b, sq, heads, hn)
+    gemm_nt(dPt, sq, qT, sq, dk, dk.stride(1), sk, hn, sq, b, heads * sk * sq, heads * hn * sq, dk.stride(0), heads, sk * sq, hn * sq, hn,
+            alpha=scale)
+    dctxT = head_transpose(dctx, b, sq, heads, hn)
+    gemm_nt(St, sq, dctxT, sq, dv, dv.stride(1), sk, hn, sq, b, heads * sk * sq, heads * hn * sq, dv.stride(0), heads, sk * sq, hn * sq, hn)
+    if padded:
+        for out, g in zip(grads, (dq[:, :L.sq], dk, dv)):
+            out.copy_(g[..., :L.hn])
+
+
 class AttentionCoreFn(torch.autograd.Function):
     """dropout(softmax(mask(Q K^T / sqrt(hn)))) V for all heads (transformer.py:283-381).
     Inputs are the projection outputs themselves: self-attention passes `qsrc` = the packed [b, s, 3, np, hn] QKV tensor (kvsrc None),
@@ -908,83 +1034,24 @@ class AttentionCoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qsrc, kvsrc, ids_q, ids_k, causal, drop_p=0.0, seed=0, site=0):
         _check_bf16(qsrc, kvsrc)
-        if kvsrc is None:
-            q, k, v = qsrc.select(-3, 0), qsrc.select(-3, 1), qsrc.select(-3, 2)
-        else:
-            q, k, v = qsrc, kvsrc.select(-3, 0), kvsrc.select(-3, 1)
-        pq, pk = isinstance(ids_q, PackedSeqs), isinstance(ids_k, PackedSeqs)
-        iq, cq, q_sb, q_ss, q_sn, b, sq = _attn_side(q, ids_q)
-        ik, ck, k_sb, k_ss, k_sn, bk, sk = _attn_side(k, ids_k)
-        _, _, v_sb, v_ss, v_sn, _, _ = _attn_side(v, ids_k)
-        if b != bk:
-            raise ValueError("query and key batches differ")
-        heads, hn = q.shape[-2:]
-        dev = q.device
-        scale = 1.0 / math.sqrt(hn)
-        ctx.causal, ctx.drop_p, ctx.seed = causal, float(drop_p), int(seed)
-        ctx.ids_q, ctx.ids_k = ids_q, ids_k
+        ctx.launch = L = _AttnLaunch(qsrc, kvsrc, ids_q, ids_k, causal)
+        ctx.drop_p, ctx.seed = drop_p, seed = float(drop_p), int(seed)
         stash_key = (ATTN_STASH.key, site) if (ATTN_STASH.enabled and ATTN_STASH.mode and site) else None
         stashed = ATTN_STASH.store.pop(stash_key, None) if (stash_key and ATTN_STASH.mode == 'consume') else None
         if stashed is not None:                                                           # the layer's re-run: reuse the first run's output
             ctxo, m, l = stashed
             ctx.save_for_backward(qsrc, kvsrc, m, l, ctxo)
-            ctx.ksplit = _splitkv_plan(b, heads, sq, sk)[0] if (hn == 64 and not pq and sk <= 65536 and (pk or sk % 32 == 0)) else 1
             return ctxo
-        m = torch.empty((heads, ids_q.rows) if pq else (b, heads, sq), dtype=torch.float32, device=dev)
+        q, k, v = _qkv_views(qsrc, kvsrc)
+        m = torch.empty(L.stat_shape, dtype=torch.float32, device=q.device)
         l = torch.empty_like(m)
-        ctxo = torch.empty(tuple(q.shape[:-2]) + (heads, hn), dtype=BF16, device=dev)
-        fused = hn == 64 and sk <= 65536 and (pk or sk % 32 == 0)
-        if (pq or pk) and not fused:
-            raise ValueError("packed attention operands need head dim 64 (the fused kernels)")
-        # few dense queries over very many keys (the FiD decoder's cross-attention, cached decoding steps): keys dealt to several workgroups
-        ksplit, ws_f, _ = _splitkv_plan(b, heads, sq, sk) if (fused and not pq) else (1, 0, 0)
-        ctx.ksplit = ksplit
-        if ksplit > 1:
-            ws = torch.empty(ws_f, dtype=torch.uint8, device=dev)
-            pairs = sq * ids_k.total if pk else b * sq * sk
-            _native.check(_lib().emdr2_attention_fwd_splitkv(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, v.data_ptr(), v_sb, v_ss, v_sn,
-                                                             ctxo.data_ptr(), iq.data_ptr(), ik.data_ptr(), _ptr(ck), int(pairs), b, heads, sq, sk, hn,
-                                                             int(causal), scale, float(drop_p), int(seed), m.data_ptr(), l.data_ptr(), ksplit,
-                                                             ws.data_ptr(), ws_f, _sp()), "attention_fwd_splitkv")
-        elif pq or pk:
-            pairs = ids_q.pairs if (pq and ids_k is ids_q) else (sq * ids_k.total if not pq else 0)
-            _native.check(_lib().emdr2_attention_varlen_fwd(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, v.data_ptr(), v_sb, v_ss, v_sn,
-                                                            ctxo.data_ptr(), iq.data_ptr(), ik.data_ptr(), _ptr(cq), _ptr(ck), ids_q.rows if pq else 0,
-                                                            int(pairs or 0), b, heads, sq, sk, hn, int(causal), scale, float(drop_p), int(seed),
-                                                            m.data_ptr(), l.data_ptr(), _sp()), "attention_varlen_fwd")
-            if pq:
+        ctxo = torch.empty(tuple(q.shape[:-2]) + (L.heads, L.hn), dtype=BF16, device=q.device)
+        if L.fused:
+            L.call("fwd", L.qkv_args(q, k, v) + (ctxo.data_ptr(),), (), (drop_p, seed, m.data_ptr(), l.data_ptr()))
+            if L.pq:
                 ids_q.zero_tail(ctxo)
-        elif fused:
-            _native.check(_lib().emdr2_attention_fwd(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss,
-                                                     k_sn, v.data_ptr(), v_sb, v_ss, v_sn, ctxo.data_ptr(), iq.data_ptr(), ik.data_ptr(), b, heads, sq,
-                                                     sk, hn, int(causal), scale, float(drop_p), int(seed), m.data_ptr(), l.data_ptr(), _sp()),
-                          "attention_fwd")
         else:
-            if sk % 32:
-                raise ValueError("dense attention operands need a key length that is a multiple of 32 (got %d: K x --seq-length; the reference's "
-                                 "sequence lengths 256 / 512 are; packed layouts take any length)" % sk)
-            # the GEMMs contract over whole 32-element steps (gemm.hip: K % 32 == 0) -- QK^T over the head dim, the backward's dK / dV products
-            # over the queries: other head dims and query counts run zero-padded.  Exact: a zero head column adds nothing to a score or to a
-            # gradient, a padded query row (token id 0: a uniform row nobody reads, zero upstream gradient) nothing to dK / dV.  The row
-            # statistics (and the dropout mask's rows) are then those of the padded [b, heads, sp] grid.
-            hp, sp = (hn + 31) // 32 * 32, (sq + 31) // 32 * 32
-            padded = hp != hn or sp != sq
-            out = ctxo
-            if padded:
-                q, k, v = _pad_seq_head(q, sp, hp), _pad_seq_head(k, sk, hp), _pad_seq_head(v, sk, hp)
-                iq = _pad_ids(iq, sp)
-                m = torch.empty((b, heads, sp), dtype=torch.float32, device=dev)
-                l = torch.empty_like(m)
-                out = torch.empty((b, sp, heads, hp), dtype=BF16, device=dev)
-            vT = head_transpose(v, b, sk, heads, hp)
-            S = torch.empty((b, heads, sp, sk), dtype=BF16, device=dev)
-            gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sp, sk, hp, b, q.stride(0), k.stride(0), heads * sp * sk, heads, q.stride(2),
-                    k.stride(2), sp * sk, alpha=scale)
-            _native.check(_lib().emdr2_softmax_mask_fwd(S.data_ptr(), iq.data_ptr(), ik.data_ptr(), b, heads, sp, sk, int(causal),
-                                                        m.data_ptr(), l.data_ptr(), float(drop_p), int(seed), _sp()), "softmax_fwd")
-            gemm_nt(S, sk, vT, sk, out, heads * hp, sp, hp, sk, b, heads * sp * sk, heads * hp * sk, sp * heads * hp, heads, sp * sk, hp * sk, hp)
-            if padded:
-                ctxo.copy_(out[:, :sq, :, :hn])
+            _composed_attention_fwd(L, q, k, v, ctxo, m, l, drop_p, seed)
         ctx.save_for_backward(qsrc, kvsrc, m, l, ctxo)
         if stash_key and ATTN_STASH.mode == 'store':
             ATTN_STASH.store[stash_key] = (ctxo, m, l)
@@ -993,103 +1060,25 @@ class AttentionCoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dctx):
         qsrc, kvsrc, m, l, ctxo = ctx.saved_tensors
-        ids_q, ids_k = ctx.ids_q, ctx.ids_k
-        if kvsrc is None:
-            q, k, v = qsrc.select(-3, 0), qsrc.select(-3, 1), qsrc.select(-3, 2)
-            dqsrc, dkvsrc = torch.empty_like(qsrc), None
-            dq, dk, dv = dqsrc.select(-3, 0), dqsrc.select(-3, 1), dqsrc.select(-3, 2)
-        else:
-            q, k, v = qsrc, kvsrc.select(-3, 0), kvsrc.select(-3, 1)
-            dqsrc, dkvsrc = torch.empty_like(qsrc), torch.empty_like(kvsrc)
-            dq, dk, dv = dqsrc, dkvsrc.select(-3, 0), dkvsrc.select(-3, 1)
-        pq, pk = isinstance(ids_q, PackedSeqs), isinstance(ids_k, PackedSeqs)
-        iq, cq, q_sb, q_ss, q_sn, b, sq = _attn_side(q, ids_q)
-        ik, ck, k_sb, k_ss, k_sn, _, sk = _attn_side(k, ids_k)
-        _, _, v_sb, v_ss, v_sn, _, _ = _attn_side(v, ids_k)
-        _, _, dq_sb, dq_ss, _, _, _ = _attn_side(dq, ids_q)
-        _, _, dkv_sb, dkv_ss, _, _, _ = _attn_side(dk, ids_k)
-        heads, hn = q.shape[-2:]
-        dev = q.device
-        causal = int(ctx.causal)
-        scale = 1.0 / math.sqrt(hn)
+        L = ctx.launch
+        q, k, v = _qkv_views(qsrc, kvsrc)
+        dqsrc, dkvsrc = torch.empty_like(qsrc), (None if kvsrc is None else torch.empty_like(kvsrc))
+        dq, dk, dv = _qkv_views(dqsrc, dkvsrc)
         dctx = dctx.contiguous()
-        H = heads * hn
-        lib = _lib()
         # scratch of the fused kernels: four per-query statistics (exp2 offset, D = rowsum(dout * o), dropout row hash, real-token flag) the dq
-        # kernel leaves for the dk / dv kernel (include/emdr2_ops.h); the unfused path below uses the first [b, heads, sq] as D
-        D = torch.empty((4,) + tuple(m.shape), dtype=torch.float32, device=dev)
-        if getattr(ctx, "ksplit", 1) > 1:
-            _, _, ws_b = _splitkv_plan(b, heads, sq, sk)
-            ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
-            pairs = sq * ids_k.total if pk else b * sq * sk
-            _native.check(lib.emdr2_attention_bwd_splitkv(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, v.data_ptr(), v_sb, v_ss, v_sn,
-                                                          ctxo.data_ptr(), dctx.data_ptr(), dq.data_ptr(), dq_sb, dq_ss, dk.data_ptr(), dv.data_ptr(), dkv_sb,
-                                                          dkv_ss, iq.data_ptr(), ik.data_ptr(), _ptr(ck), int(pairs), m.data_ptr(), l.data_ptr(), D.data_ptr(),
-                                                          b, heads, sq, sk, hn, causal, scale, ctx.drop_p, ctx.seed, ctx.ksplit, ws.data_ptr(), ws_b, _sp()),
-                          "attention_bwd_splitkv")
-            if pk and dkvsrc is not None:
-                ids_k.zero_tail(dkvsrc)
-            return dqsrc, dkvsrc, None, None, None, None, None, None
-        if pq or pk:
-            pairs = ids_q.pairs if (pq and ids_k is ids_q) else (sq * ids_k.total if not pq else 0)
-            _native.check(lib.emdr2_attention_varlen_bwd(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, v.data_ptr(), v_sb, v_ss, v_sn,
-                                                         ctxo.data_ptr(), dctx.data_ptr(), dq.data_ptr(), dq_sb, dq_ss, dk.data_ptr(), dv.data_ptr(), dkv_sb,
-                                                         dkv_ss, iq.data_ptr(), ik.data_ptr(), _ptr(cq), _ptr(ck), ids_q.rows if pq else 0, int(pairs or 0),
-                                                         m.data_ptr(), l.data_ptr(), D.data_ptr(), b, heads, sq, sk, hn, causal, scale, ctx.drop_p,
-                                                         ctx.seed, _sp()), "attention_varlen_bwd")
-            if pq:                                                                        # tail rows feed the weight-gradient GEMMs: zeros
-                ids_q.zero_tail(dqsrc)
-            if pk and dkvsrc is not None:
-                ids_k.zero_tail(dkvsrc)
-            return dqsrc, dkvsrc, None, None, None, None, None, None
-        if hn == 64 and sk % 32 == 0 and sk <= 65536:                                     # fused: no [sq, sk] matrix, no operand transposes
-            _native.check(lib.emdr2_attention_bwd(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1),
-                                                  k.stride(2), v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), ctxo.data_ptr(), dctx.data_ptr(),
-                                                  dq.data_ptr(), dq.stride(0), dq.stride(1), dk.data_ptr(), dv.data_ptr(), dk.stride(0),
-                                                  dk.stride(1), iq.data_ptr(), ik.data_ptr(), m.data_ptr(), l.data_ptr(), D.data_ptr(), b,
-                                                  heads, sq, sk, hn, causal, scale, ctx.drop_p, ctx.seed, _sp()), "attention_bwd")
-            return dqsrc, dkvsrc, None, None, None, None, None, None
-        ids_q, ids_k = iq, ik
-        hp, sp = (hn + 31) // 32 * 32, (sq + 31) // 32 * 32                              # zero-padded like the forward (see there)
-        padded = hp != hn or sp != sq
-        if padded:
-            q, k, v = _pad_seq_head(q, sp, hp), _pad_seq_head(k, sk, hp), _pad_seq_head(v, sk, hp)
-            dctx = _pad_seq_head(dctx.view(b, sq, heads, hn), sp, hp).view(b, sp, heads * hp)
-            ids_q = _pad_ids(ids_q, sp)
-            outs = (dq, dk, dv, sq, hn)
-            dq = torch.empty((b, sp, heads, hp), dtype=BF16, device=dev)
-            dk, dv = torch.empty((b, sk, heads, hp), dtype=BF16, device=dev), torch.empty((b, sk, heads, hp), dtype=BF16, device=dev)
-            sq, hn, H = sp, hp, heads * hp
-        # main orientation: S = scale Q K^T (recomputed), dP = dctx V^T, dS = P (dP_eff - D) with P rebuilt from (m, l)
-        S = torch.empty((b, heads, sq, sk), dtype=BF16, device=dev)
-        gemm_nt(q, q.stride(1), k, k.stride(1), S, sk, sq, sk, hn, b, q.stride(0), k.stride(0), heads * sq * sk, heads, q.stride(2), k.stride(2),
-                sq * sk, alpha=scale)
-        dP = torch.empty((b, heads, sq, sk), dtype=BF16, device=dev)
-        gemm_nt(dctx, H, v, v.stride(1), dP, sk, sq, sk, hn, b, sq * H, v.stride(0), heads * sq * sk, heads, hn, v.stride(2), sq * sk)
-        _native.check(lib.emdr2_softmax_mask_bwd(S.data_ptr(), dP.data_ptr(), ids_q.data_ptr(), ids_k.data_ptr(), m.data_ptr(), l.data_ptr(), b,
-                                                 heads, sq, sk, causal, ctx.drop_p, ctx.seed, D.data_ptr(), _sp()), "softmax_bwd")
-        del S
-        kT = head_transpose(k, b, sk, heads, hn)
-        gemm_nt(dP, sk, kT, sk, dq, dq.stride(1), sq, hn, sk, b, heads * sq * sk, heads * hn * sk, dq.stride(0), heads, sq * sk, hn * sk, hn,
-                alpha=scale)
-        del dP
-        # transposed orientation: S^T, dP^T recomputed in the layout dK / dV need (no [sq, sk] transposes)
-        St = torch.empty((b, heads, sk, sq), dtype=BF16, device=dev)
-        gemm_nt(k, k.stride(1), q, q.stride(1), St, sq, sk, sq, hn, b, k.stride(0), q.stride(0), heads * sk * sq, heads, k.stride(2), q.stride(2),
-                sk * sq, alpha=scale)
-        dPt = torch.empty_like(St)
-        gemm_nt(v, v.stride(1), dctx, H, dPt, sq, sk, sq, hn, b, v.stride(0), sq * H, heads * sk * sq, heads, v.stride(2), hn, sk * sq)
-        _native.check(lib.emdr2_softmax_mask_t(St.data_ptr(), dPt.data_ptr(), ids_q.data_ptr(), ids_k.data_ptr(), m.data_ptr(), l.data_ptr(),
-                                               D.data_ptr(), b, heads, sq, sk, causal, ctx.drop_p, ctx.seed, _sp()), "softmax_t")
-        qT = head_transpose(q, b, sq, heads, hn)
-        gemm_nt(dPt, sq, qT, sq, dk, dk.stride(1), sk, hn, sq, b, heads * sk * sq, heads * hn * sq, dk.stride(0), heads, sk * sq, hn * sq, hn,
-                alpha=scale)
-        dctxT = head_transpose(dctx.view(b, sq, heads, hn), b, sq, heads, hn)
-        gemm_nt(St, sq, dctxT, sq, dv, dv.stride(1), sk, hn, sq, b, heads * sk * sq, heads * hn * sq, dv.stride(0), heads, sk * sq, hn * sq, hn)
-        if padded:
-            outs[0].copy_(dq[:, :outs[3], :, :outs[4]])
-            outs[1].copy_(dk[..., :outs[4]])
-            outs[2].copy_(dv[..., :outs[4]])
+        # kernel leaves for the dk / dv kernel (include/emdr2_ops.h); the composed path uses the first [b, heads, sp] as D
+        D = torch.empty((4,) + tuple(m.shape), dtype=torch.float32, device=q.device)
+        if L.fused:
+            dq_st = (0, dq.stride(0)) if L.pq else (dq.stride(0), dq.stride(1))            # (batch, sequence) strides of the gradients
+            dkv_st = (0, dk.stride(0)) if L.pk else (dk.stride(0), dk.stride(1))
+            L.call("bwd", L.qkv_args(q, k, v) + (ctxo.data_ptr(), dctx.data_ptr(), dq.data_ptr()) + dq_st + (dk.data_ptr(), dv.data_ptr()) + dkv_st,
+                   (m.data_ptr(), l.data_ptr(), D.data_ptr()), (ctx.drop_p, ctx.seed))
+            if L.pq:                                                                      # tail rows feed the weight-gradient GEMMs: zeros
+                L.ids_q.zero_tail(dqsrc)
+            if L.pk and dkvsrc is not None:
+                L.ids_k.zero_tail(dkvsrc)
+        else:
+            _composed_attention_bwd(L, q, k, v, m, l, D, dctx, dq, dk, dv, ctx.drop_p, ctx.seed)
         return dqsrc, dkvsrc, None, None, None, None, None, None
 
 

@@ -193,6 +193,8 @@ class AttentionCoreFn(torch.autograd.Function):
             q, k, v = qsrc.select(-3, 0), qsrc.select(-3, 1), qsrc.select(-3, 2)
         else:
             q, k, v = qsrc, kvsrc.select(-3, 0), kvsrc.select(-3, 1)
+        K._attn_side(q, ids_q)           # the kernels read the ids as contiguous int64 [b, s]: the bf16 path's check of a dense side
+        K._attn_side(k, ids_k)
         b, sq, heads, hn = q.shape
         sk = k.shape[1]
         scale = 1.0 / math.sqrt(hn)

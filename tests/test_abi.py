@@ -114,6 +114,76 @@ def test_r05_entry_points_validate_their_arguments(lib):
     assert lib.emdr2_attention_splitkv_plan(0, 12, 32, 25600, ctypes.byref(ks), ctypes.byref(fb), ctypes.byref(bb)) == -1
 
 
+_ONE = ctypes.c_void_p(4096)               # a non-null, 16-byte aligned fake pointer: every row below returns before any launch
+
+
+def _attn_call(lib, entry, **kw):
+    """One attention entry with batch = heads = 1, every stride 64, head dim 64, sq 32, every pointer the fake aligned one, unless `kw` says otherwise."""
+    a = dict(batch=1, heads=1, sq=32, sk=64, head_dim=64, causal=0, scale=0.125, drop_p=0.0, seed=0, cu_q=None, cu_k=None, total_q=0, pairs=0,
+             ksplit=1, ws=None, ws_bytes=0, q=_ONE, dq=_ONE, q_ss=64, dq_ss=64)
+    assert set(kw) <= set(a), kw
+    a.update(kw)
+    qkv = (a["q"], 64, a["q_ss"], 64, _ONE, 64, 64, 64, _ONE, 64, 64, 64)
+    bwd = entry.endswith("bwd") or "bwd_" in entry
+    ptrs = (_ONE, _ONE, a["dq"], 64, a["dq_ss"], _ONE, _ONE, 64, 64, _ONE, _ONE) if bwd else (_ONE, _ONE, _ONE)     # o [dout dq .. dkv_ss] ids_q ids_k
+    stats = (_ONE, _ONE, _ONE) if bwd else ()                                                                        # m l dstat (the forward's m, l: the tail)
+    shape = (a["batch"], a["heads"], a["sq"], a["sk"], a["head_dim"], a["causal"], a["scale"], a["drop_p"], a["seed"])
+    tail = () if bwd else (_ONE, _ONE)
+    if "splitkv" in entry:
+        args = qkv + ptrs + (a["cu_k"], a["pairs"]) + stats + shape + tail + (a["ksplit"], a["ws"], a["ws_bytes"], None)
+    elif "varlen" in entry:
+        args = qkv + ptrs + (a["cu_q"], a["cu_k"], a["total_q"], a["pairs"]) + stats + shape + tail + (None,)
+    else:
+        args = qkv + ptrs + stats + shape + tail + (None,)
+    return getattr(lib, entry)(*args)
+
+
+# (entry, arguments, code): the codes are what the library returned BEFORE the launchers were rewritten on shared validators; the order of the
+# checks decides which code a doubly-wrong call gets (null pointers -1, ksplit -1, shape / strides -4, packed row count -1, alignment and
+# drop_p -1, workspace size -2), and the forward splits only at >= 4,096 keys while the backward accepts any sk whose ranges match.
+_ATTN_CODES = [
+    ("emdr2_attention_fwd_splitkv", dict(sk=2048, ksplit=2, ws=_ONE, ws_bytes=1 << 30), -1),       # the forward does not split below 4,096 keys
+    ("emdr2_attention_fwd_splitkv", dict(sk=4096, ksplit=2, ws=None), -1),
+    ("emdr2_attention_fwd_splitkv", dict(sk=4096, ksplit=2, ws=_ONE, ws_bytes=0), -2),
+    ("emdr2_attention_fwd_splitkv", dict(sq=129, sk=4096, ksplit=2, ws=_ONE, ws_bytes=1 << 30), -1),
+    ("emdr2_attention_fwd_splitkv", dict(ksplit=1, ws=None, head_dim=32), -4),
+    ("emdr2_attention_bwd_splitkv", dict(sk=2112, ksplit=2, ws=_ONE, ws_bytes=0), -2),             # the backward has no 4,096 floor
+    ("emdr2_attention_fwd_splitkv", dict(sk=2112, ksplit=2, ws=_ONE, ws_bytes=0), -1),
+    ("emdr2_attention_bwd_splitkv", dict(sq=129, sk=4096, ksplit=2, ws=_ONE, ws_bytes=1 << 30), -1),
+    ("emdr2_attention_varlen_fwd", dict(), -1),                                                    # neither side packed
+    ("emdr2_attention_varlen_bwd", dict(), -1),
+    ("emdr2_attention_varlen_fwd", dict(cu_q=_ONE, total_q=0), -1),
+    ("emdr2_attention_varlen_fwd", dict(cu_q=_ONE, total_q=0, head_dim=32), -4),                   # the shape check comes first
+    ("emdr2_attention_bwd", dict(dq_ss=60), -4),
+    ("emdr2_attention_bwd", dict(drop_p=1.0), -1),
+    # the same orderings seen from the other launcher, and each kind of check once per direction
+    ("emdr2_attention_varlen_fwd", dict(cu_q=_ONE, total_q=0, q_ss=60), -4),                       # forward: strides with the shape, before the row count
+    ("emdr2_attention_varlen_bwd", dict(cu_q=_ONE, total_q=0, q_ss=60), -1),                       # backward: the row count before the strides
+    ("emdr2_attention_varlen_bwd", dict(cu_q=_ONE, total_q=0, head_dim=32), -4),
+    ("emdr2_attention_fwd", dict(q_ss=60), -4),
+    ("emdr2_attention_fwd", dict(q=ctypes.c_void_p(4104)), -1),
+    ("emdr2_attention_fwd", dict(q=ctypes.c_void_p(4104), sk=72), -4),                             # dense keys: whole 32-key steps, before alignment
+    ("emdr2_attention_fwd", dict(q=None, head_dim=32), -1),                                        # null pointers before everything
+    ("emdr2_attention_fwd", dict(sk=65568), -4),
+    ("emdr2_attention_bwd", dict(sk=72), -4),
+    ("emdr2_attention_bwd", dict(dq=ctypes.c_void_p(4100)), -1),
+    ("emdr2_attention_bwd", dict(dq=None, sk=72), -1),
+    ("emdr2_attention_bwd", dict(heads=1 << 16), -4),                                              # 32-bit lane offsets of the dk / dv staging
+    ("emdr2_attention_bwd_splitkv", dict(sk=4096, ksplit=3, ws=_ONE, ws_bytes=1 << 30), -1),       # not the number of ranges of 4,096 keys
+    ("emdr2_attention_bwd_splitkv", dict(sk=4096, ksplit=2, ws=ctypes.c_void_p(4104), ws_bytes=1 << 30), -1),
+    ("emdr2_attention_bwd_splitkv", dict(sk=4096, ksplit=2, ws=_ONE, ws_bytes=1 << 30, head_dim=32), -4),
+    ("emdr2_attention_fwd_splitkv", dict(sk=4096, ksplit=65, ws=_ONE, ws_bytes=1 << 30), -1),
+    ("emdr2_attention_fwd_splitkv", dict(sk=4096, ksplit=0), -1),
+    ("emdr2_attention_varlen_fwd", dict(cu_k=_ONE, sk=72, drop_p=-0.5), -1),                       # packed keys take any length
+]
+
+
+@pytest.mark.parametrize("row", range(len(_ATTN_CODES)))
+def test_attention_entry_points_keep_their_return_codes(lib, row):
+    entry, kw, code = _ATTN_CODES[row]
+    assert _attn_call(lib, entry, **kw) == code, (entry, kw)
+
+
 def test_fp32_validation_entry_points_validate_their_arguments(lib):
     """include/emdr2_ops_f32.h (ABI 4): null pointers / empty shapes are refused before any launch."""
     one = ctypes.c_void_p(4096)
