@@ -25,6 +25,7 @@ SIGNATURES = {
     "emdr2_mips_layout_bytes": (_i32, [_i64, _i32, ctypes.POINTER(_sz)]),
     "emdr2_mips_pack_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp]),
     "emdr2_mips_unpack_rows": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "emdr2_mips_gather_rows": (_i32, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp]),
     "emdr2_mips_export_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp]),
     "emdr2_mips_digest_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp]),
     "emdr2_mips_workspace_bytes": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_sz)]),
@@ -113,6 +114,8 @@ SIGNATURES["emdr2_attention_bwd_splitkv"] = (_i32, [_vp, _i64, _i64, _i64, _vp, 
 SIGNATURES["emdr2_gemm_nt_lse_bf16"] = (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp])
 SIGNATURES["emdr2_retriever_prior_fwd"] = (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])
 SIGNATURES["emdr2_retriever_prior_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])
+SIGNATURES["emdr2_retriever_prior_h16_fwd"] = (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])
+SIGNATURES["emdr2_retriever_prior_h16_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])
 SIGNATURES["emdr2_marginal_fwd"] = (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp])
 SIGNATURES["emdr2_marginal_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp])
 SIGNATURES["emdr2_lse_combine"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp])

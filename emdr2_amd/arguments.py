@@ -127,6 +127,16 @@ def get_parser():
                         'tuning knob: the index holds a mix of embedding generations, the retrieved rows being the freshest.  Allowed '
                         'without --async-indexer; with --async-indexer it needs --index-refresh-in-place (in swap mode every write would '
                         'be discarded at the next swap)')
+    g.add_argument('--context-embeddings-from-index', action='store_true',
+                   help='(not in the reference; needs --no-context-embedder-training) take the embeddings of the batch-size x topk retrieved '
+                        'passages from the index rows the search returned instead of running the frozen context encoder over them, in '
+                        'training and in evaluation mode: one gather launch (with several ranks plus one all-reduce of the gathered buffer) '
+                        'replaces the context tower\'s forward.  A choice of semantics, not a tuning knob: the prior is computed from '
+                        'WHATEVER the index holds -- fp16 rows widened exactly to fp32, no dropout.  For an index built from the frozen '
+                        'context encoder that is the tower\'s own output to within its bf16 arithmetic; an index built from other weights '
+                        'gives other scores.  Refused with --index-writeback (the step no longer computes anything to write back).  '
+                        '--async-indexer, with or without --index-refresh-in-place, stays allowed: re-embedding with a frozen encoder '
+                        'rewrites equal rows, and rows are read from the live image on the main stream, in the same order as the search')
     g.add_argument('--save-index-snapshot', action='store_true',
                    help='(not in the reference; needs --save) with --async-indexer: after every index update write the index just committed '
                         'to the one file <save>/evidence_index.flat (+ .meta), overwritten atomically like the reference\'s embedding file, a '
@@ -169,6 +179,12 @@ def parse_args(argv=None):
     if args.index_writeback and args.async_indexer and not args.index_refresh_in_place:
         raise ValueError("--index-writeback with --async-indexer needs --index-refresh-in-place (in swap mode a refresh is always in progress: "
                          "the index refuses in-place updates, and the next swap would discard them anyway)")
+    if args.context_embeddings_from_index and not args.no_context_embedder_training:
+        raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
+                         "silently stop receiving gradients)")
+    if args.context_embeddings_from_index and args.index_writeback:
+        raise ValueError("--context-embeddings-from-index and --index-writeback are exclusive (the step reads the passages' embeddings from "
+                         "the index: it no longer computes anything to write back)")
     args.iteration = 0
     # the reference's --fp16 (fp16 activations, fp32 masters inside FP16_Optimizer, dynamic loss scaling) maps to this build's ONLY
     # precision mode: bf16 activations and working weights, fp32 master weights and gradients, no loss scaling.  Said once, recorded in args.

@@ -979,9 +979,14 @@ extern "C" int emdr2_dropout(const void *x, void *out, int64_t n, int cols, floa
 }
 
 // ---- retriever prior (emdr2_model.py:134-145): sim[b, k] = <q[b], c[b, k]> * scale, log-softmax over the K retrieved passages --------------------
-// One workgroup per question; K <= 1024 (top-k 50 / 100 + 1 in the shipped scripts).  q, c bf16, everything else fp32.  prob (= exp(logp)) is
-// kept for the backward.
+// One workgroup per question; K <= 1024 (top-k 50 / 100 + 1 in the shipped scripts).  q bf16, everything else fp32.  prob (= exp(logp)) is
+// kept for the backward.  The contexts c are bf16 (the context tower's output) or fp16 (rows of the evidence index, --context-embeddings-from-
+// index): both widen exactly to fp32, so the kernels are templates over the context element and the arithmetic is stated once.
 #define PRIOR_MAX_K 1024
+struct CtxBf16 { static __device__ __forceinline__ float widen(uint16_t h) { return bf2f(h); } };
+struct CtxFp16 { static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); } };
+
+template <typename Ctx>
 __global__ void __launch_bounds__(256) retriever_prior_fwd_kernel(const uint16_t *q, const uint16_t *c, float *logp, float *prob, int K, int H, float scale)
 {
     __shared__ float sim[PRIOR_MAX_K];
@@ -996,7 +1001,7 @@ __global__ void __launch_bounds__(256) retriever_prior_fwd_kernel(const uint16_t
             const uint32_t qw[4] = {qa.x, qa.y, qa.z, qa.w}, cw[4] = {ca.x, ca.y, ca.z, ca.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                s += bf2f((uint16_t)(qw[j] & 0xffff)) * bf2f((uint16_t)(cw[j] & 0xffff)) + bf2f((uint16_t)(qw[j] >> 16)) * bf2f((uint16_t)(cw[j] >> 16));
+                s += bf2f((uint16_t)(qw[j] & 0xffff)) * Ctx::widen((uint16_t)(cw[j] & 0xffff)) + bf2f((uint16_t)(qw[j] >> 16)) * Ctx::widen((uint16_t)(cw[j] >> 16));
         }
         s = wave_sum(s);
         if (lane == 0) sim[k] = s * scale;
@@ -1020,6 +1025,7 @@ __global__ void __launch_bounds__(256) retriever_prior_fwd_kernel(const uint16_t
 }
 
 // d sim[k] = (g[k] - prob[k] * sum_j g[j]) * scale;  dq[h] = sum_k dsim[k] c[k, h];  dc[k, h] = dsim[k] q[h]   (bf16 gradients out)
+template <typename Ctx>
 __global__ void __launch_bounds__(256) retriever_prior_bwd_kernel(const float *g, const float *prob, const uint16_t *q, const uint16_t *c, uint16_t *dq,
                                                                   uint16_t *dc, int K, int H, float scale)
 {
@@ -1041,7 +1047,7 @@ __global__ void __launch_bounds__(256) retriever_prior_bwd_kernel(const float *g
         float acc = 0.f;
         const float qh = bf2f(qb[h]);
         for (int k = 0; k < K; ++k) {
-            acc += dsim[k] * bf2f(cb[(long long)k * H + h]);
+            acc += dsim[k] * Ctx::widen(cb[(long long)k * H + h]);
             if (dc) dc[((long long)b * K + k) * H + h] = f2bf(dsim[k] * qh);
         }
         if (dq) dq[(long long)b * H + h] = f2bf(acc);
@@ -1095,13 +1101,28 @@ __global__ void __launch_bounds__(256) lse_combine_kernel(const float *pmax, con
     }
 }
 
-extern "C" int emdr2_retriever_prior_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream)
+template <typename Ctx>
+static int prior_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream)
 {
     if (!q || !c || !logp || !prob || batch < 1 || K < 1 || H < 8 || (H & 7) || ((uintptr_t)q & 15) || ((uintptr_t)c & 15)) return -1;
     if (K > PRIOR_MAX_K) return -4;
-    hipLaunchKernelGGL(retriever_prior_fwd_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)c, logp, prob, K,
-                       H, scale);
+    hipLaunchKernelGGL(retriever_prior_fwd_kernel<Ctx>, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)c, logp, prob,
+                       K, H, scale);
     return LAUNCH_OK();
+}
+
+template <typename Ctx>
+static int prior_bwd(const float *dlogp, const float *prob, const void *q, const void *c, void *dq, void *dc, int batch, int K, int H, float scale,
+                     void *stream)
+{
+    hipLaunchKernelGGL(retriever_prior_bwd_kernel<Ctx>, dim3(batch), dim3(256), 0, (hipStream_t)stream, dlogp, prob, (const uint16_t *)q,
+                       (const uint16_t *)c, (uint16_t *)dq, (uint16_t *)dc, K, H, scale);
+    return LAUNCH_OK();
+}
+
+extern "C" int emdr2_retriever_prior_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream)
+{
+    return prior_fwd<CtxBf16>(q, c, logp, prob, batch, K, H, scale, stream);
 }
 
 extern "C" int emdr2_retriever_prior_bwd(const float *dlogp, const float *prob, const void *q, const void *c, void *dq, void *dc, int batch, int K, int H,
@@ -1109,9 +1130,22 @@ extern "C" int emdr2_retriever_prior_bwd(const float *dlogp, const float *prob, 
 {
     if (!dlogp || !prob || !q || !c || (!dq && !dc) || batch < 1 || K < 1 || H < 8) return -1;
     if (K > PRIOR_MAX_K) return -4;
-    hipLaunchKernelGGL(retriever_prior_bwd_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, dlogp, prob, (const uint16_t *)q, (const uint16_t *)c,
-                       (uint16_t *)dq, (uint16_t *)dc, K, H, scale);
-    return LAUNCH_OK();
+    return prior_bwd<CtxBf16>(dlogp, prob, q, c, dq, dc, batch, K, H, scale, stream);
+}
+
+// fp16 contexts (rows gathered from the evidence index): the same kernels, the same checks as the forward above for both directions.  The
+// contexts are constants of the step, so the backward has no dc.
+extern "C" int emdr2_retriever_prior_h16_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream)
+{
+    return prior_fwd<CtxFp16>(q, c, logp, prob, batch, K, H, scale, stream);
+}
+
+extern "C" int emdr2_retriever_prior_h16_bwd(const float *dlogp, const float *prob, const void *q, const void *c, void *dq, int batch, int K, int H,
+                                             float scale, void *stream)
+{
+    if (!dlogp || !prob || !q || !c || !dq || batch < 1 || K < 1 || H < 8 || (H & 7) || ((uintptr_t)q & 15) || ((uintptr_t)c & 15)) return -1;
+    if (K > PRIOR_MAX_K) return -4;
+    return prior_bwd<CtxFp16>(dlogp, prob, q, c, dq, nullptr, batch, K, H, scale, stream);
 }
 
 extern "C" int emdr2_marginal_fwd(const float *prior, const float *gold, float *marginal, int batch, int K, int L, void *stream)

@@ -116,7 +116,14 @@ int emdr2_mips_unpack_rows(const void *tiled, int64_t n_rows_total, int dim, con
                            void *rows_rm, emdr2_stream_t stream)
 {
     if (!tiled || !row_ids || !rows_rm || bad_shape(n_rows_total, dim) || n_out < 0) return EMDR2_E_BADARG;
-    return mips_launch_unpack_rows(tiled, dim, row_ids, n_out, rows_rm, (hipStream_t)stream);
+    return mips_launch_unpack_rows(tiled, n_rows_total, dim, 0, row_ids, n_out, rows_rm, (hipStream_t)stream);
+}
+
+int emdr2_mips_gather_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const int64_t *global_rows, int64_t n_out,
+                           void *rows_rm, emdr2_stream_t stream)
+{
+    if (!tiled || !global_rows || !rows_rm || bad_shape(n_rows, dim) || row_base < 0 || n_out < 0) return EMDR2_E_BADARG;
+    return mips_launch_unpack_rows(tiled, n_rows, dim, row_base, global_rows, n_out, rows_rm, (hipStream_t)stream);
 }
 
 int emdr2_mips_export_rows(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm,

@@ -179,24 +179,30 @@ int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t
     return CHECK_LAUNCH();
 }
 
-__global__ void unpack_rows_kernel(const char *__restrict__ tiled, int nseg, const int64_t *__restrict__ row_ids,
-                                   int64_t n_out, uint4 *__restrict__ rows_rm)
+// The one gather out of the image (emdr2_mips_unpack_rows: row_base 0; emdr2_mips_gather_rows: global rows): output row r is image row
+// row_ids[r] - row_base when that lies in [0, n_rows), all zero bytes otherwise (-1, a row of another shard, a row of the zero padding).
+// One 16-byte segment per thread; the ids are never used as an address unchecked.
+__global__ void unpack_rows_kernel(const char *__restrict__ tiled, int nseg, int64_t n_rows, int64_t row_base,
+                                   const int64_t *__restrict__ row_ids, int64_t n_out, uint4 *__restrict__ rows_rm)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_out * nseg) return;
     const int64_t r = i / nseg;
     const int seg = (int)(i - r * nseg);
-    rows_rm[i] = *(const uint4 *)(tiled + tiled_seg_offset(row_ids[r], seg, nseg >> 2));
+    const int64_t id = row_ids[r];
+    // (compared before the subtraction: no id, however wild, can wrap into the range)
+    const bool mine = id >= row_base && id - row_base < n_rows;
+    rows_rm[i] = mine ? *(const uint4 *)(tiled + tiled_seg_offset(id - row_base, seg, nseg >> 2)) : make_uint4(0, 0, 0, 0);
 }
 
-int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, int64_t n_out, void *rows_rm,
-                            hipStream_t stream)
+int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const int64_t *row_ids, int64_t n_out,
+                            void *rows_rm, hipStream_t stream)
 {
     const int nseg = dim / 8;
     const int64_t total = n_out * nseg;
     if (total == 0) return 0;
     hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const char *)tiled, nseg,
-                       row_ids, n_out, (uint4 *)rows_rm);
+                       n_rows, row_base, row_ids, n_out, (uint4 *)rows_rm);
     return CHECK_LAUNCH();
 }
 

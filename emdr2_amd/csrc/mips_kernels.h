@@ -75,8 +75,9 @@ int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64
                               unsigned *n_touched, unsigned *touched, unsigned cap, hipStream_t stream);
 int mips_launch_block_norms_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, float *block_norm_sq,
                                  hipStream_t stream);
-int mips_launch_unpack_rows(const void *tiled, int dim, const int64_t *row_ids, int64_t n_out, void *rows_rm,
-                            hipStream_t stream);
+// rows_rm[i] = image row row_ids[i] - row_base if that lies in [0, n_rows), else zero bytes
+int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const int64_t *row_ids, int64_t n_out,
+                            void *rows_rm, hipStream_t stream);
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);

@@ -683,6 +683,25 @@ class HipIndexShard(object):
                                                       out.data_ptr(), _native.stream_ptr()), "unpack_rows")
         return out
 
+    def rows_global(self, global_rows, out=None):
+        """Rows of the LIVE image (during a swap-mode refresh: the image being searched, not the spare) addressed by GLOBAL row, as a search
+        returns them: CUDA int64 of any shape [...] -> fp16 [..., dim], enqueued on the current stream (csrc: emdr2_mips_gather_rows).  A
+        row outside this shard's [row_base, row_base + n_rows) -- -1, another rank's row, the padding -- comes back as zeros, so every
+        rank can be handed the same merged list.  `out`: a contiguous CUDA fp16 buffer of that shape to write into.  Ordered against
+        in-place updates like a search: the caller orders it."""
+        if not torch.is_tensor(global_rows) or global_rows.dtype != torch.int64 or global_rows.device != self.device:
+            raise ValueError("global_rows must be an int64 tensor on %s" % (self.device,))
+        r = global_rows.contiguous()
+        shape = tuple(r.shape) + (self.dim,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float16, device=self.device)
+        elif out.dtype != torch.float16 or tuple(out.shape) != shape or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA float16 %s tensor" % (shape,))
+        if r.numel():
+            _native.check(self.lib.emdr2_mips_gather_rows(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, r.data_ptr(), r.numel(),
+                                                          out.data_ptr(), _native.stream_ptr()), "gather_rows")
+        return out
+
     # -- snapshots: the way out of HBM (emdr2_mips_export_rows / _digest_rows) ---------------------------------------------------------
     def _check_range(self, local_row, n):
         if self._filled != self.n_rows:
@@ -950,6 +969,35 @@ class DistributedBruteForceIndex(object):
     def _merge_records(self, gathered, f32):
         return merge_shard_records(gathered, f32)
 
+    # -- stored vectors by global row (search_and_reconstruct; --context-embeddings-from-index) ------------------------------------------
+    def reconstruct_rows(self, global_rows, scatter=False):
+        """The stored fp16 vectors of `global_rows` (CUDA int64 [...], as a search returns them: `last_search_rows`) -> CUDA fp16
+        [..., dim], bit for bit, at any world size; -1 (an empty slot) gives a zero vector.  Collective when the index is sharded: every
+        rank passes the SAME row tensor and every rank receives all vectors.  Each rank gathers its own rows into a buffer whose foreign
+        rows are zero (HipIndexShard.rows_global); the buffer, viewed as int32 (RCCL has no 16-bit integer type), goes through ONE
+        all_reduce(SUM): exactly one rank contributes non-zero bits to a row, so the integer sum hands back the stored bits -- -0.0, inf
+        and NaN payloads included, which a floating-point sum would not.  `scatter`: return only this rank's slice of the leading
+        dimension (which the world size must divide): reduce_scatter_tensor on RCCL, all_reduce + slice on other transports.  Enqueued on
+        the current stream, in the same order against in-place updates as a search: the caller orders it."""
+        if self.shard is None:
+            raise RuntimeError("MIPS Index is not initialized")
+        rank, world = self._world()
+        if world == 1:
+            return self.shard.rows_global(global_rows)
+        n = global_rows.shape[0] if global_rows.dim() else 0
+        if scatter and (global_rows.dim() < 1 or n % world):
+            raise ValueError("scatter: the world size %d must divide the leading dimension of %s" % (world, tuple(global_rows.shape)))
+        buf = self.shard.rows_global(global_rows)
+        if buf.numel() == 0:
+            return buf[rank * (n // world):(rank + 1) * (n // world)] if scatter else buf
+        words = buf.view(torch.int32)                                # (dim % 32 == 0: whole words)
+        if scatter and torch.distributed.get_backend(self.process_group) == "nccl":
+            mine = torch.empty((n // world,) + tuple(buf.shape[1:]), dtype=torch.float16, device=buf.device)
+            torch.distributed.reduce_scatter_tensor(mine.view(torch.int32), words, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
+            return mine
+        torch.distributed.all_reduce(words, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
+        return buf[rank * (n // world):(rank + 1) * (n // world)] if scatter else buf
+
 
 class FaissMIPSIndex(DistributedBruteForceIndex):
     """The evaluator's index (reference: emdr2_index.py:103-197: `faiss.IndexFlatIP(embed_size)` under `IndexIDMap`, optionally
@@ -982,8 +1030,6 @@ class FaissMIPSIndex(DistributedBruteForceIndex):
         indices = idx.to(torch.int64).cpu().numpy()
         if not reconstruct:
             return distances, indices
-        if world > 1:
-            raise NotImplementedError("search_and_reconstruct over a sharded index is not used by the reference evaluator")
-        local = (row - self.shard.row_base).clamp(min=0).reshape(-1)
-        vecs = self.shard.rows(local).to(torch.float32).reshape(row.shape[0], row.shape[1], self.embed_size)
+        # the hit vectors by their merged global rows, wherever they live (one all-reduce when sharded); an empty slot (row -1) is a zero vector
+        vecs = self.reconstruct_rows(row.contiguous()).to(torch.float32)
         return distances, indices, vecs.cpu().numpy()

@@ -147,19 +147,46 @@ class PreComputedEvidenceDocsRetriever(object):
         distance, topkindex = self._search(query_tensor)
         out = self.arena.assemble(topkindex, self.args.topk_retrievals, query_uid, query_ids_t5, query_ids_t5_len,
                                   self.args.seq_length_ret, self.args.seq_length, cls_id, sep_id, pad_id)
-        self.last_kept_rows = None
+        self.last_kept_rows = self._last_kept_slots = None
         if getattr(self, "track_rows", False) and self.last_search_rows is not None:
-            self.last_kept_rows = kept_rows(out[4], topkindex, self.last_search_rows)
+            self._last_kept_slots = kept_slots(out[4], topkindex)
+            self.last_kept_rows = _rows_of_slots(self._last_kept_slots, self.last_search_rows)
         return out + (distance,)
+
+    def kept_embeddings(self):
+        """(--context-embeddings-from-index) the stored index vectors fp16 [b, K, H] of `last_kept_rows` -- the passages the last
+        `get_topk_assembled` kept, under `track_rows` -- zero vectors where the row is -1.  One rank: one gather launch on the live image.
+        Several ranks: a rank's kept rows are its own, but `reconstruct_rows` wants the same list everywhere, so the merged rows of the
+        search (the same on every rank) go through the index's exchange in its scatter form -- ONE collective per forward on every rank,
+        behind the search's own -- and this rank's k searched vectors per question are cut down to the K kept slots on the device."""
+        if self.last_kept_rows is None:
+            raise RuntimeError("no tracked rows: kept_embeddings() follows a get_topk_assembled() with track_rows set")
+        if self._world()[1] == 1:
+            return self.mips_index.reconstruct_rows(self.last_kept_rows)
+        searched = self.mips_index.reconstruct_rows(self.mips_index.last_search_rows, scatter=True)            # [b, k, H]
+        slot, found = self._last_kept_slots
+        kept = searched.gather(1, slot.unsqueeze(2).expand(-1, -1, searched.shape[2]))
+        return kept.masked_fill(~found.unsqueeze(2), 0)
+
+
+def kept_slots(kept_ids, searched_ids):
+    """(slot int64 [b, K], found bool [b, K]): where among the question's own searched doc ids [b, k], k = K or K + 1, each doc id that
+    `assemble` kept [b, K] stands: doc ids are unique per index, so a kept id matches exactly one searched slot (the slot dropped as
+    trivial, or as the surplus one, matches none and is never named).  Empty slots (-1) are not found.  Static shapes, no host read."""
+    match = kept_ids.unsqueeze(2) == searched_ids.unsqueeze(1)                               # [b, K, k]
+    return match.to(torch.int8).argmax(2), (kept_ids >= 0) & match.any(2)
+
+
+def _rows_of_slots(slots, searched_rows):
+    slot, found = slots
+    rows = searched_rows.gather(1, slot)
+    return torch.where(found, rows, torch.full_like(rows, -1))
 
 
 def kept_rows(kept_ids, searched_ids, searched_rows):
     """The index rows [b, K] of the doc ids `assemble` kept [b, K], found among the question's own searched (doc id [b, k], row [b, k])
-    pairs, k = K or K + 1: doc ids are unique per index, so a kept id matches exactly one searched slot (the slot dropped as trivial, or
-    as the surplus one, matches none and is never named).  Empty slots (-1) stay -1.  Static shapes, no host read."""
-    match = kept_ids.unsqueeze(2) == searched_ids.unsqueeze(1)                               # [b, K, k]
-    rows = searched_rows.gather(1, match.to(torch.int8).argmax(2))
-    return torch.where((kept_ids >= 0) & match.any(2), rows, torch.full_like(rows, -1))
+    pairs (`kept_slots`).  Empty slots (-1) stay -1."""
+    return _rows_of_slots(kept_slots(kept_ids, searched_ids), searched_rows)
 
 
 # =====================================================================================================================
@@ -201,7 +228,8 @@ class EMDR2Model(torch.nn.Module):
 
     def __init__(self, evidence_retriever, cfg=None, t5_vocab_size=None, bert_vocab_size=None, topk=None, seq_length=None, seq_length_ret=None,
                  cls_id=None, sep_id=None, pad_id=0, update_retriever=True, retriever_score_scaling=True, checkpoint_activations=False,
-                 disable_retriever_dropout=False, no_query_embedder_training=False, no_context_embedder_training=False):
+                 disable_retriever_dropout=False, no_query_embedder_training=False, no_context_embedder_training=False,
+                 context_embeddings_from_index=False):
         """`EMDR2Model(evidence_retriever)` -- the reference's form (emdr2_model.py:31-61): architecture, sequence lengths, top-k and the
         training switches from `get_args()`, vocabulary sizes and special ids from the global tokenizers.  Passing `cfg` and the rest
         explicitly bypasses the globals (tests, bench)."""
@@ -220,6 +248,7 @@ class EMDR2Model(torch.nn.Module):
             update_retriever, retriever_score_scaling = a.update_retriever, a.retriever_score_scaling
             checkpoint_activations, disable_retriever_dropout = a.checkpoint_activations, a.disable_retriever_dropout
             no_query_embedder_training, no_context_embedder_training = a.no_query_embedder_training, a.no_context_embedder_training
+            context_embeddings_from_index = getattr(a, "context_embeddings_from_index", False)
         self.topk = topk
         self.language_model = T5Model(cfg, t5_vocab_size, 2, checkpoint_activations)
         self._language_model_key = 'encoder/t5_model'
@@ -233,6 +262,12 @@ class EMDR2Model(torch.nn.Module):
         self.disable_retriever_dropout = disable_retriever_dropout                  # --disable-retriever-dropout (arguments.py:558)
         self.no_query_embedder_training = no_query_embedder_training              # emdr2_model.py:103-104
         self.no_context_embedder_training = no_context_embedder_training          # emdr2_model.py:130-131
+        # --context-embeddings-from-index: the prior over the K retrieved passages is computed from the index rows the search returned
+        # (PreComputedEvidenceDocsRetriever.kept_embeddings); the context tower is not run, in training or in evaluation mode
+        if context_embeddings_from_index and not no_context_embedder_training:
+            raise ValueError("context_embeddings_from_index needs no_context_embedder_training: the context tower is not run, so it would "
+                             "silently stop receiving gradients")
+        self.context_embeddings_from_index = bool(context_embeddings_from_index)
         self.fuse_lm_head_loss = True          # one-context pass: LM head + log-softmax + gather in one GEMM (OneContextLogits); False = reference tensor
         # --index-writeback: in training mode keep the step's fresh context embeddings and the index rows they belong to, for
         # `take_writeback` at the step boundary.  Off: nothing is kept and the retriever does not track rows.
@@ -261,8 +296,9 @@ class EMDR2Model(torch.nn.Module):
         with torch.no_grad():                                            # emdr2_model.py:107-115 on the device
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
+            ctx_embeds = self.evidence_retriever.kept_embeddings() if self.context_embeddings_from_index else None
         self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
-        return self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids)
+        return self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids, ctx_embeds)
 
     def _keeps_writeback(self):
         return self.index_writeback and self.training
@@ -271,7 +307,9 @@ class EMDR2Model(torch.nn.Module):
         """Start of a step's forward: drop what an earlier (possibly failed and now re-run) step kept, tell the retriever whether to
         track the rows of what it retrieves."""
         self._writeback_rows, self._writeback_embeds = None, []
-        if self.index_writeback:
+        if self.context_embeddings_from_index:
+            self.evidence_retriever.track_rows = True                   # the rows are what the prior is computed from, in eval mode too
+        elif self.index_writeback:
             self.evidence_retriever.track_rows = self.training
 
     def take_writeback(self):
@@ -285,17 +323,23 @@ class EMDR2Model(torch.nn.Module):
         emb = torch.cat(embeds, dim=0) if len(embeds) > 1 else embeds[0]
         return rows.reshape(-1).to(torch.int64), emb.reshape(-1, emb.shape[-1]).to(torch.float16)
 
-    def forward_assembled(self, query_logits, ctx_ids, ctx_types, qext, qone, dec_ids):
+    def forward_assembled(self, query_logits, ctx_ids, ctx_types, qext, qone, dec_ids, ctx_embeds=None):
+        """`ctx_embeds` (--context-embeddings-from-index): the stored index vectors fp16 [B, K, H] of this call's questions; given, the
+        context tower is not run and the prior is computed from them (fp16 widened exactly, constants of the step)."""
         B, Kk = ctx_ids.shape[:2]
         H = self.hidden_size
-        ctx_logits = self.retriever_embedder(ctx_ids.reshape(B * Kk, -1), None, ctx_types.reshape(B * Kk, -1), "context",
-                                             self.disable_retriever_dropout).reshape(B, Kk, H)
-        if self.no_context_embedder_training:
-            ctx_logits = ctx_logits.detach()
-        if self._writeback_rows is not None and self._keeps_writeback():
-            self._writeback_embeds.append(ctx_logits.detach())          # [b, K, H] of this call's questions (--index-writeback)
-        # fresh retriever scores -> prior over the K passages (emdr2_model.py:134-145): fp32 dot products, /sqrt(H), log-softmax, one HIP kernel
-        topk_log_probs = K.retriever_prior(query_logits, ctx_logits, 1.0 / math.sqrt(H) if self.retriever_score_scaling else 1.0)
+        scale = 1.0 / math.sqrt(H) if self.retriever_score_scaling else 1.0
+        if ctx_embeds is not None:
+            topk_log_probs = K.retriever_prior_h16(query_logits, ctx_embeds, scale)
+        else:
+            ctx_logits = self.retriever_embedder(ctx_ids.reshape(B * Kk, -1), None, ctx_types.reshape(B * Kk, -1), "context",
+                                                 self.disable_retriever_dropout).reshape(B, Kk, H)
+            if self.no_context_embedder_training:
+                ctx_logits = ctx_logits.detach()
+            if self._writeback_rows is not None and self._keeps_writeback():
+                self._writeback_embeds.append(ctx_logits.detach())          # [b, K, H] of this call's questions (--index-writeback)
+            # fresh retriever scores -> prior over the K passages (emdr2_model.py:134-145): fp32 dot products, /sqrt(H), log-softmax, one HIP kernel
+            topk_log_probs = K.retriever_prior(query_logits, ctx_logits, scale)
 
         S = qext.shape[1]
         packed = self.language_model.language_model.packs()
@@ -365,6 +409,7 @@ class EMDR2Model(torch.nn.Module):
         with torch.no_grad():                                            # ONE search + device-side fetch / assembly for all B questions
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
+            ctx_embeds = self.evidence_retriever.kept_embeddings() if self.context_embeddings_from_index else None
         self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
         Kk = ctx_ids.shape[1]
         q_leaf = query_logits.detach().requires_grad_(query_logits.requires_grad)
@@ -374,7 +419,7 @@ class EMDR2Model(torch.nn.Module):
             for i, (lo, hi) in enumerate(bounds):
                 K.DROPOUT.micro = i
                 lm, tlp, one = self.forward_assembled(q_leaf[lo:hi], ctx_ids[lo:hi], ctx_types[lo:hi], qext[lo * Kk:hi * Kk], qone[lo * Kk:hi * Kk],
-                                                      dec_ids[lo:hi])
+                                                      dec_ids[lo:hi], ctx_embeds[lo:hi] if ctx_embeds is not None else None)
                 loss, stats = emdr2_loss(lm, tlp, one, labels[lo:hi], loss_mask[lo:hi], eos_id, ret_kldiv=ret_kldiv, totals=totals)
                 del lm, tlp, one
                 if on_group is not None:

@@ -1244,6 +1244,48 @@ def retriever_prior(q, c, scale):
     return RetrieverPriorFn.apply(q, c, scale)
 
 
+class RetrieverPriorH16Fn(torch.autograd.Function):
+    """RetrieverPriorFn over fp16 contexts [B, K, H] -- rows of the evidence index (--context-embeddings-from-index), constants of the step:
+    the gradient goes to q alone.  q bf16 and c fp16 are widened exactly inside the kernel (emdr2_retriever_prior_h16_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, q, c, scale):
+        _check_bf16(q)
+        if c.dtype != torch.float16 or not c.is_cuda or c.dim() != 3:
+            raise TypeError("expected a CUDA float16 [B, K, H] tensor of index rows")
+        q, c = q.contiguous(), c.contiguous()
+        B, Kk, H = c.shape
+        logp = torch.empty((B, Kk), dtype=torch.float32, device=q.device)
+        prob = torch.empty_like(logp)
+        _native.check(_lib().emdr2_retriever_prior_h16_fwd(q.data_ptr(), c.data_ptr(), logp.data_ptr(), prob.data_ptr(), B, Kk, H, float(scale), _sp()),
+                      "retriever_prior_h16_fwd")
+        ctx.save_for_backward(q, c, prob)
+        ctx.scale = float(scale)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        q, c, prob = ctx.saved_tensors
+        B, Kk, H = c.shape
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        dq = torch.empty_like(q)
+        g = dlogp.to(torch.float32).contiguous()
+        _native.check(_lib().emdr2_retriever_prior_h16_bwd(g.data_ptr(), prob.data_ptr(), q.data_ptr(), c.data_ptr(), dq.data_ptr(), B, Kk, H, ctx.scale,
+                                                           _sp()), "retriever_prior_h16_bwd")
+        return dq, None, None
+
+
+def retriever_prior_h16(q, c_fp16, scale):
+    """The prior from index rows: q [B, H] (bf16; fp32 under --fp32-validation), c_fp16 [B, K, H] fp16 constants.  Under --fp32-validation
+    there is no kernel of its own: the rows are widened with .float(), which is exact, and go to the fp32 prior."""
+    if c_fp16.requires_grad:
+        raise ValueError("retriever_prior_h16 takes the contexts as constants (index rows): c must not require grad")
+    if _f32(q):
+        return _F32().retriever_prior(q, c_fp16.float(), scale)
+    return RetrieverPriorH16Fn.apply(q, c_fp16, scale)
+
+
 class MarginalFn(torch.autograd.Function):
     """marginal [B, L] = logsumexp_k(prior[b, k] + gold[b, k, l]) (train_e2eqa.py:98-123); gold comes from the no-grad pass (constant)."""
 

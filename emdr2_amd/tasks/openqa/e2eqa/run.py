@@ -65,7 +65,8 @@ def model_provider(args=None, bert_tokenizer=None, t5_tokenizer=None, arena=None
                        checkpoint_activations=args.checkpoint_activations and getattr(args, "question_micro_batches", 1) <= 1,
                        disable_retriever_dropout=args.disable_retriever_dropout,
                        no_query_embedder_training=args.no_query_embedder_training,
-                       no_context_embedder_training=args.no_context_embedder_training)
+                       no_context_embedder_training=args.no_context_embedder_training,
+                       context_embeddings_from_index=bool(getattr(args, "context_embeddings_from_index", False)))
     model.index_writeback = bool(getattr(args, "index_writeback", False))
     model.set_recompute_keep_last(getattr(args, "recompute_keep_last_layers", 0))
     sel = [int(v) for v in str(getattr(args, "selective_retention_layers", "0,0,0")).split(",")]

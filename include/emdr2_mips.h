@@ -14,6 +14,8 @@
  *                                       and the two broadcasts                       emdr2_model.py:451-452
  *                                       (here: k-way merge of per-shard top-k after ONE all-gather)
  *   emdr2_mips_unpack_rows    inverse of pack_rows (reconstruct / store export)
+ *   emdr2_mips_gather_rows    the same by GLOBAL row, zero rows outside the shard (search_and_reconstruct over a sharded index;
+ *                             the retrieved passages' embeddings for --context-embeddings-from-index)
  *
  * Conventions: raw device pointers + sizes + hipStream_t; the caller (torch) owns every buffer;
  * nothing is allocated inside; every function returns 0 on success or a negative EMDR2_E_* code
@@ -68,9 +70,19 @@ int emdr2_mips_layout_bytes(int64_t n_rows, int dim, size_t *bytes);
 int emdr2_mips_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset,
                          int64_t n_rows_total, void *tiled, float *emax_sq, emdr2_stream_t stream);
 
-/* Gather rows back: rows_rm[i] = E[row_ids[i]] (row-major fp16), row_ids device int64 (local rows). */
+/* Gather rows back: rows_rm[i] = E[row_ids[i]] (row-major fp16), row_ids device int64 (local rows).  An id outside [0, n_rows_total)
+ * yields a zero row (it is _gather_rows with row_base 0). */
 int emdr2_mips_unpack_rows(const void *tiled, int64_t n_rows_total, int dim, const int64_t *row_ids,
                            int64_t n_out, void *rows_rm, emdr2_stream_t stream);
+
+/* Gather by GLOBAL row (search results: out_row / last_search_rows): rows_rm (device fp16 [n_out, dim], row-major, 16-byte aligned)
+ * row i receives image row global_rows[i] - row_base, bit for bit, when that row lies in [0, n_rows); otherwise all zero bytes -- -1 (an
+ * empty slot), a row of another rank's shard, a row in the zero padding.  So every rank can be handed the same merged row list and the
+ * buffers of the ranks have exactly one non-zero contributor per row.  One launch of 16-byte segment copies on `stream`; nothing is
+ * allocated, no host synchronisation.  n_out == 0 is a no-op returning 0; EMDR2_E_BADARG for null pointers, row_base < 0 or a dim
+ * outside the layout's envelope. */
+int emdr2_mips_gather_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const int64_t *global_rows, int64_t n_out,
+                           void *rows_rm, emdr2_stream_t stream);
 
 /*
  * Index snapshots: a contiguous row range of a shard image back out of HBM, and its digest.

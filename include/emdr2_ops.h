@@ -215,6 +215,14 @@ int emdr2_lse_combine(const float *part_max, const float *part_sum, const float 
 int emdr2_retriever_prior_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream);
 int emdr2_retriever_prior_bwd(const float *dlogp, const float *prob, const void *q, const void *c, void *dq, void *dc, int batch, int K, int H,
                               float scale, void *stream);
+/* The same prior with fp16 contexts: c fp16 [batch, K, H], row-major, 16-byte aligned -- rows gathered from the evidence index
+ * (emdr2_mips_gather_rows, --context-embeddings-from-index).  q bf16 and c fp16 are both widened exactly to fp32, fp32 accumulation, * scale,
+ * log-softmax over K: the kernels of the entries above instantiated for the other context element, not a cast (fp16 -> bf16 would drop three
+ * mantissa bits of every stored value).  Same checks: K > 1024 -> -4; null or misaligned q / c, H < 8 or H & 7 -> -1.  The contexts are
+ * constants of the step: the backward writes dq (bf16 [batch, H]) only. */
+int emdr2_retriever_prior_h16_fwd(const void *q, const void *c, float *logp, float *prob, int batch, int K, int H, float scale, void *stream);
+int emdr2_retriever_prior_h16_bwd(const float *dlogp, const float *prob, const void *q, const void *c, void *dq, int batch, int K, int H,
+                                  float scale, void *stream);
 /* EMDR2 marginal likelihood (train_e2eqa.py:98-123): marginal[b, l] = logsumexp_k( prior[b, k] + gold[b, k, l] ), gold = per-passage gold
  * log-likelihoods of the no-grad one-context pass (constants).  bwd: dprior[b, k] = sum_l dmarginal[b, l] * posterior[b, k, l].  All fp32. */
 int emdr2_marginal_fwd(const float *prior, const float *gold, float *marginal, int batch, int K, int L, void *stream);
