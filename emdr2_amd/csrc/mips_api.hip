@@ -185,14 +185,32 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         const int BM = kBM[variant], BN = kBN[variant];
         const uint16_t *qp = (const uint16_t *)queries + (size_t)q0 * dim;
         int rc;
-        if ((rc = mips_launch_pack_queries(qp, nqp, dim, BN, w.q_tiled, w.qnorm, stream))) return rc;
-        EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
         const int64_t dense_rows = n_rows < seg0 ? n_rows : seg0;
         unsigned *const count8 = w.count + 512, *const pcount = count8 + 8 * 512, *const prog0 = pcount + 512;
-        // thresholds, counts, flags -- and the sub-list counts, pending counts and pair-progress counters of the persistent scan launches -- in one launch
-        if ((rc = mips_launch_init(w.tau, w.count, out_flags + q0, BN, nqp, (unsigned)dense_rows, count8,
-                                   9 * 512 + (variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0), stream)))
-            return rc;
+        // the int8 query image and the per-query constants live where the fragment-tiled query image of the experiment kernels would
+        // (half its size + 8 KiB); packed only if some segment of this search can take the int8 path
+        const bool shadow_ok = shadow && variant <= 1 && scan_kernel == 1 && (dim % 256) == 0 && n_rows - dense_rows >= shadow->min_rows;
+        char *const q8_tiled = w.q_frag;
+        float *const qc = (float *)(w.q_frag + (size_t)(dim / 64) * 512 * 64);
+        // query images and norms; thresholds, counts, flags -- and the sub-list counts, pending counts and pair-progress counters of the
+        // persistent scan launches -- in one launch
+        PrepareParams pp;
+        pp.queries = qp;
+        pp.n_q = nqp;
+        pp.dim = dim;
+        pp.bn = BN;
+        pp.q_tiled = w.q_tiled;
+        pp.qnorm = w.qnorm;
+        pp.tau = w.tau;
+        pp.count = w.count;
+        pp.flags = out_flags + q0;
+        pp.dense_count = (unsigned)dense_rows;
+        pp.zero = count8;
+        pp.n_zero = 9 * 512 + (variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0);
+        pp.q8_tiled = shadow_ok ? q8_tiled : nullptr;
+        pp.qc = qc;
+        if ((rc = mips_launch_prepare(pp, stream))) return rc;
+        EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
 
         ScanParams sp;
         sp.e_tiled = (const char *)tiled;
@@ -213,12 +231,6 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         sp.trace = (unsigned long long *)w.cand + (size_t)511 * CAPQ; // scratch tail of the candidate area (ABL 9 only)
 
         int scan8_launches = 0;                              // (fp16 and int8 launches share the progress counters zeroed above: both count)
-        // the int8 query image and the per-query constants live where the fragment-tiled query image of the experiment kernels would
-        // (half its size + 8 KiB); packed only if some segment of this search can take the int8 path
-        const bool shadow_ok = shadow && variant <= 1 && scan_kernel == 1 && (dim % 256) == 0 && n_rows - dense_rows >= shadow->min_rows;
-        char *const q8_tiled = w.q_frag;
-        float *const qc = (float *)(w.q_frag + (size_t)(dim / 64) * 512 * 64);
-        if (shadow_ok && (rc = mips_launch_pack_queries_i8(qp, nqp, dim, BN, q8_tiled, qc, stream))) return rc;
         const bool couple = EXP_MIPS_COUPLE();
         int64_t done = 0, seg_end = dense_rows;
         int mode = 1;
@@ -266,11 +278,10 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
                 pending = true;
             }
             // (the select after the LAST segment runs inside the finalize launch -- after a select of its own when something is pending: the
-            // deferred pass wants the tightest tau, and its survivors must be in the main list before the final select)
+            // deferred pass, the first thing that launch does then, wants the tightest tau)
             if ((seg_end < n_rows || pending) &&
                 (rc = mips_launch_select(w.cand, w.count, w.cand8, count8, w.tau, out_flags + q0, CAPQ, kp, nqp, stream)))
                 return rc;
-            if (seg_end >= n_rows && pending && (rc = mips_launch_rescore_pending(sp, qp, w.pend, pcount, stream))) return rc;
             done = seg_end;
             // the next segment ends at `growth` times the rows done so far -- at `growth_i8` times once a segment of that length runs on the int8
             // image: its survivors are ~6 x the fp16 filter's and each costs a 1.5 KB gather in the re-score, so a fresher threshold pays there
@@ -304,6 +315,8 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         fp.k = k;
         fp.kp = kp;
         fp.capq = CAPQ;
+        fp.pend = pending ? w.pend : nullptr;
+        fp.pcount = pcount;
         if ((rc = mips_launch_finalize(fp, true, stream))) return rc;
     }
     return EMDR2_OK;
@@ -530,7 +543,14 @@ int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const vo
     if (force_variant >= 0 && force_variant <= 2 && kBN[force_variant] >= n_q) variant = force_variant;
     const int BM = kBM[variant], BN = kBN[variant];
     int rc;
-    if ((rc = mips_launch_pack_queries(queries, n_q, dim, BN, w.q_tiled, w.qnorm, stream))) return rc;
+    PrepareParams pp = {};                                   // (the query image alone: a dense scan has no thresholds and no lists)
+    pp.queries = queries;
+    pp.n_q = n_q;
+    pp.dim = dim;
+    pp.bn = BN;
+    pp.q_tiled = w.q_tiled;
+    pp.qnorm = w.qnorm;
+    if ((rc = mips_launch_prepare(pp, stream))) return rc;
     ScanParams sp;
     sp.e_tiled = (const char *)tiled;
     sp.q_tiled = w.q_tiled;

@@ -303,26 +303,80 @@ int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int6
 // ------------------------------------------------------------------------------------------------
 // query packing: [n_q, dim] row-major -> per chunk a [bn rows x 64 B] swizzled block (zero padded)
 // ------------------------------------------------------------------------------------------------
-__global__ void pack_queries_kernel(const uint4 *__restrict__ queries, int n_q, int nseg, int bn, char *__restrict__ q_tiled,
-                                    float *__restrict__ qnorm)
+// Everything a search sets up before its first scan, in one launch (PrepareParams in mips_kernels.h names the three parts); one wave per
+// padded query row, which it reads from memory once.  The fp16 image and ||q|| come straight from the loaded segments; the int8 image needs
+// max |q| first, so the row waits in LDS (dim * 2 bytes, only when that part is asked for) and is quantised from there: chunk-tiled like the
+// fp16 one with 64 k-values per chunk, per query {t_q, a_q, b_q} of mips_scan8i.hip.  The wave's threads also spread the few thousand words
+// of thresholds, counts, flags and zeroed counters over the grid.
+__global__ void __launch_bounds__(64) prepare_kernel(PrepareParams p)
 {
-    const int q = blockIdx.x; // one wave per padded query row
-    const int lane = threadIdx.x;
-    float s = 0.f;
+    extern __shared__ uint4 sh_qrow[];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int n_q = p.n_q, nseg = p.dim / 8, bn = p.bn;
+    const uint4 *queries = (const uint4 *)p.queries;
+    char *const q_tiled = (char *)p.q_tiled, *const q8 = (char *)p.q8_tiled;
+    float s = 0.f, amax = 0.f;
     for (int seg = lane; seg < nseg; seg += 64) {
         uint4 v = make_uint4(0, 0, 0, 0);
         if (q < n_q) {
             v = queries[(size_t)q * nseg + seg];
             const half8 h = __builtin_bit_cast(half8, v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float x = (float)h[j]; s += x * x; }
+            for (int j = 0; j < 8; ++j) { const float x = (float)h[j]; s += x * x; amax = fmaxf(amax, fabsf(x)); }
         }
         const int c = seg >> 2, sp = (seg & 3) ^ ((q >> 2) & 3);
         *(uint4 *)(q_tiled + ((size_t)c * bn * 4 + (size_t)q * 4 + sp) * 16) = v;
+        if (q8) sh_qrow[seg] = v;
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0 && q < n_q) qnorm[q] = sqrtf(s) * 1.001f;
+    if (lane == 0 && q < n_q) p.qnorm[q] = sqrtf(s) * 1.001f;
+
+    if (p.tau) {
+        const unsigned i = (unsigned)q * 64 + lane;
+        if (i < (unsigned)bn) {
+            p.tau[i] = -__builtin_inff();
+            p.count[i] = (i < (unsigned)n_q) ? p.dense_count : 0u;
+        }
+        if (i < (unsigned)n_q) p.flags[i] = 0u;
+        // the sub-list counts, pending counts and pair-progress counters of the persistent scan launches (mips_scan8.hip)
+        uint4 *const zero16 = (uint4 *)p.zero;
+        const unsigned n_zero16 = (unsigned)(p.n_zero / 4);
+        for (unsigned j = i; j < n_zero16; j += gridDim.x * 64) zero16[j] = make_uint4(0u, 0u, 0u, 0u);
+    }
+
+    if (!q8) return;
+    __syncthreads();                                           // (a lane quantises segments its neighbours staged)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    const float t = amax / 127.f;
+    const float inv = t > 0.f ? 127.f / amax : 0.f;
+    float a2 = 0.f, b2 = 0.f;
+    for (int g = lane; g < nseg / 2; g += 64) {                // 16 k-values: fp16 groups 2 g, 2 g + 1 -> int8 group g
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (q < n_q) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const half8 h = __builtin_bit_cast(half8, sh_qrow[2 * g + hf]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float x = (float)h[j];
+                    const int qv = quant8(x, inv);
+                    const float y = t * (float)qv, r = x - y;
+                    a2 += r * r; b2 += y * y;
+                    w[2 * hf + (j >> 2)] |= ((unsigned)qv & 255u) << (8 * (j & 3));
+                }
+            }
+        }
+        const int c = g >> 2, sp = (g & 3) ^ ((q >> 2) & 3);
+        *(uint4 *)(q8 + ((size_t)c * bn * 4 + (size_t)q * 4 + sp) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { a2 += __shfl_xor(a2, o); b2 += __shfl_xor(b2, o); }
+    // (the same fp32 evaluation slack on the residual as in the seal: ||q|| <= ||q - t q8|| + ||t q8||)
+    const float ra = sqrtf(a2), rb = sqrtf(b2);
+    if (lane == 0)
+        ((float4 *)p.qc)[q] = q < n_q ? make_float4(t, (ra + (ra + rb) * 0x1p-22f) * 1.001f, rb * 1.001f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __global__ void pack_queries_frag_kernel(const uint4 *__restrict__ queries, int n_q, int nseg, char *__restrict__ q_frag)
@@ -345,33 +399,11 @@ int mips_launch_pack_queries_frag(const void *queries, int n_q, int dim, void *q
     return CHECK_LAUNCH();
 }
 
-int mips_launch_pack_queries(const void *queries, int n_q, int dim, int bn, void *q_tiled, float *qnorm,
-                             hipStream_t stream)
+int mips_launch_prepare(const PrepareParams &p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(pack_queries_kernel, dim3(bn), dim3(64), 0, stream, (const uint4 *)queries, n_q, dim / 8, bn, (char *)q_tiled,
-                       qnorm);
-    return CHECK_LAUNCH();
-}
-
-__global__ void init_kernel(float *tau, unsigned *count, unsigned *flags, int bn, int n_q, unsigned dense_count, uint4 *zero16, unsigned n_zero16)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < bn) {
-        tau[i] = -__builtin_inff();
-        count[i] = (i < n_q) ? dense_count : 0u;
-    }
-    if (i < n_q) flags[i] = 0u;
-    // the pair-progress counters of the persistent scan launches (mips_scan8.hip), zeroed here instead of by a memset of their own
-    for (unsigned j = (unsigned)i; j < n_zero16; j += gridDim.x * blockDim.x) zero16[j] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-int mips_launch_init(float *tau, unsigned *count, unsigned *flags, int bn, int n_q, unsigned dense_count, unsigned *zero, size_t n_zero,
-                     hipStream_t stream)
-{
-    if (n_zero & 3) return -1;
-    const int blocks = zero && n_zero ? 128 : (bn + 255) / 256;
-    hipLaunchKernelGGL(init_kernel, dim3(blocks < (bn + 255) / 256 ? (bn + 255) / 256 : blocks), dim3(256), 0, stream, tau, count, flags, bn, n_q, dense_count,
-                       (uint4 *)zero, (unsigned)(zero ? n_zero / 4 : 0));
+    if (p.tau && ((p.n_zero & 3) || ((uintptr_t)p.zero & 15) || (p.n_zero && !p.zero))) return -1;
+    if (p.q8_tiled && (p.dim % 16)) return -1;
+    hipLaunchKernelGGL(prepare_kernel, dim3(p.bn), dim3(64), p.q8_tiled ? (size_t)p.dim * 2 : 0, stream, p);
     return CHECK_LAUNCH();
 }
 
@@ -433,6 +465,8 @@ struct CandView {
     }
 };
 
+// (a block of NT threads, a multiple of 256: the stand-alone select has 256, finalize_kernel<2> FINISH_THREADS)
+template <int NT>
 __device__ __forceinline__ void select_block(SelectShared &sh, uint2 *cand_all, unsigned *count, uint2 *cand8, unsigned *count8, float *tau, unsigned *flags,
                                              unsigned capq, int kp, int q)
 {
@@ -457,7 +491,7 @@ __device__ __forceinline__ void select_block(SelectShared &sh, uint2 *cand_all, 
     if (any_sub && tid < 8) count8[tid * 512 + q] = 0;                // the next segment appends to empty sub-lists
     if (n <= (unsigned)kp) {
         if (any_sub) {                                                // fewer than kp candidates in all: move the sub-list entries behind the main ones
-            for (unsigned i = cv.n_main + tid; i < n; i += 256) cand[i] = cv.at(i);
+            for (unsigned i = cv.n_main + tid; i < n; i += NT) cand[i] = cv.at(i);
             if (tid == 0) count[q] = n;
         }
         return;
@@ -465,22 +499,22 @@ __device__ __forceinline__ void select_block(SelectShared &sh, uint2 *cand_all, 
     const bool staged = n <= SEL_LDS;
     if (staged) {
         // eight loads in flight per thread (one at a time, the 32 rounds of an 8,192-entry list each paid a full L2 latency)
-        for (unsigned i0 = tid; i0 < n; i0 += 8 * 256) {
+        for (unsigned i0 = tid; i0 < n; i0 += 8 * NT) {
             uint2 e[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const unsigned i = i0 + j * 256; e[j] = cv.at(i < n ? i : n - 1); }
+            for (int j = 0; j < 8; ++j) { const unsigned i = i0 + j * NT; e[j] = cv.at(i < n ? i : n - 1); }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const unsigned i = i0 + j * 256; if (i < n) sh.key[i] = cand_key(e[j]); }
+            for (int j = 0; j < 8; ++j) { const unsigned i = i0 + j * NT; if (i < n) sh.key[i] = cand_key(e[j]); }
         }
     }
     uint64_t prefix = 0, mask = 0;
     unsigned need = (unsigned)kp;
     for (int pass = 0; pass < 8; ++pass) {
         const int shift = 56 - 8 * pass;
-        sh.hist[tid] = 0;
+        if (NT == 256 || tid < 256) sh.hist[tid] = 0;
         __syncthreads();
         unsigned run_digit = 0xffffffffu, run = 0;
-        for (unsigned i = tid; i < n; i += 256) {
+        for (unsigned i = tid; i < n; i += NT) {
             const uint64_t k = staged ? sh.key[i] : cand_key(cv.at(i));
             if ((k & mask) == prefix) {
                 const unsigned d = (unsigned)(k >> shift) & 255u;
@@ -508,7 +542,7 @@ __device__ __forceinline__ void select_block(SelectShared &sh, uint2 *cand_all, 
     // prefix is now the kp-th largest key; keys are unique, so exactly kp keys are >= prefix
     if (tid == 0) sh.out = 0;
     __syncthreads();
-    for (unsigned i = tid; i < n; i += 256) {
+    for (unsigned i = tid; i < n; i += NT) {
         const uint64_t k = staged ? sh.key[i] : cand_key(cv.at(i));
         if (k >= prefix) {                                            // (a key is its entry: score bits from the ordered form, row from the low word)
             const unsigned s = atomicAdd(&sh.out, 1u);
@@ -526,7 +560,7 @@ __device__ __forceinline__ void select_block(SelectShared &sh, uint2 *cand_all, 
 __global__ void __launch_bounds__(256) select_kernel(uint2 *cand_all, unsigned *count, uint2 *cand8, unsigned *count8, float *tau, unsigned *flags, unsigned capq, int kp)
 {
     __shared__ SelectShared sh;
-    select_block(sh, cand_all, count, cand8, count8, tau, flags, capq, kp, blockIdx.x);
+    select_block<256>(sh, cand_all, count, cand8, count8, tau, flags, capq, kp, blockIdx.x);
 }
 
 int mips_launch_select(uint2 *cand, unsigned *count, uint2 *cand8, unsigned *count8, float *tau, unsigned *flags, unsigned capq, int kp, int n_q,
@@ -594,17 +628,60 @@ __device__ __forceinline__ void exact_dot_wave_x4(const char *e_tiled, const uns
     }
 }
 
-template <bool SELECT_FIRST>
-__global__ void __launch_bounds__(256) finalize_kernel(FinalizeParams p)
+// LEAD: what the block does before the exact re-score -- 0: nothing, the list is final; 1: the select behind the last scan segment; 2: the
+// deferred pass of the int8 segments, then that select (FINISH_THREADS threads: the pass is a gather of whole rows, 16 waves keep 64 of a
+// query's rows in flight, and two such blocks with their SelectShared fit a CU).
+#define FINISH_THREADS 1024
+template <int LEAD>
+__global__ void __launch_bounds__(LEAD == 2 ? FINISH_THREADS : 256) finalize_kernel(FinalizeParams p)
 {
+    constexpr int NT = LEAD == 2 ? FINISH_THREADS : 256, NW = NT / 64;
     __shared__ uint64_t fkey[128];
     __shared__ uint32_t sh_kth;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if constexpr (SELECT_FIRST) {
+    if constexpr (LEAD != 0) {
+        __shared__ SelectShared sel;
+        if constexpr (LEAD == 2) {
+            // The deferred pass: tau_q, from the select behind the last segment, is the tightest threshold the search will have.  A pending
+            // entry with U < tau_q is dropped unread -- its fp32 score is below tau_q like that of a row the scan pruned --, the others get
+            // their fp32 score and go behind the main list's kp entries (at most kp + PENDCAP < capq), where the select below finds them.
+            // All of the list's entries are loaded at once and the kept rows compacted into ONE work list (where the select stages its keys
+            // afterwards: PENDCAP words of its 64 KiB), so the gather runs without a barrier between its rows.
+            __shared__ unsigned sh_w[NW];
+            unsigned *const sh_row = (unsigned *)sel.key;
+            static_assert(PENDCAP * sizeof(unsigned) <= sizeof(sel.key) && PENDCAP % NT == 0, "the work list holds a whole pending list");
+            unsigned np = p.pcount[q];
+            if (np > PENDCAP) np = PENDCAP;
+            unsigned next = p.count[q];
+            if (next > p.capq) next = p.capq;
+            const float tq = p.tau[q];
+            const uint2 *const pq = p.pend + (size_t)q * PENDCAP;
+            uint2 *const main_list = (uint2 *)p.cand + (size_t)q * p.capq;
+            const unsigned capq = p.capq;
+            uint2 e[PENDCAP / NT];
+#pragma unroll
+            for (unsigned r = 0; r < PENDCAP / NT; ++r) { const unsigned i = r * NT + tid; e[r] = i < np ? pq[i] : make_uint2(0u, 0u); }
+            unsigned n_keep = 0;
+#pragma unroll
+            for (unsigned r = 0; r < PENDCAP / NT; ++r) {
+                if (r * NT >= np) break;                                      // (block-uniform)
+                const bool keep = r * NT + tid < np && !(__uint_as_float(e[r].x) < tq);
+                unsigned n_round;
+                const unsigned w = block_rank<NW>(keep, sh_w, n_round);
+                if (keep) sh_row[n_keep + w] = e[r].y;
+                n_keep += n_round;
+            }
+            __syncthreads();
+            rescore_worklist<NW>(p.e_tiled, (const uint4 *)p.queries + (size_t)q * (p.dim / 8), p.dim / 8, sh_row, n_keep,
+                                 [&](unsigned j) { return next + j < capq ? main_list + next + j : nullptr; });
+            next += n_keep;
+            if (tid == 0) ((unsigned *)p.count)[q] = next;
+            __threadfence_block();
+            __syncthreads();
+        }
         // the select that follows the LAST scan segment, run by the block that consumes its result (one launch less per search; the list, its
         // count and tau go through global memory as between two kernels: the fence orders them for this block's own reads below)
-        __shared__ SelectShared sel;
-        select_block(sel, (uint2 *)p.cand, (unsigned *)p.count, p.cand8, p.count8, (float *)p.tau, p.flags, p.capq, p.kp, q);
+        select_block<NT>(sel, (uint2 *)p.cand, (unsigned *)p.count, p.cand8, p.count8, (float *)p.tau, p.flags, p.capq, p.kp, q);
         __threadfence_block();
         __syncthreads();
     }
@@ -615,16 +692,16 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeParams p)
     const uint16_t *qrow = p.queries + (size_t)q * p.dim;
 
     if (nseg <= 128) {
-        for (unsigned j0 = wave; j0 < cnt; j0 += 16) {                        // this wave's candidates j0, j0 + 4, j0 + 8, j0 + 12 together
+        for (unsigned j0 = wave; j0 < cnt; j0 += 4 * NW) {                    // this wave's candidates j0, j0 + NW, j0 + 2 NW, j0 + 3 NW together
             unsigned rows[4];
             int nv = 0;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { const unsigned j = j0 + 4 * c; rows[c] = j < cnt ? cand[j].y : 0u; nv += j < cnt; }
+            for (int c = 0; c < 4; ++c) { const unsigned j = j0 + NW * c; rows[c] = j < cnt ? cand[j].y : 0u; nv += j < cnt; }
             int64_t lo[4], hi[4];
             exact_dot_wave_x4(p.e_tiled, rows, nv, qrow, nseg, lane, lo, hi);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const unsigned j = j0 + 4 * c;
+                const unsigned j = j0 + NW * c;
                 if (j < cnt && lane == 0) {
                     const uint32_t ord = p.f32 ? f32_order(fixed_to_float(lo[c], hi[c])) : h16_order(fixed_to_half(lo[c], hi[c]));
                     fkey[j] = ((uint64_t)ord << 32) | (uint64_t)(0xffffffffu - rows[c]);
@@ -632,7 +709,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeParams p)
             }
         }
     } else {
-        for (unsigned j = wave; j < cnt; j += 4) {
+        for (unsigned j = wave; j < cnt; j += NW) {
             const unsigned row = cand[j].y;
             int64_t lo, hi;
             exact_dot_wave(p.e_tiled, (int64_t)row, qrow, nseg, lane, lo, hi);
@@ -665,7 +742,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeParams p)
             if (rank == kk - 1) sh_kth = (uint32_t)(mine >> 32);
         }
     }
-    for (unsigned j = kk + tid; j < (unsigned)p.k; j += 256) { // shard holds fewer than k rows
+    for (unsigned j = kk + tid; j < (unsigned)p.k; j += NT) { // shard holds fewer than k rows
         const size_t o = (size_t)q * p.k + j;
         if (p.out_rec) { p.out_rec[o] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, p.f32 ? 0xff800000u : 0xfc00u); continue; }
         if (p.f32) ((float *)p.out_dist)[o] = -INFINITY; else ((uint16_t *)p.out_dist)[o] = 0xfc00;
@@ -689,8 +766,10 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeParams p)
 
 int mips_launch_finalize(const FinalizeParams &p, bool select_first, hipStream_t stream)
 {
-    if (select_first) hipLaunchKernelGGL(finalize_kernel<true>, dim3(p.n_q), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(finalize_kernel<false>, dim3(p.n_q), dim3(256), 0, stream, p);
+    if (p.pend && (!select_first || !p.pcount)) return -1;
+    if (p.pend) hipLaunchKernelGGL(finalize_kernel<2>, dim3(p.n_q), dim3(FINISH_THREADS), 0, stream, p);
+    else if (select_first) hipLaunchKernelGGL(finalize_kernel<1>, dim3(p.n_q), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(finalize_kernel<0>, dim3(p.n_q), dim3(256), 0, stream, p);
     return CHECK_LAUNCH();
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mips_device.h"
 
 #define CAPQ 16384u /* candidate slots per query (8 B each) */
 #define SUBCAP 1024u /* ... plus 8 sub-lists of this many per query, one per XCD, filled by the persistent scan (mips_scan8.hip) */
@@ -41,17 +42,14 @@ int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int
 // the same seal over a device list of blocks (a scattered row update): `grid` workgroups, workgroup i seals touched[i] if i < *n_touched
 int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, void *e8, float *blk,
                                  unsigned *nonfinite, hipStream_t stream);
-// int8 query image [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -}
-int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream);
 // mips_launch_scan8 on the shadow image: survivors carry their INTEGER sum in the score word until mips_launch_triage has run
 int mips_launch_scan8i(const ScanParams &p, const void *e8_tiled, const float *blk, const void *q8_tiled, const float *qc, int bn, int64_t row_begin,
                        int64_t row_end, int cus, unsigned *prog, hipStream_t stream);
 // the entries an int8 segment appended (sub-lists, and the main list from `pre` on): fp32 scores (fp16 products of the fp16 image) for those whose
-// estimate + margin * eps reaches tau; the others go to `pend` [n_q][PENDCAP] / `pcount` [n_q] (zeroed per search) with score word -inf
+// estimate + margin * eps reaches tau; the others go to `pend` [n_q][PENDCAP] / `pcount` [n_q] (zeroed per search) with score word -inf; the
+// finalize launch reads those whose bound still reaches the final tau (FinalizeParams::pend)
 int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, const float *blk, const float *qc, void *pend, unsigned *pcount,
                        float margin, hipStream_t stream);
-// after the select behind the last segment: pending entries whose bound still reaches tau get their fp32 score and join the main list
-int mips_launch_rescore_pending(const ScanParams &p, const void *queries, const void *pend, const unsigned *pcount, hipStream_t stream);
 // production filter scan, ping-pong wave schedule (mode 0 only)
 int mips_launch_scan_pp(int variant, int depth, const ScanParams &p, int grid, hipStream_t stream);
 // production filter scan for 512 queries, query operand streamed straight to registers (mode 0, variant 0 only)
@@ -81,11 +79,24 @@ int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t 
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
-// queries row-major fp16 [n_q, dim] -> chunk-tiled image for BN rows (zero padded) + ||q||_2 upper bounds
-int mips_launch_pack_queries(const void *queries, int n_q, int dim, int bn, void *q_tiled, float *qnorm,
-                             hipStream_t stream);
-int mips_launch_init(float *tau, unsigned *count, unsigned *flags, int bn, int n_q, unsigned dense_count, unsigned *zero, size_t n_zero,
-                     hipStream_t stream);
+// The start of a search, one launch that reads every query row once.  Always: queries row-major fp16 [n_q, dim] -> chunk-tiled image for `bn`
+// rows (zero padded) + ||q||_2 upper bounds.  With `tau`: thresholds -inf, counts (dense_count for the n_q real queries), flags 0 and `n_zero`
+// (a multiple of 4) zeroed uints at `zero` -- sub-list counts, pending counts, pair-progress counters.  With `q8_tiled`: the int8 query image
+// [dim / 64][bn * 64 B] + per query float4 {t_q, a_q, b_q, -} for mips_launch_scan8i.
+struct PrepareParams {
+    const void *queries;
+    int n_q, dim, bn;
+    void *q_tiled;
+    float *qnorm;
+    float *tau;              // nullptr: no thresholds / counts / flags / zeroing (emdr2_mips_debug_scores)
+    unsigned *count, *flags;
+    unsigned dense_count;
+    unsigned *zero;
+    size_t n_zero;
+    void *q8_tiled;          // nullptr: no int8 image
+    float *qc;
+};
+int mips_launch_prepare(const PrepareParams &p, hipStream_t stream);
 // keep the kp best candidates of every query (by (score desc,row asc)), publish tau = kp-th score
 int mips_launch_select(uint2 *cand, unsigned *count, uint2 *cand8, unsigned *count8, float *tau, unsigned *flags, unsigned capq, int kp, int n_q,
                        hipStream_t stream);
@@ -111,6 +122,8 @@ struct FinalizeParams {
     int f32;                 // 1: FaissMIPSIndex-style scores RNE_fp32(exact dot), order (fp32 score desc, row asc)
     uint4 *out_rec;          // non-null: ONE 16-byte record per (query, slot) instead of the three arrays -- {row lo, row hi, idx, score bits
                              // (fp16 in the low half, or fp32)} -- written straight into the all-gather send buffer of a sharded search
+    const uint2 *pend;       // non-null (with select_first): the deferred pass of the int8 segments runs first, in the same launch -- a pending
+    const unsigned *pcount;  // entry whose bound still reaches tau gets its fp32 score and joins the main list behind its kp entries
 };
 int mips_launch_finalize(const FinalizeParams &p, bool select_first, hipStream_t stream);      // select_first: run the select of the last scan segment in the same launch
 // k-way merge of [n_shards, n_q, k] per-shard canonical lists (f32: float scores, else fp16 bits); -4 = n_shards * k too large
@@ -129,3 +142,82 @@ int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const
                              hipStream_t stream);
 int mips_launch_exact_select(const void *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k, const int32_t *ids, int f32,
                              void *out_dist, int32_t *out_idx, int64_t *out_row, unsigned *flags, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
+// device code of the int8 segments that two files share: query quantisation (prepare_kernel in mips_aux.hip) and row quantisation (the seal
+// in mips_scan8i.hip), the fp32 re-score of survivors right behind a segment (triage_kernel there) and at the end of the search
+// (finalize_kernel<2> here)
+// ------------------------------------------------------------------------------------------------
+// the int8 value of x under the scale 1 / inv: index rows per 256-row block (seal_shadow_kernel), queries per query (prepare_kernel)
+__device__ __forceinline__ int quant8(float x, float inv)
+{
+    int v = (int)rintf(x * inv);
+    return v > 127 ? 127 : (v < -127 ? -127 : v);              // (|x| <= 127 / inv up to rounding: the clamp never bites, and D_b is measured on the stored value anyway)
+}
+
+// fp32 scores of four (row, query) pairs at a time: the sum of the exact fp16 products of a row of the fp16 image and the query, a lane's
+// segments in order, then the xor tree (any fp32 accumulation order satisfies the eps of DESIGN 3.3, so select, finalize and the proof run
+// unchanged -- but every caller forms THIS sum, so which of them scores a row never shows in a score word).  All four rows' loads go out
+// before the first is used; rows past n_valid repeat rows[0].
+__device__ __forceinline__ void rescore_wave_x4(const char *__restrict__ tiled, const unsigned (&rows)[4], const uint4 *__restrict__ qrow, int nseg, int lane,
+                                                float (&out)[4])
+{
+    const int nch = nseg >> 2;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int seg = lane; seg < nseg; seg += 64) {
+        uint4 ev[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ev[c] = *(const uint4 *)(tiled + tiled_seg_offset(rows[c], seg, nch));
+        const half8 qv = __builtin_bit_cast(half8, qrow[seg]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const half8 e = __builtin_bit_cast(half8, ev[c]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s[c] += (float)e[j] * (float)qv[j];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s[c] += __shfl_xor(s[c], o);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[c] = s[c];
+}
+
+// exclusive rank of the threads with `flag` among the block's NW waves, and their number (two barriers; `sh` is NW words)
+template <int NW>
+__device__ __forceinline__ unsigned block_rank(bool flag, unsigned *sh, unsigned &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
+    const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+    __syncthreads();                                           // (sh may still be read from the previous call)
+    if (lane == 0) sh[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { const unsigned v = sh[w]; off += w < wave ? v : 0u; tot += v; }
+    total = tot;
+    return off + before;
+}
+
+// the work list sh_row[0, n) of a block of NW waves: fp32 score words, four per wave at a time; entry j goes to dst(j) unless that is null
+template <int NW, class Dst>
+__device__ __forceinline__ void rescore_worklist(const char *__restrict__ tiled, const uint4 *__restrict__ qrow, int nseg, const unsigned *sh_row, unsigned n,
+                                                 const Dst &dst)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (unsigned j0 = 4 * wave; j0 < n; j0 += 4 * NW) {
+        unsigned rows[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) rows[c] = sh_row[j0 + c < n ? j0 + c : j0];
+        float sc[4];
+        rescore_wave_x4(tiled, rows, qrow, nseg, lane, sc);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (lane == 0 && j0 + c < n) {
+                uint2 *const d = dst(j0 + c);
+                if (d) *d = make_uint2(__float_as_uint(sc[c]), rows[c]);
+            }
+    }
+}

@@ -100,12 +100,6 @@ __device__ __forceinline__ float block_max_256(float v, float *sh)
     return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
-__device__ __forceinline__ int quant8(float x, float inv)
-{
-    int v = (int)rintf(x * inv);
-    return v > 127 ? 127 : (v < -127 ? -127 : v);              // (|x| <= 127 / inv up to rounding: the clamp never bites, and D_b is measured on the stored value anyway)
-}
-
 // One workgroup per 256-row block, one thread per row.  Pass 1: max |e| and max ||e_r||^2 of the block; pass 2 (the block is in L2 now):
 // quantise with the block's scale, write the int8 rows, measure ||e_r - s_b e8_r||.  Rows past the end of the shard are zero in the fp16
 // image and stay zero here.  Workgroup i seals block first_block + i and reads or writes nothing of any other block: a full seal is the range
@@ -169,120 +163,13 @@ __global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict
     if (threadIdx.x == 0) blk[block] = make_float4(s, nb, (sqrtf(d2) + nb * 0x1p-22f) * 1.001f, 0.f);
 }
 
-// int8 query image (chunk-tiled like the fp16 one, 64 k-values per chunk) + per query {t_q, a_q, b_q}; one wave per padded query row
-__global__ void pack_queries_i8_kernel(const uint4 *__restrict__ queries, int n_q, int nseg, int bn, char *__restrict__ q8, float4 *__restrict__ qc)
-{
-    const int q = blockIdx.x, lane = threadIdx.x;
-    float amax = 0.f;
-    if (q < n_q)
-        for (int seg = lane; seg < nseg; seg += 64) {
-            const half8 h = __builtin_bit_cast(half8, queries[(size_t)q * nseg + seg]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)h[j]));
-        }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    const float t = amax / 127.f;
-    const float inv = t > 0.f ? 127.f / amax : 0.f;
-    float a2 = 0.f, b2 = 0.f;
-    for (int g = lane; g < nseg / 2; g += 64) {
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-        if (q < n_q) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const half8 h = __builtin_bit_cast(half8, queries[(size_t)q * nseg + 2 * g + hf]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float x = (float)h[j];
-                    const int qv = quant8(x, inv);
-                    const float y = t * (float)qv, r = x - y;
-                    a2 += r * r; b2 += y * y;
-                    w[2 * hf + (j >> 2)] |= ((unsigned)qv & 255u) << (8 * (j & 3));
-                }
-            }
-        }
-        const int c = g >> 2, sp = (g & 3) ^ ((q >> 2) & 3);
-        *(uint4 *)(q8 + ((size_t)c * bn * 4 + (size_t)q * 4 + sp) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { a2 += __shfl_xor(a2, o); b2 += __shfl_xor(b2, o); }
-    // (the same fp32 evaluation slack on the residual as in the seal: ||q|| <= ||q - t q8|| + ||t q8||)
-    const float ra = sqrtf(a2), rb = sqrtf(b2);
-    if (lane == 0) qc[q] = q < n_q ? make_float4(t, (ra + (ra + rb) * 0x1p-22f) * 1.001f, rb * 1.001f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// fp32 scores of four (row, query) pairs at a time: the sum of the exact fp16 products of a row of the fp16 image and the query, a lane's
-// segments in order, then the xor tree (any fp32 accumulation order satisfies the eps of DESIGN 3.3, so select, finalize and the proof run
-// unchanged -- but both callers form THIS sum, so which of them scores a row never shows in a score word).  All four rows' loads go out
-// before the first is used; rows past n_valid repeat rows[0].
-__device__ __forceinline__ void rescore_wave_x4(const char *__restrict__ tiled, const unsigned (&rows)[4], const uint4 *__restrict__ qrow, int nseg, int lane,
-                                                float (&out)[4])
-{
-    const int nch = nseg >> 2;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int seg = lane; seg < nseg; seg += 64) {
-        uint4 ev[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ev[c] = *(const uint4 *)(tiled + tiled_seg_offset(rows[c], seg, nch));
-        const half8 qv = __builtin_bit_cast(half8, qrow[seg]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const half8 e = __builtin_bit_cast(half8, ev[c]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s[c] += (float)e[j] * (float)qv[j];
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s[c] += __shfl_xor(s[c], o);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) out[c] = s[c];
-}
-
-// exclusive rank of the threads with `flag` among the block's 256 threads, and their number (two barriers; `sh` is 4 words)
-__device__ __forceinline__ unsigned block_rank_256(bool flag, unsigned *sh, unsigned &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
-    const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-    __syncthreads();                                           // (sh may still be read from the previous call)
-    if (lane == 0) sh[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const unsigned v = sh[w]; off += w < wave ? v : 0u; tot += v; }
-    total = tot;
-    return off + before;
-}
-
-// the block's work list sh_row[0, n) (entry sh_idx[j] of `dst`): fp32 score words, four per wave at a time
-__device__ __forceinline__ void rescore_worklist(const char *__restrict__ tiled, const uint4 *__restrict__ qrow, int nseg, const unsigned *sh_row,
-                                                 const unsigned *sh_idx, unsigned n, uint2 *dst, unsigned dst_end)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (unsigned j0 = 4 * wave; j0 < n; j0 += 16) {
-        unsigned rows[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) rows[c] = sh_row[j0 + c < n ? j0 + c : j0];
-        float sc[4];
-        rescore_wave_x4(tiled, rows, qrow, nseg, lane, sc);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (lane == 0 && j0 + c < n) {
-                const unsigned i = sh_idx[j0 + c];
-                if (i < dst_end) dst[i] = make_uint2(__float_as_uint(sc[c]), rows[c]);
-            }
-    }
-}
-
 // Triage of what one int8 segment appended.  New entries of query q: the eight sub-lists up to min(count8, SUBCAP) and the main list from `pre`
 // to min(count, capq); the entries below `pre` were kept by the select before the segment and keep their scores bit for bit.  `pre` is kp: an
 // int8 segment always follows a select over at least the dense segment's rows, which leaves exactly kp entries.  With est = t_q s_b I:
 //   est + margin eps >= tau_q (the tau the segment was scanned with): a likely winner.  Its score word becomes the fp32 score, in place, so the
 //     select that follows raises tau over the rows that matter;
 //   otherwise: (U, row) goes to the query's pending list and the score word becomes -inf, which the select ranks below the kp finite entries
-//     the main list holds.  mips_launch_rescore_pending reads the row at the end of the search only if U still reaches the final tau;
+//     the main list holds.  finalize_kernel<2> (mips_aux.hip) reads the row at the end of the search only if U still reaches the final tau;
 //   the pending list is full: re-scored in place like a likely winner.  Nothing is ever dropped here and no flag is raised.
 // `margin` decides only who is read now and who (perhaps) later.  grid (9 lists, n_q); a block reserves its pending slots with ONE atomic.
 __global__ void __launch_bounds__(256) triage_kernel(const char *__restrict__ tiled, const uint4 *__restrict__ queries, int nseg, uint2 *cand,
@@ -340,7 +227,7 @@ __global__ void __launch_bounds__(256) triage_kernel(const char *__restrict__ ti
         if (i < hi) deferred(i, e, u);
         const bool def = (sh_def[((i0 - lo) >> 6) + (tid >> 6)] >> (tid & 63)) & 1ull;
         unsigned n_def;
-        const unsigned slot = next + block_rank_256(def, sh4, n_def);
+        const unsigned slot = next + block_rank<4>(def, sh4, n_def);
         next += n_def;
         const bool parked = def && slot < PENDCAP;
         if (parked) {
@@ -348,44 +235,10 @@ __global__ void __launch_bounds__(256) triage_kernel(const char *__restrict__ ti
             ent[i].x = 0xff800000u;
         }
         unsigned n_now;
-        const unsigned w = block_rank_256(i < hi && !parked, sh4, n_now);
+        const unsigned w = block_rank<4>(i < hi && !parked, sh4, n_now);
         if (i < hi && !parked) { sh_row[w] = e.y; sh_idx[w] = i; }
         __syncthreads();
-        rescore_worklist(tiled, qrow, nseg, sh_row, sh_idx, n_now, ent, hi);
-    }
-}
-
-// The deferred pass, after the select that follows the last segment: tau_q is the tightest threshold the search will have.  A pending entry
-// with U < tau_q is dropped unread -- its fp32 score is below tau_q like that of a row the scan pruned --, the others get their fp32 score and
-// go behind the main list's kp entries (at most kp + PENDCAP < capq), where the final select finds them.  grid (slices, n_q): a query's list
-// is cut into equal slices.
-__global__ void __launch_bounds__(256) rescore_pending_kernel(const char *__restrict__ tiled, const uint4 *__restrict__ queries, int nseg, uint2 *cand,
-                                                              unsigned *count, unsigned capq, const float *__restrict__ tau, const uint2 *__restrict__ pend,
-                                                              const unsigned *__restrict__ pcount)
-{
-    __shared__ unsigned sh4[4], sh_base, sh_row[256], sh_idx[256];
-    const int q = blockIdx.y, tid = threadIdx.x;
-    unsigned np = pcount[q];
-    if (np > PENDCAP) np = PENDCAP;
-    const unsigned lo = (unsigned)((uint64_t)np * blockIdx.x / gridDim.x), hi = (unsigned)((uint64_t)np * (blockIdx.x + 1) / gridDim.x);
-    if (lo >= hi) return;
-    const float tq = tau[q];
-    const uint2 *const pq = pend + (size_t)q * PENDCAP;
-    const uint4 *qrow = queries + (size_t)q * nseg;
-    uint2 *const main_list = cand + (size_t)q * capq;
-    for (unsigned i0 = lo; i0 < hi; i0 += 256) {
-        const unsigned i = i0 + tid;
-        const uint2 e = i < hi ? pq[i] : make_uint2(0u, 0u);
-        const bool keep = i < hi && !(__uint_as_float(e.x) < tq);
-        unsigned n_keep;
-        const unsigned w = block_rank_256(keep, sh4, n_keep);
-        if (n_keep == 0) continue;                             // (block-uniform)
-        if (tid == 0) sh_base = atomicAdd(&count[q], n_keep);
-        if (keep) sh_row[w] = e.y;
-        __syncthreads();
-        if (keep) sh_idx[w] = sh_base + w;
-        __syncthreads();
-        rescore_worklist(tiled, qrow, nseg, sh_row, sh_idx, n_keep, main_list, capq);
+        rescore_worklist<4>(tiled, qrow, nseg, sh_row, n_now, [&](unsigned j) { const unsigned i = sh_idx[j]; return i < hi ? ent + i : nullptr; });
     }
 }
 
@@ -409,24 +262,11 @@ int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *tou
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int mips_launch_pack_queries_i8(const void *queries, int n_q, int dim, int bn, void *q8_tiled, float *qc, hipStream_t stream)
-{
-    hipLaunchKernelGGL(pack_queries_i8_kernel, dim3(bn), dim3(64), 0, stream, (const uint4 *)queries, n_q, dim / 8, bn, (char *)q8_tiled, (float4 *)qc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, const float *blk, const float *qc, void *pend, unsigned *pcount,
                        float margin, hipStream_t stream)
 {
     hipLaunchKernelGGL(triage_kernel, dim3(9, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count, p.cand8,
                        p.count8, p.capq, pre, (const float4 *)blk, (const float4 *)qc, p.tau, (uint2 *)pend, pcount, margin);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int mips_launch_rescore_pending(const ScanParams &p, const void *queries, const void *pend, const unsigned *pcount, hipStream_t stream)
-{
-    hipLaunchKernelGGL(rescore_pending_kernel, dim3(8, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count,
-                       p.capq, p.tau, (const uint2 *)pend, pcount);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -40,7 +40,7 @@ for f in glob.glob(out + "/*/*kernel_trace.csv"):
     for r in csv.DictReader(open(f)):
         recs.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
 recs.sort()
-starts = [i for i, r in enumerate(recs) if "pack_queries_kernel" in r[2]]      # (not pack_queries_i8_kernel, the second launch of a search)
+starts = [i for i, r in enumerate(recs) if "prepare_kernel" in r[2]]           # the first launch of a search
 last = recs[starts[-1]:]
 t0, prev_end = last[0][0], last[0][0]
 print("one search: %s rows, %s queries, top-%s%s" % (rows, nq, k, " (fp16 only)" if mode == ["fp16"] else ""))
