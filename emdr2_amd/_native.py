@@ -14,6 +14,14 @@ EMDR2_ABI_VERSION = 4
 FLAG_AMBIGUOUS = 1
 FLAG_OVERFLOW = 2
 MAX_TOPK = 120
+AUDIT_WORDS = 16
+# the report of emdr2_mips_audit, in word order (include/emdr2_mips.h); words 14 and 15 are reserved
+AUDIT_NAMES = ("rows_checked", "pad_rows_nonzero", "nonfinite_rows", "rows_over_emax", "block_norm_low", "block_norm_noncanonical",
+               "emax_noncanonical", "shadow_pad_rows_nonzero", "shadow_norm_low", "shadow_resid_low", "shadow_rows_noncanonical",
+               "shadow_table_noncanonical", "first_bad_row", "first_bad_block")
+AUDIT_SOUND_WORDS = (1, 2, 3, 4, 7, 8, 9)           # a non-zero count: a search result may be wrong (word 2 only while a shadow is in use)
+AUDIT_CANONICAL_WORDS = (5, 6, 10, 11)              # a non-zero count: the image is not byte for byte a fresh build
+AUDIT_NONE = (1 << 64) - 1                          # first_bad_row / first_bad_block: no offender
 
 _ERRORS = {-1: "bad argument", -2: "workspace too small", -3: "HIP launch/runtime error", -4: "unsupported shape"}
 
@@ -49,6 +57,7 @@ SIGNATURES = {
     "emdr2_mips_update_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_scatter_workspace_bytes": (_i32, [_i64, _i64, ctypes.POINTER(_sz)]),
     "emdr2_mips_update_rows_scattered": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "emdr2_mips_audit": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_debug_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "emdr2_mips_set_timing": (_i32, [_i32]),
     "emdr2_mips_timing_collect": (_i32, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i64), _i32, ctypes.POINTER(_i32)]),

@@ -145,6 +145,13 @@ def get_parser():
                         'change between swaps, so a resumed run searches exactly what the uninterrupted run searched at that step; the '
                         'refresher\'s in-flight pass is not saved and restarts.  With --index-refresh-in-place the snapshot is a mix of '
                         'embedding generations, as the live index is, and the pass cursor is not saved')
+    g.add_argument('--audit-index-interval', type=int, default=0,
+                   help='(not in the reference) N > 0: audit the evidence index in HBM (DistributedBruteForceIndex.audit: the premises of '
+                        'the search\'s exactness proof and the "byte for byte a fresh build" contract, one streaming pass over the live '
+                        'images) once before the first step and at every iteration divisible by N, at the step boundary after the index '
+                        'swap and the write-back and before the snapshot writer reads the image.  Rank 0 prints one line per audit; a '
+                        'failing audit raises RuntimeError on every rank.  Two small all-reduces per audit when the index is sharded, at '
+                        'iterations that depend on N alone.  0: off, nothing changes')
     g.add_argument('--indexer-batch-size', type=int, default=128)
     g.add_argument('--indexer-log-interval', type=int, default=1000)
     g.add_argument('--report-topk-accuracies', nargs='+', type=int, default=[])
@@ -179,6 +186,8 @@ def parse_args(argv=None):
     if args.index_writeback and args.async_indexer and not args.index_refresh_in_place:
         raise ValueError("--index-writeback with --async-indexer needs --index-refresh-in-place (in swap mode a refresh is always in progress: "
                          "the index refuses in-place updates, and the next swap would discard them anyway)")
+    if args.audit_index_interval < 0:
+        raise ValueError("--audit-index-interval must be >= 0")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

@@ -437,6 +437,17 @@ int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids
     return EMDR2_OK;
 }
 
+int emdr2_mips_audit(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const float *block_norm_sq,
+                     const void *shadow, const void *table, uint64_t *report, emdr2_stream_t stream)
+{
+    if (!tiled || !emax_sq || !report || ((uintptr_t)report & 7) || row_base < 0 || bad_shape(n_rows, dim)) return EMDR2_E_BADARG;
+    if ((shadow == nullptr) != (table == nullptr)) return EMDR2_E_BADARG;
+    if (shadow && (((uintptr_t)table & 15) || (dim % 256) != 0)) return EMDR2_E_BADARG;
+    const AuditParams p = {(const char *)tiled, (const char *)shadow, (const float4 *)table, block_norm_sq, emax_sq, (unsigned long long *)report,
+                           n_rows, row_base, (n_rows + 255) / 256, dim / 32};
+    return mips_launch_audit(p, (hipStream_t)stream);
+}
+
 int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const void *shadow,
                              const void *table, int64_t shadow_min_rows, const void *queries, int n_q, int k, const int32_t *ids, int f32,
                              void *out_dist, int32_t *out_idx, int64_t *out_row, void *out_records, uint32_t *out_flags, void *workspace,

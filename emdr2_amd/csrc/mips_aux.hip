@@ -2,6 +2,7 @@
 // candidate selection, exact integer re-scoring + validity proof, shard merge, all-exact fallback.
 #include "mips_device.h"
 #include "mips_kernels.h"
+#include "mips_derived.h"
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
 
@@ -19,36 +20,7 @@ __global__ void pack_rows_kernel(const uint4 *__restrict__ rows_rm, int64_t n_ch
     *(uint4 *)(tiled + tiled_seg_offset(row_offset + r, seg, nseg >> 2)) = rows_rm[i];
 }
 
-// ||E[r]||^2 of one row by one wave, the same value in every lane: lane l takes the 8-element groups l, l + 64, ... in order, then a
-// butterfly over the lanes.  emax_sq of a freshly packed shard (row_norm_max_kernel, row-major rows) and of a shard updated in place
-// (block_norms_kernel, rows read back from the tiled image) must agree bit for bit -- the search's validity bound reads it -- so both
-// kernels go through this one routine and differ only in where a group comes from.  Whether the compiler contracts `s += x * x` into an
-// fma in one instance and not in the other cannot matter: the square of an fp16 value has at most 22 significant bits and is exact in
-// fp32, so the fma and the multiply-then-add round the same sum.
-struct RowMajorRow {
-    const uint4 *row;                                           // rows_rm + r * nseg
-    __device__ __forceinline__ uint4 operator()(int seg) const { return row[seg]; }
-};
-struct TiledRow {
-    const char *tiled;
-    int64_t row;
-    int nch;
-    __device__ __forceinline__ uint4 operator()(int seg) const { return *(const uint4 *)(tiled + tiled_seg_offset(row, seg, nch)); }
-};
-template <class Load>
-__device__ __forceinline__ float row_norm_sq_wave(const Load &load, int nseg, int lane)
-{
-    float s = 0.f;
-    for (int seg = lane; seg < nseg; seg += 64) {
-        const half8 h = __builtin_bit_cast(half8, load(seg));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float x = (float)h[j]; s += x * x; }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
+// (||E[r]||^2 of a row by a wave, row_norm_sq_wave, and the block routine behind block_norms_kernel: mips_derived.h)
 __global__ void row_norm_max_kernel(const uint4 *__restrict__ rows_rm, int64_t n_chunk, int nseg, float *emax_sq)
 {
     const int lane = threadIdx.x & 63;
@@ -66,15 +38,10 @@ template <class Blocks>
 __global__ void __launch_bounds__(256) block_norms_kernel(const char *__restrict__ tiled, int nseg, Blocks blocks, float *__restrict__ block_norm_sq)
 {
     __shared__ float sh[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int64_t block;
     if (!blocks.get(block)) return;
-    float best = 0.f;
-#pragma unroll 4                                                 // (four rows' loads in flight; each row's own arithmetic is untouched)
-    for (int i = 0; i < 64; ++i) best = fmaxf(best, row_norm_sq_wave(TiledRow{tiled, block * 256 + wave * 64 + i, nseg >> 2}, nseg, lane));
-    if (lane == 0) sh[wave] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) block_norm_sq[block] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    StoreBlockNorm sink{block_norm_sq};
+    block_norm_256(tiled, nseg, block, sh, sink);
 }
 
 // *emax_sq = max of the whole table (one workgroup: 82,092 entries at the full index), so the bound can FALL when the row that held the

@@ -79,6 +79,17 @@ int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t 
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
+// index audit (mips_audit.hip): the report of emdr2_mips_audit for the padded image of n_rows rows; e8 / table null: no shadow;
+// sealed_blocks = ceil(n_rows / 256), the blocks a seal covers; block_norm_sq may be null
+struct AuditParams {
+    const char *tiled, *e8;
+    const float4 *table;
+    const float *block_norm_sq, *emax_sq;
+    unsigned long long *report;
+    int64_t n_rows, row_base, sealed_blocks;
+    int nch;
+};
+int mips_launch_audit(const AuditParams &p, hipStream_t stream);
 // The start of a search, one launch that reads every query row once.  Always: queries row-major fp16 [n_q, dim] -> chunk-tiled image for `bn`
 // rows (zero padded) + ||q||_2 upper bounds.  With `tau`: thresholds -inf, counts (dense_count for the n_q real queries), flags 0 and `n_zero`
 // (a multiple of 4) zeroed uints at `zero` -- sub-list counts, pending counts, pair-progress counters.  With `q8_tiled`: the int8 query image

@@ -17,6 +17,7 @@
 // kernel's: half the K-tiles per item, half the bytes per MAC at every level.  A survivor's score word holds the INTEGER sum until
 // mips_launch_triage has run.
 #include "mips_scan8.h"
+#include "mips_derived.h"
 
 namespace {
 
@@ -90,21 +91,10 @@ struct Scan8Int8 {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-__device__ __forceinline__ float block_max_256(float v, float *sh)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();                                           // (sh may still be read from the previous reduction)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-
-// One workgroup per 256-row block, one thread per row.  Pass 1: max |e| and max ||e_r||^2 of the block; pass 2 (the block is in L2 now):
-// quantise with the block's scale, write the int8 rows, measure ||e_r - s_b e8_r||.  Rows past the end of the shard are zero in the fp16
-// image and stay zero here.  Workgroup i seals block first_block + i and reads or writes nothing of any other block: a full seal is the range
-// [0, n_blocks), an in-place row update re-seals the blocks it touched with the very same code: a range (emdr2_mips_update_rows) or the
-// touched-block list of a scattered update (emdr2_mips_update_rows_scattered), see BlockRange / BlockList in mips_device.h.
+// One workgroup per 256-row block, one thread per row; the seal itself is seal_block_256 (mips_derived.h), here with the storing sink.
+// Workgroup i seals block first_block + i and reads or writes nothing of any other block: a full seal is the range [0, n_blocks), an
+// in-place row update re-seals the blocks it touched with the very same code: a range (emdr2_mips_update_rows) or the touched-block list
+// of a scattered update (emdr2_mips_update_rows_scattered), see BlockRange / BlockList in mips_device.h.
 template <class Blocks>
 __global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict__ tiled, int nch, Blocks blocks, char *__restrict__ e8,
                                                           float4 *__restrict__ blk, unsigned *__restrict__ nonfinite)
@@ -112,55 +102,8 @@ __global__ void __launch_bounds__(256) seal_shadow_kernel(const char *__restrict
     __shared__ float sh[4];
     int64_t block;
     if (!blocks.get(block)) return;
-    const int64_t row = block * 256 + threadIdx.x;
-    const int nseg = nch * 4;
-    float amax = 0.f, n2 = 0.f;
-    bool bad = false;
-    for (int seg = 0; seg < nseg; ++seg) {
-        const uint4 v = *(const uint4 *)(tiled + tiled_seg_offset(row, seg, nch));
-        const half8 h = __builtin_bit_cast(half8, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = (float)h[j];
-            bad |= !(fabsf(x) <= 65504.f);
-            amax = fmaxf(amax, fabsf(x));
-            n2 += x * x;
-        }
-    }
-    if (bad) atomicOr(nonfinite, 1u);
-    amax = block_max_256(amax, sh);
-    n2 = block_max_256(n2, sh);
-    const float s = amax / 127.f;
-    const float inv = s > 0.f ? 127.f / amax : 0.f;
-    float d2 = 0.f;
-    const int nch8 = nch >> 1;
-    for (int g = 0; g < nseg / 2; ++g) {                       // 16 k-values: fp16 groups 2 g, 2 g + 1 -> int8 group g
-        unsigned w[4];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            const uint4 v = *(const uint4 *)(tiled + tiled_seg_offset(row, 2 * g + hf, nch));
-            const half8 h = __builtin_bit_cast(half8, v);
-#pragma unroll
-            for (int j = 0; j < 8; j += 4) {
-                unsigned pk = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const float x = (float)h[j + b];
-                    const int qv = quant8(x, inv);
-                    const float r = x - s * (float)qv;
-                    d2 += r * r;
-                    pk |= ((unsigned)qv & 255u) << (8 * b);
-                }
-                w[2 * hf + (j >> 2)] = pk;
-            }
-        }
-        *(uint4 *)(e8 + tiled_seg_offset(row, g, nch8)) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    d2 = block_max_256(d2, sh);
-    // the residual e - s e8 was evaluated in fp32: each element is off by up to 2^-24 |s e8| + 2^-24 |e - s e8|, which matters exactly when the
-    // quantisation is (nearly) exact -- ternary rows have d2 = 0 while 127 * fl(1 / 127) is not 1.  2^-22 N_b covers it.
-    const float nb = sqrtf(n2) * 1.001f;
-    if (threadIdx.x == 0) blk[block] = make_float4(s, nb, (sqrtf(d2) + nb * 0x1p-22f) * 1.001f, 0.f);
+    StoreSeal sink{e8, blk, nonfinite};
+    seal_block_256(tiled, nch, block, sh, sink);
 }
 
 // Triage of what one int8 segment appended.  New entries of query q: the eight sub-lists up to min(count8, SUBCAP) and the main list from `pre`

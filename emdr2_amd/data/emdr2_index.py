@@ -381,6 +381,33 @@ def resolve_duplicate_rows(row_ids):
     return torch.empty_like(row_ids).scatter_(0, order, torch.where(loses, torch.full_like(s, -1), s))
 
 
+def audit_result(words, shadow_in_use, nonfinite_under_shadow=None):
+    """The dict `HipIndexShard.audit` / `DistributedBruteForceIndex.audit` return, from the 14 named report words of emdr2_mips_audit
+    (Python ints, the first-offender words as unsigned: 2**64 - 1 = none).  `sound`: no premise of the search's proof is violated (words
+    1-4 and 7-9 are zero, and no shard searches through its shadow while it holds an inf / NaN); `canonical`: every derived structure is
+    bit for bit a fresh build (words 5, 6, 10, 11 are zero)."""
+    out = dict(zip(_native.AUDIT_NAMES, (int(w) for w in words)))
+    if nonfinite_under_shadow is None:
+        nonfinite_under_shadow = bool(shadow_in_use) and out["nonfinite_rows"] > 0
+    out["sound"] = all(words[i] == 0 for i in _native.AUDIT_SOUND_WORDS if i != 2) and not nonfinite_under_shadow
+    out["canonical"] = all(words[i] == 0 for i in _native.AUDIT_CANONICAL_WORDS)
+    out["shadow_in_use"] = bool(shadow_in_use)
+    return out
+
+
+def audit_failures(result):
+    """One line naming the non-zero counters of an audit result and its first offenders ('' for a sound and canonical one)."""
+    if result["sound"] and result["canonical"]:
+        return ""
+    parts = ["%s=%d" % (n, result[n]) for n in _native.AUDIT_NAMES[1:12] if result[n]]
+    if result["nonfinite_rows"] and result["shadow_in_use"]:
+        parts.append("(non-finite rows under a shadow in use)")
+    for n in ("first_bad_row", "first_bad_block"):
+        if result[n] != _native.AUDIT_NONE:
+            parts.append("%s=%d" % (n, result[n]))
+    return ", ".join(parts)
+
+
 class HipIndexShard(object):
     """One contiguous row shard resident in this process's GPU, stripe-tiled for the HIP scan.
 
@@ -702,6 +729,23 @@ class HipIndexShard(object):
                                                           out.data_ptr(), _native.stream_ptr()), "gather_rows")
         return out
 
+    # -- audit: the premises of the search's proof, re-checked on the live image (emdr2_mips_audit) -------------------
+    def audit(self):
+        """One streaming pass over the image this shard is SEARCHING (between `begin_refresh` and `commit_refresh` that is the old image,
+        not the spare), its int8 shadow when one is in use, `emax_sq` and -- if an in-place update has built it -- the block-norm table;
+        enqueued on the current stream and ordered like a search, then ONE host read of the 128-byte report.  -> dict of the named report
+        words (include/emdr2_mips.h) plus `sound`, `canonical`, `shadow_in_use` (`audit_result`).  Nothing is built and nothing repaired."""
+        if self._filled != self.n_rows:
+            raise RuntimeError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
+        report = torch.empty(_native.AUDIT_WORDS, dtype=torch.int64, device=self.device)
+        shadow, norms = self._shadow, self._block_norms
+        _native.check(self.lib.emdr2_mips_audit(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base, self.emax_sq.data_ptr(),
+                                                None if norms is None else norms.data_ptr(), None if shadow is None else shadow[0].data_ptr(),
+                                                None if shadow is None else shadow[1].data_ptr(), report.data_ptr(), _native.stream_ptr()),
+                      "mips_audit")
+        words = [w & _native.AUDIT_NONE for w in report.tolist()]
+        return audit_result(words[:len(_native.AUDIT_NAMES)], shadow is not None)
+
     # -- snapshots: the way out of HBM (emdr2_mips_export_rows / _digest_rows) ---------------------------------------------------------
     def _check_range(self, local_row, n):
         if self._filled != self.n_rows:
@@ -881,6 +925,32 @@ class DistributedBruteForceIndex(object):
             flat = FlatEmbeddingFile(flat)
         self.add_arrays(flat.ids, flat.rows)
 
+    # -- audit (HipIndexShard.audit over every rank's shard) -----------------------------------------------------------------------------
+    def audit(self):
+        """Every rank audits its own shard; ONE int64 all_reduce(SUM) of the counters (and of how many shards use their shadow, and how
+        many of those hold a non-finite row), ONE all_reduce(MIN) of the two first-offender words -> the same dict on every rank
+        (`audit_result`; `first_bad_row` is a global row, `first_bad_block` the smallest offending block number local to its shard).  The
+        collective sequence does not depend on what the audit finds."""
+        if self.shard is None:
+            raise RuntimeError("MIPS Index is not initialized")
+        mine = self.shard.audit()
+        rank, world = self._world()
+        if world == 1:
+            return mine
+        dist = torch.distributed
+        on_device = dist.get_backend(self.process_group) == "nccl"
+        place = (lambda t: t.to(self.shard.device)) if on_device else (lambda t: t)
+        bad_nf = mine["shadow_in_use"] and mine["nonfinite_rows"] > 0
+        counts = place(torch.tensor([mine[n] for n in _native.AUDIT_NAMES[:12]] + [int(mine["shadow_in_use"]), int(bad_nf)], dtype=torch.int64))
+        # (unsigned words through a signed reduction: 2**64 - 1, "none", travels as the largest int64)
+        none = (1 << 63) - 1
+        first = place(torch.tensor([min(mine[n], none) for n in ("first_bad_row", "first_bad_block")], dtype=torch.int64))
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.process_group)
+        dist.all_reduce(first, op=dist.ReduceOp.MIN, group=self.process_group)
+        counts, first = counts.tolist(), first.tolist()
+        words = counts[:12] + [_native.AUDIT_NONE if f == none else f for f in first]
+        return audit_result(words, counts[12] > 0, counts[13] > 0)
+
     # -- snapshots (data/index_snapshot.py) ----------------------------------------------------------------------------------------------
     def save_flat_file(self, path, meta=None):
         """Write the index as it stands in HBM to the `FlatEmbeddingFile` `path` plus `path + '.meta'` (JSON: format, n, dim, world, the
@@ -892,10 +962,11 @@ class DistributedBruteForceIndex(object):
         writer.begin(path, meta)
         writer.finish()
 
-    def load_flat_snapshot(self, path):
+    def load_flat_snapshot(self, path, audit=False):
         """Build the index from a snapshot written by `save_flat_file` at ANY world size and verify it: meta against the file's header
         and ids, then the device digest of what now stands in HBM (combined over the ranks) against the meta's.  A mismatch raises
-        ValueError.  Returns the meta."""
+        ValueError.  `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
+        ValueError naming the non-zero words unless it is sound and canonical.  Returns the meta."""
         from emdr2_amd.data import index_snapshot as snap
         meta = snap.read_snapshot_meta(path)
         flat = FlatEmbeddingFile(path)
@@ -908,6 +979,10 @@ class DistributedBruteForceIndex(object):
         want = (int(meta["digest_sum"], 16), int(meta["digest_xor"], 16))
         if got != want:
             raise ValueError("index snapshot %s: digest %016x %016x in HBM, %016x %016x in the meta" % ((path,) + got + want))
+        if audit:
+            bad = audit_failures(self.audit())
+            if bad:
+                raise ValueError("index snapshot %s: the index audit failed: %s" % (path, bad))
         return meta
 
     def add_arrays(self, ids, rows):

@@ -231,6 +231,32 @@ def index_writeback(model, batch_size, topk):
     retriever.mips_index.update_rows_at(rows, embeds)
 
 
+def audit_index(index, iteration):
+    """--audit-index-interval: one audit of the evidence index (`DistributedBruteForceIndex.audit`: every rank its own shard, the counters
+    reduced over the index's group, so every rank holds the same result and takes the same decision).  Rank 0 prints one line; an index
+    that is not sound and canonical raises RuntimeError on every rank, naming the non-zero report words and the first offender."""
+    from emdr2_amd.data.emdr2_index import audit_failures
+    torch.cuda.synchronize()
+    t0 = time.time()
+    result = index.audit()                                      # (ends with its one host read: the time below is the audit's)
+    ms = (time.time() - t0) * 1000.0
+    bad = audit_failures(result)
+    if bad:
+        print_rank_0("index audit at iteration %d: %d rows, FAILED: %s (%.2f ms)" % (iteration, result["rows_checked"], bad, ms))
+        raise RuntimeError("index audit failed at iteration %d: %s" % (iteration, bad))
+    print_rank_0("index audit at iteration %d: %d rows, sound, canonical (%.2f ms)" % (iteration, result["rows_checked"], ms))
+    return result
+
+
+def maybe_audit_index(index, iteration, interval):
+    """The step-boundary rule of --audit-index-interval: audit at every iteration divisible by `interval`; 0 = never.  Whether a boundary
+    audits -- and so issues the audit's collectives -- depends on the iteration number alone.  -> whether it did."""
+    if interval <= 0 or iteration % interval:
+        return False
+    audit_index(index, iteration)
+    return True
+
+
 def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_of_epoch_callback, end_of_epoch_callback2, eos_id, indexer=None):
     """train_e2eqa.py:413-552.  `indexer`: an AsyncIndexBuilder when --async-indexer (re-indexing on a side stream; the swap at a step
     boundary replaces the NEW_INDEX_READY / NEW_CHKPT_READY handshake and the reload from disk)."""
@@ -258,6 +284,10 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
         snapshots = indexer.snapshot_writer = IndexSnapshotWriter(
             indexer.index, chunk_rows=IndexSnapshotWriter.paced_chunk_rows(hi - lo, args.index_reload_interval), log=print_rank_0)
         snapshot_path = os.path.join(args.save, SNAPSHOT_NAME)
+    audit_interval = int(getattr(args, "audit_index_interval", 0) or 0)
+    audited = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if audit_interval > 0 else None
+    if audited is not None:
+        audit_index(audited, args.iteration)          # what was loaded or restored, before the first step searches it
     start_epoch = args.iteration // args.train_iters_per_epoch
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
@@ -286,6 +316,9 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
             if getattr(args, "index_writeback", False):
                 # after the refresher's rows of this boundary (they come from an older snapshot of the weights): the write-back goes last and wins
                 index_writeback(model, args.batch_size, args.topk_retrievals)
+            if audited is not None:
+                # after everything that writes the live image at this boundary, before the snapshot writer exports from it
+                maybe_audit_index(audited, iteration, audit_interval)
             if snapshots is not None:
                 snapshots.pump()
                 snapshots.maybe_finalize(iteration)

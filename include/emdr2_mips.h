@@ -16,6 +16,7 @@
  *   emdr2_mips_unpack_rows    inverse of pack_rows (reconstruct / store export)
  *   emdr2_mips_gather_rows    the same by GLOBAL row, zero rows outside the shard (search_and_reconstruct over a sharded index;
  *                             the retrieved passages' embeddings for --context-embeddings-from-index)
+ *   emdr2_mips_audit          no counterpart in the reference: re-checks, on the image in HBM, the stored bounds the search's proof rests on
  *
  * Conventions: raw device pointers + sizes + hipStream_t; the caller (torch) owns every buffer;
  * nothing is allocated inside; every function returns 0 on success or a negative EMDR2_E_* code
@@ -245,6 +246,47 @@ int emdr2_mips_scatter_workspace_bytes(int64_t n_rows_total, int64_t n_upd, size
 int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total,
                                      void *tiled, float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite,
                                      void *workspace, size_t workspace_bytes, emdr2_stream_t stream);
+
+/*
+ * Index audit: one streaming pass over a shard's LIVE images that re-checks the premises of the search's
+ * proof from the stored bits and, separately, the "bit for bit a fresh build" contract of the derived structures -- emax_sq, the
+ * block-norm table, the int8 shadow image and its {s_b, N_b, D_b} table, which pack_rows, seal_shadow, update_rows, update_rows_scattered
+ * and an image swap all maintain.  It repairs nothing.
+ *   tiled, n_rows, dim, row_base, emax_sq   as for _search
+ *   block_norm_sq   the block-norm table of _block_norms, or NULL (words 4 and 5 stay 0)
+ *   shadow, table   the int8 image and its table as _search_shadow takes them, or both NULL (words 7..11 stay 0)
+ *   report          device uint64[EMDR2_AUDIT_WORDS], 8-byte aligned; the call clears it itself
+ * Enqueued on `stream` (three launches), nothing allocated, no host synchronisation; the caller orders it against updates of the shard like
+ * a search.  n_rows == 0: every counter 0 and both first-offender words ~0, nothing is read.  EMDR2_E_BADARG: null tiled, emax_sq or report,
+ * a dim outside the layout's envelope, row_base < 0, shadow without table or table without shadow, a shadow with dim % 256 != 0.
+ *
+ * Report words.  SOUND words: a non-zero count means a search of this image may return a wrong top-k with flags == 0.  They are evaluated
+ * in float64 from the stored bits -- the fp16 value widened exactly, the int8 byte as stored, s_b the stored float widened exactly -- and
+ * share no arithmetic with the seal or the norm routine.  NO tolerance is added: the square of an fp16 value is exact in float64 and the
+ * float64 sum of 8,192 of them is off by ~1e-12 relative, nine orders below the 0.1 % slack that every stored bound carries.  CANONICAL
+ * words: the structure differs in bits from what the project's own routine gives for this image (the audit runs that routine -- the code of
+ * _block_norms / _seal_shadow itself -- and compares instead of storing); the proof may still hold.  b = the 256-row block of row r.
+ *    0  rows_checked               n_rows
+ *    1  pad_rows_nonzero           rows of the fp16 image's zero padding (n_rows up to the next multiple of 512) with any bit set
+ *    2  nonfinite_rows             rows holding an inf / NaN (a shard searched through its shadow must hold none); excluded from 3, 4, 8, 9
+ *    3  rows_over_emax             sound: ||e_r||_2 > sqrtf(*emax_sq) * 1.001f, the bound formed in float exactly as the search's proof forms it
+ *    4  block_norm_low             sound, with block_norm_sq: ||e_r||_2^2 > block_norm_sq[b] * 1.001^2 (the same slack: the table feeds emax_sq)
+ *    5  block_norm_noncanonical    canonical, with block_norm_sq: blocks whose entry differs from _block_norms' value
+ *    6  emax_noncanonical          canonical: 1 if *emax_sq differs from the maximum over the image's blocks of that value
+ *    7  shadow_pad_rows_nonzero    rows past n_rows of the last sealed block of the int8 image (the seal covers ceil(n_rows / 256) blocks)
+ *                                  with any byte set
+ *    8  shadow_norm_low            sound: rows with ||e_r||_2 > N_b
+ *    9  shadow_resid_low           sound: rows with ||e_r - s_b e8_r||_2 > D_b, e8_r = the stored bytes
+ *   10  shadow_rows_noncanonical   canonical: rows of the sealed blocks whose int8 bytes differ from a fresh seal of the block
+ *   11  shadow_table_noncanonical  canonical: blocks whose {s_b, N_b, D_b} differ from a fresh seal
+ *   12  first_bad_row              the smallest GLOBAL row (row_base + local) counted in any of 1..4, 7..10; ~0 if none
+ *   13  first_bad_block            the smallest local 256-row block counted in 5 or 11; ~0 if none
+ *   14, 15  reserved, 0
+ * Counters are integer atomics: the report does not depend on the order the blocks are visited in.
+ */
+#define EMDR2_AUDIT_WORDS 16
+int emdr2_mips_audit(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const float *block_norm_sq,
+                     const void *shadow, const void *table, uint64_t *report, emdr2_stream_t stream);
 
 /* Diagnostics for tests: fp32 MFMA scores S~[n_q, n_rows] (row-major float) of the scan kernel's
  * arithmetic, for measuring |S~ - exact| against the bound used by the validity check. */
