@@ -22,6 +22,9 @@ AUDIT_NAMES = ("rows_checked", "pad_rows_nonzero", "nonfinite_rows", "rows_over_
 AUDIT_SOUND_WORDS = (1, 2, 3, 4, 7, 8, 9)           # a non-zero count: a search result may be wrong (word 2 only while a shadow is in use)
 AUDIT_CANONICAL_WORDS = (5, 6, 10, 11)              # a non-zero count: the image is not byte for byte a fresh build
 AUDIT_NONE = (1 << 64) - 1                          # first_bad_row / first_bad_block: no offender
+GEN_WORDS = 37                                      # the report of emdr2_mips_generation_stats: the five named words, then the 32 age bins
+GEN_NAMES = ("count", "sum_age", "min_age", "max_age", "from_future")
+GEN_MAX = (1 << 31) - 1                             # generations are below 2^31
 
 _ERRORS = {-1: "bad argument", -2: "workspace too small", -3: "HIP launch/runtime error", -4: "unsupported shape"}
 
@@ -57,6 +60,10 @@ SIGNATURES = {
     "emdr2_mips_update_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_scatter_workspace_bytes": (_i32, [_i64, _i64, ctypes.POINTER(_sz)]),
     "emdr2_mips_update_rows_scattered": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "emdr2_mips_update_rows_stamped": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i32, _vp, _vp]),
+    "emdr2_mips_update_rows_scattered_stamped": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, ctypes.c_uint32,
+                                                         _i32, _vp, _vp]),
+    "emdr2_mips_generation_stats": (_i32, [_vp, _i64, _i64, _vp, _i64, ctypes.c_uint32, _vp, _vp]),
     "emdr2_mips_audit": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_debug_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "emdr2_mips_set_timing": (_i32, [_i32]),

@@ -116,17 +116,34 @@ def get_parser():
                         'steps.  No spare fp16 image and no spare int8 shadow image: half the index HBM of the swap mode.  A choice of '
                         'semantics, not a tuning knob: searches then see a MIX of two embedding generations -- rows already re-embedded in '
                         'the current pass next to rows of the pass before -- where the default, the reference\'s update_index, replaces '
-                        'the whole index atomically')
+                        'the whole index atomically.  The refresher writes whatever its pass reaches, also over rows that '
+                        '--index-writeback has written from newer weights since; --index-newest-wins changes that')
     g.add_argument('--index-writeback', action='store_true',
                    help='(not in the reference; needs --disable-retriever-dropout) at every step boundary write the embeddings the step has '
                         'just computed with the LIVE context encoder for the batch-size x topk passages it retrieved into the index rows they '
                         'were retrieved from (with several ranks: two all-gathers per step, every rank updates its own shard).  No encoder '
                         'work is added.  A row holds whatever was written LAST: a passage retrieved by several questions keeps the last '
                         'one\'s embedding, and the rolling refresher (--async-indexer --index-refresh-in-place) will later overwrite a '
-                        'written-back row with its older snapshot\'s embedding when its pass comes round.  A choice of semantics, not a '
+                        'written-back row with its older snapshot\'s embedding when its pass comes round (unless --index-newest-wins is '
+                        'given, which makes every in-place writer leave rows from newer weights alone).  A choice of semantics, not a '
                         'tuning knob: the index holds a mix of embedding generations, the retrieved rows being the freshest.  Allowed '
                         'without --async-indexer; with --async-indexer it needs --index-refresh-in-place (in swap mode every write would '
                         'be discarded at the next swap)')
+    g.add_argument('--index-generations', action='store_true',
+                   help='(not in the reference) the evidence index keeps one 32-bit generation stamp per row on the device (84 MB at 21 M '
+                        'rows): the number of optimizer steps the weights that wrote the row had taken -- 0 for rows loaded from '
+                        '--embedding-path, the snapshot\'s iteration for rows restored from an index snapshot (stamps are not saved: ages '
+                        'after a resume are a lower bound).  Every writer stamps what it writes.  At every --log-interval rank 0 prints one '
+                        'line: mean / max age, in steps, of the rows the last step retrieved (as its search found them), mean / max age of '
+                        'the whole index, and the rows that newest-wins updates have left alone since the last line.  One small device pass '
+                        'and two small all-reduces per statistic, at iterations that depend on --log-interval alone.  No search result changes')
+    g.add_argument('--index-newest-wins', action='store_true',
+                   help='(not in the reference; implies --index-generations; needs an in-place writer: --index-refresh-in-place or '
+                        '--index-writeback) the rolling refresher and the write-back leave a row alone when its stamp is above the '
+                        'generation they would write: a row written back from the weights of step t - 1 is no longer replaced by the '
+                        'refresher\'s embedding from a snapshot taken up to a whole pass earlier.  Ties write, so within one generation the '
+                        'last writer still wins.  A choice of semantics, not a tuning knob: without it a row holds whatever was written '
+                        'LAST, with it whatever came from the NEWEST weights; the index is a fresh build of its rows either way')
     g.add_argument('--context-embeddings-from-index', action='store_true',
                    help='(not in the reference; needs --no-context-embedder-training) take the embeddings of the batch-size x topk retrieved '
                         'passages from the index rows the search returned instead of running the frozen context encoder over them, in '
@@ -186,6 +203,11 @@ def parse_args(argv=None):
     if args.index_writeback and args.async_indexer and not args.index_refresh_in_place:
         raise ValueError("--index-writeback with --async-indexer needs --index-refresh-in-place (in swap mode a refresh is always in progress: "
                          "the index refuses in-place updates, and the next swap would discard them anyway)")
+    if args.index_newest_wins:
+        if not (args.index_writeback or (args.async_indexer and args.index_refresh_in_place)):
+            raise ValueError("--index-newest-wins needs an in-place writer of the index: --index-writeback or --async-indexer "
+                             "--index-refresh-in-place (the swap refresher replaces whole images: there is nothing to arbitrate)")
+        args.index_generations = True
     if args.audit_index_interval < 0:
         raise ValueError("--audit-index-interval must be >= 0")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:

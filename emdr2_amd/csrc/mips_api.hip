@@ -380,8 +380,9 @@ int emdr2_mips_block_norms(const void *tiled, int64_t n_rows, int dim, int64_t f
     return mips_launch_block_norms(tiled, dim, first_block, n_blocks, block_norm_sq, (hipStream_t)stream);
 }
 
-int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
-                           float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream_)
+// both forms of the contiguous update: `stamp` null = emdr2_mips_update_rows as it always was
+static int update_rows_impl(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled, float *block_norm_sq,
+                            float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, const RowStamp *stamp, emdr2_stream_t stream_)
 {
     if (!rows_rm || !tiled || !block_norm_sq || !emax_sq || bad_shape(n_rows_total, dim) || n_chunk < 0 || row_offset < 0 ||
         row_offset + n_chunk > n_rows_total)
@@ -391,11 +392,32 @@ int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t first_block = row_offset / 256, n_blocks = (row_offset + n_chunk - 1) / 256 - first_block + 1;   // the blocks these rows touch
     int rc;
-    if ((rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, stream))) return rc;
+    if ((rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, stamp, stream))) return rc;
     if ((rc = mips_launch_block_norms(tiled, dim, first_block, n_blocks, block_norm_sq, stream))) return rc;
     if ((rc = mips_launch_table_max(block_norm_sq, (n_rows_total + 511) / 512 * 2, emax_sq, stream))) return rc;
     if (shadow) return mips_launch_seal_shadow(tiled, dim, first_block, n_blocks, shadow, (float *)table, nonfinite, stream);
     return EMDR2_OK;
+}
+
+int emdr2_mips_update_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
+                           float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, emdr2_stream_t stream)
+{
+    return update_rows_impl(rows_rm, n_chunk, dim, row_offset, n_rows_total, tiled, block_norm_sq, emax_sq, shadow, table, nonfinite, nullptr, stream);
+}
+
+// (stamps are below 2^31; the stamp array and the counter are 4-byte words of device memory)
+static bool bad_stamp(const uint32_t *generation, uint32_t gen, const uint32_t *n_kept_newer)
+{
+    return !generation || ((uintptr_t)generation & 3) || ((uintptr_t)n_kept_newer & 3) || gen >= 0x80000000u;
+}
+
+int emdr2_mips_update_rows_stamped(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
+                                   float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, uint32_t *generation,
+                                   uint32_t gen, int newest_wins, uint32_t *n_kept_newer, emdr2_stream_t stream)
+{
+    if (bad_stamp(generation, gen, n_kept_newer)) return EMDR2_E_BADARG;
+    const RowStamp stamp = {generation, gen, newest_wins ? 1 : 0, n_kept_newer};
+    return update_rows_impl(rows_rm, n_chunk, dim, row_offset, n_rows_total, tiled, block_norm_sq, emax_sq, shadow, table, nonfinite, &stamp, stream);
 }
 
 // workspace of a scattered update: one claim word per 256-row block of the padded image, the touched-block counter (a 16-byte slot), then
@@ -411,9 +433,10 @@ int emdr2_mips_scatter_workspace_bytes(int64_t n_rows_total, int64_t n_upd, size
     return EMDR2_OK;
 }
 
-int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled,
-                                     float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, void *workspace,
-                                     size_t workspace_bytes, emdr2_stream_t stream_)
+// both forms of the scattered update: `stamp` null = emdr2_mips_update_rows_scattered as it always was
+static int update_rows_scattered_impl(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled,
+                                      float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, void *workspace,
+                                      size_t workspace_bytes, const RowStamp *stamp, emdr2_stream_t stream_)
 {
     if (!rows_rm || !row_ids || !tiled || !block_norm_sq || !emax_sq || !workspace || ((uintptr_t)workspace & 15) || bad_shape(n_rows_total, dim) ||
         bad_scatter_shape(n_rows_total, n_upd))
@@ -430,11 +453,40 @@ int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids
     unsigned *claimed = (unsigned *)workspace, *n_touched = (unsigned *)((char *)workspace + claim_bytes), *touched = n_touched + 4;
     if (hipMemsetAsync(workspace, 0, claim_bytes + 16, stream) != hipSuccess) return EMDR2_E_LAUNCH;
     int rc;
-    if ((rc = mips_launch_write_rows_at(rows_rm, row_ids, n_upd, dim, n_rows_total, tiled, claimed, n_touched, touched, cap, stream))) return rc;
+    if ((rc = mips_launch_write_rows_at(rows_rm, row_ids, n_upd, dim, n_rows_total, tiled, claimed, n_touched, touched, cap, stamp, stream))) return rc;
     if ((rc = mips_launch_block_norms_list(tiled, dim, touched, n_touched, cap, block_norm_sq, stream))) return rc;
     if ((rc = mips_launch_table_max(block_norm_sq, table_blocks, emax_sq, stream))) return rc;
     if (shadow) return mips_launch_seal_shadow_list(tiled, dim, touched, n_touched, cap, shadow, (float *)table, nonfinite, stream);
     return EMDR2_OK;
+}
+
+int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled,
+                                     float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, void *workspace,
+                                     size_t workspace_bytes, emdr2_stream_t stream)
+{
+    return update_rows_scattered_impl(rows_rm, row_ids, n_upd, dim, n_rows_total, tiled, block_norm_sq, emax_sq, shadow, table, nonfinite, workspace,
+                                      workspace_bytes, nullptr, stream);
+}
+
+int emdr2_mips_update_rows_scattered_stamped(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled,
+                                             float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite, void *workspace,
+                                             size_t workspace_bytes, uint32_t *generation, uint32_t gen, int newest_wins, uint32_t *n_kept_newer,
+                                             emdr2_stream_t stream)
+{
+    if (bad_stamp(generation, gen, n_kept_newer)) return EMDR2_E_BADARG;
+    const RowStamp stamp = {generation, gen, newest_wins ? 1 : 0, n_kept_newer};
+    return update_rows_scattered_impl(rows_rm, row_ids, n_upd, dim, n_rows_total, tiled, block_norm_sq, emax_sq, shadow, table, nonfinite, workspace,
+                                      workspace_bytes, &stamp, stream);
+}
+
+static_assert(MIPS_GEN_WORDS == EMDR2_GEN_WORDS, "the report layout of include/emdr2_mips.h");
+int emdr2_mips_generation_stats(const uint32_t *generation, int64_t n_rows, int64_t row_base, const int64_t *global_rows, int64_t n_sel, uint32_t now,
+                                uint64_t *report, emdr2_stream_t stream)
+{
+    if (!report || ((uintptr_t)report & 7) || ((uintptr_t)generation & 3) || n_rows < 0 || row_base < 0 || (n_rows > 0 && !generation) ||
+        (global_rows && n_sel < 0))
+        return EMDR2_E_BADARG;
+    return mips_launch_generation_stats(generation, n_rows, row_base, global_rows, global_rows ? n_sel : n_rows, now, report, (hipStream_t)stream);
 }
 
 int emdr2_mips_audit(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const float *block_norm_sq,

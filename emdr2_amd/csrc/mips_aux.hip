@@ -10,13 +10,35 @@
 // index re-layout (reference: add_embed_data uploads a dense row-major fp16 matrix,
 // megatron/data/emdr2_index.py:248-256; here the upload is re-tiled into scan order)
 // ------------------------------------------------------------------------------------------------
+// Generation stamps (emdr2_mips_update_rows_stamped, _update_rows_scattered_stamped; RowStamp in mips_kernels.h): one 32-bit word per row, the
+// number of optimizer steps behind the weights that wrote it.  A row writer has one thread per 16-byte segment, so a row's threads sit in
+// several waves, maybe several workgroups, and each of them takes the newest-wins decision for itself from the row's stamp while the thread of
+// segment 0 stores the new stamp.  That is only sound because the rule is NON-STRICT: a thread reads either the old stamp s or, after that
+// store, gen; s <= gen and gen <= gen say the same, and for s > gen nobody stores at all -- every thread of the row decides alike, whatever
+// it saw.  Under a strict s < gen a thread that read gen would skip its segment while its neighbours wrote theirs: a row mixed of old and
+// new segments.  (A strict rule needs the decision taken once per row and a launch boundary between it and the stamp store.)  Ties write,
+// which keeps "the last writer of a generation wins".  The stamp is read and stored as relaxed device-scope atomics: plain 4-byte accesses
+// for the hardware, and the compiler may neither split nor repeat them.  -> whether this thread moves its segment.
+__device__ __forceinline__ bool stamp_admits(const RowStamp &st, int64_t row, int seg)
+{
+    if (st.newest_wins && __hip_atomic_load(st.generation + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > st.gen) {
+        if (seg == 0 && st.n_kept_newer) atomicAdd(st.n_kept_newer, 1u);        // a kept-newer row is counted once
+        return false;
+    }
+    if (seg == 0) __hip_atomic_store(st.generation + row, st.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+
+// (STAMPED = false is the kernel as it was before there were stamps: the stamp argument is an empty struct nobody reads)
+template <bool STAMPED>
 __global__ void pack_rows_kernel(const uint4 *__restrict__ rows_rm, int64_t n_chunk, int nseg, int64_t row_offset,
-                                 char *__restrict__ tiled)
+                                 char *__restrict__ tiled, typename StampArg<STAMPED>::type st)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_chunk * nseg) return;
     const int64_t r = i / nseg;
     const int seg = (int)(i - r * nseg);
+    if constexpr (STAMPED) { if (!stamp_admits(st, row_offset + r, seg)) return; }
     *(uint4 *)(tiled + tiled_seg_offset(row_offset + r, seg, nseg >> 2)) = rows_rm[i];
 }
 
@@ -86,13 +108,17 @@ int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *e
 }
 
 // pack_rows_kernel alone: rows into the image, emax_sq untouched (the in-place update recomputes it from the block table)
-int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, hipStream_t stream)
+int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, const RowStamp *stamp, hipStream_t stream)
 {
     const int nseg = dim / 8;
     const int64_t total = n_chunk * nseg;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg,
-                       row_offset, (char *)tiled);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (stamp)
+        hipLaunchKernelGGL(pack_rows_kernel<true>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg, row_offset, (char *)tiled, *stamp);
+    else
+        hipLaunchKernelGGL(pack_rows_kernel<false>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg, row_offset, (char *)tiled,
+                           NoStamp{});
     return CHECK_LAUNCH();
 }
 
@@ -101,10 +127,13 @@ int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_
 // a row's first segment also claims the row's 256-row block: an atomic exchange on the block's flag word (zeroed per call), and whoever
 // finds it 0 appends the block to `touched` through the counter -- once per block however many rows of the call fall into it.  Both are
 // device-scope atomics on words nobody reads in this launch; the list and its count are read by LATER launches on the same stream.  At most
-// min(n_upd, table blocks) = `cap` distinct blocks can be claimed, which is the list's length.
+// min(n_upd, table blocks) = `cap` distinct blocks can be claimed, which is the list's length.  STAMPED: a row that stamp_admits leaves
+// alone is neither written nor does it claim its block (nothing in the block changed on its account); invalid ids are skipped before the
+// stamp is looked at, so they are never counted as kept newer.
+template <bool STAMPED>
 __global__ void pack_rows_at_kernel(const uint4 *__restrict__ rows_rm, const int64_t *__restrict__ row_ids, int64_t n_upd, int nseg, int64_t n_rows_total,
                                     char *__restrict__ tiled, unsigned *__restrict__ claimed, unsigned *__restrict__ n_touched,
-                                    unsigned *__restrict__ touched, unsigned cap)
+                                    unsigned *__restrict__ touched, unsigned cap, typename StampArg<STAMPED>::type st)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_upd * nseg) return;
@@ -112,6 +141,7 @@ __global__ void pack_rows_at_kernel(const uint4 *__restrict__ rows_rm, const int
     const int seg = (int)(i - r * nseg);
     const int64_t row = row_ids[r];
     if (row < 0 || row >= n_rows_total) return;
+    if constexpr (STAMPED) { if (!stamp_admits(st, row, seg)) return; }
     *(uint4 *)(tiled + tiled_seg_offset(row, seg, nseg >> 2)) = rows_rm[i];
     if (seg == 0) {
         const unsigned b = (unsigned)(row >> 8);
@@ -123,14 +153,19 @@ __global__ void pack_rows_at_kernel(const uint4 *__restrict__ rows_rm, const int
 }
 
 int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled, unsigned *claimed,
-                              unsigned *n_touched, unsigned *touched, unsigned cap, hipStream_t stream)
+                              unsigned *n_touched, unsigned *touched, unsigned cap, const RowStamp *stamp, hipStream_t stream)
 {
     const int nseg = dim / 8;
     const int64_t total = n_upd * nseg;
     if (total == 0) return 0;
     if ((total + 255) / 256 > 0x7fffffff) return -4;
-    hipLaunchKernelGGL(pack_rows_at_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4 *)rows_rm, row_ids, n_upd, nseg,
-                       n_rows_total, (char *)tiled, claimed, n_touched, touched, cap);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (stamp)
+        hipLaunchKernelGGL(pack_rows_at_kernel<true>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, row_ids, n_upd, nseg, n_rows_total,
+                           (char *)tiled, claimed, n_touched, touched, cap, *stamp);
+    else
+        hipLaunchKernelGGL(pack_rows_at_kernel<false>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, row_ids, n_upd, nseg, n_rows_total,
+                           (char *)tiled, claimed, n_touched, touched, cap, NoStamp{});
     return CHECK_LAUNCH();
 }
 
@@ -138,7 +173,7 @@ int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t
                           float *emax_sq, hipStream_t stream)
 {
     if (n_chunk == 0) return 0;
-    const int rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, stream);
+    const int rc = mips_launch_write_rows(rows_rm, n_chunk, dim, row_offset, tiled, nullptr, stream);
     if (rc) return rc;
     int nb = (int)((n_chunk + 3) / 4);
     if (nb > 4096) nb = 4096;
@@ -170,6 +205,88 @@ int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t 
     if (total == 0) return 0;
     hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const char *)tiled, nseg,
                        n_rows, row_base, row_ids, n_out, (uint4 *)rows_rm);
+    return CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------
+// generation statistics (emdr2_mips_generation_stats; the report words are documented in include/emdr2_mips.h)
+// ------------------------------------------------------------------------------------------------
+// One pass over the stamps of a whole shard (global_rows null: item i is local row i) or of a list of GLOBAL rows (item i is global_rows[i]
+// when it falls into [row_base, row_base + n_rows), else it is left out -- compared before the subtraction, like unpack_rows_kernel).  A
+// thread walks its items grid-stride and keeps its own count / sum / min / max; runs of equal histogram bins go to the workgroup's LDS
+// tally with one atomic (the stamps of neighbouring rows are mostly equal: one writer, one pass).  The workgroup flushes its non-zero words
+// with 64-bit integer atomics, like the audit: the report does not depend on the order the items are visited in.
+enum { G_COUNT = 0, G_SUM = 1, G_MIN = 2, G_MAX = 3, G_FUTURE = 4, G_HIST = 5, G_WORDS = G_HIST + 32 };
+static_assert(G_WORDS == MIPS_GEN_WORDS && G_WORDS <= 64, "the report layout of include/emdr2_mips.h, cleared by one wave");
+
+__global__ void __launch_bounds__(64) generation_stats_init_kernel(unsigned long long *report)
+{
+    if (threadIdx.x < G_WORDS) report[threadIdx.x] = threadIdx.x == G_MIN ? ~0ull : 0ull;
+}
+
+__global__ void __launch_bounds__(256) generation_stats_kernel(const uint32_t *__restrict__ generation, int64_t n_rows, int64_t row_base,
+                                                               const int64_t *__restrict__ global_rows, int64_t n_items, uint32_t now,
+                                                               unsigned long long *__restrict__ report)
+{
+    __shared__ unsigned long long sh_sum;
+    __shared__ unsigned sh_count, sh_future, sh_min, sh_max, sh_hist[32];
+    const int tid = threadIdx.x;
+    if (tid < 32) sh_hist[tid] = 0u;
+    if (tid == 0) { sh_sum = 0ull; sh_count = 0u; sh_future = 0u; sh_min = 0xffffffffu; sh_max = 0u; }
+    __syncthreads();
+    unsigned long long sum = 0ull;
+    unsigned count = 0u, future = 0u, lo = 0xffffffffu, hi = 0u, run_bin = 0u, run = 0u;    // (a thread sees < 2^32 items: the grid is sized for it)
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n_items; i += stride) {
+        int64_t row = i;
+        if (global_rows) {
+            const int64_t id = global_rows[i];
+            if (id < row_base || id - row_base >= n_rows) continue;
+            row = id - row_base;
+        }
+        const uint32_t g = generation[row];
+        const uint32_t age = g > now ? 0u : now - g;
+        future += g > now;
+        ++count; sum += age;
+        lo = age < lo ? age : lo; hi = age > hi ? age : hi;
+        unsigned bin = age ? 32u - (unsigned)__clz(age) : 0u;          // [2^(b-1), 2^b) -> b
+        bin = bin > 31u ? 31u : bin;                                    // (ages of 2^31 and more cannot come from stamps below 2^31)
+        if (bin != run_bin) {
+            if (run) atomicAdd(&sh_hist[run_bin], run);
+            run_bin = bin; run = 0u;
+        }
+        ++run;
+    }
+    if (run) atomicAdd(&sh_hist[run_bin], run);
+    if (count) {
+        atomicAdd(&sh_count, count); atomicAdd(&sh_sum, sum); atomicMin(&sh_min, lo); atomicMax(&sh_max, hi);
+        if (future) atomicAdd(&sh_future, future);
+    }
+    __syncthreads();
+    if (sh_count == 0u) return;                                         // (uniform: nothing of this workgroup's was covered)
+    if (tid == 0) {
+        atomicAdd(&report[G_COUNT], (unsigned long long)sh_count);
+        atomicAdd(&report[G_SUM], sh_sum);
+        atomicMin(&report[G_MIN], (unsigned long long)sh_min);
+        atomicMax(&report[G_MAX], (unsigned long long)sh_max);
+        if (sh_future) atomicAdd(&report[G_FUTURE], (unsigned long long)sh_future);
+    } else if (tid >= 32 && tid < 64 && sh_hist[tid - 32]) {
+        atomicAdd(&report[G_HIST + tid - 32], (unsigned long long)sh_hist[tid - 32]);
+    }
+}
+
+int mips_launch_generation_stats(const uint32_t *generation, int64_t n_rows, int64_t row_base, const int64_t *global_rows, int64_t n_items,
+                                 uint32_t now, uint64_t *report, hipStream_t stream)
+{
+    hipLaunchKernelGGL(generation_stats_init_kernel, dim3(1), dim3(64), 0, stream, (unsigned long long *)report);
+    if (n_rows > 0 && n_items > 0) {
+        int64_t blocks = (n_items + 255) / 256;
+        // two workgroups per CU, a thread then walks n_items / 131,072 items: every workgroup ends in five to a dozen atomics on the SAME
+        // 37 words, which serialise -- with 2,048 workgroups they, not the 10 MB of stamps of an N / 8 shard, set the time of the pass
+        if (blocks > 512) blocks = 512;
+        hipLaunchKernelGGL(generation_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, generation, n_rows, row_base, global_rows, n_items,
+                           now, (unsigned long long *)report);
+    }
     return CHECK_LAUNCH();
 }
 

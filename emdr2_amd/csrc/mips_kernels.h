@@ -63,19 +63,36 @@ int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t
                           float *emax_sq, hipStream_t stream);
 // in-place row updates: rows into the image without touching emax_sq; block_norm_sq[b] = max ||E[r]||^2 over block b's 256 rows for
 // b in [first_block, first_block + n_blocks); *emax_sq = max of the table's n_blocks entries
-int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, hipStream_t stream);
+// generation stamps of the two row writers (emdr2_mips_update_rows_stamped, _scattered_stamped): generation[row] = gen for every row written;
+// with newest_wins a row whose stamp is above gen is left alone, image and stamp, and counted in *n_kept_newer (may be null).  A null
+// RowStamp pointer launches the unstamped kernel, whose stamp argument is the empty NoStamp.
+struct RowStamp {
+    uint32_t *generation;
+    uint32_t gen;
+    int newest_wins;
+    uint32_t *n_kept_newer;
+};
+struct NoStamp {};
+template <bool STAMPED> struct StampArg { typedef NoStamp type; };
+template <> struct StampArg<true> { typedef RowStamp type; };
+int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled, const RowStamp *stamp, hipStream_t stream);
 int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int64_t n_blocks, float *block_norm_sq, hipStream_t stream);
 int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream);
 // scattered row updates: rows_rm[i] into image row row_ids[i] (ids outside [0, n_rows_total) skipped); every touched 256-row block is
 // claimed once through claimed[table blocks] (zeroed by the caller) and appended to touched[cap] through *n_touched (zeroed too);
 // then the block norms of exactly the listed blocks
 int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total, void *tiled, unsigned *claimed,
-                              unsigned *n_touched, unsigned *touched, unsigned cap, hipStream_t stream);
+                              unsigned *n_touched, unsigned *touched, unsigned cap, const RowStamp *stamp, hipStream_t stream);
 int mips_launch_block_norms_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, float *block_norm_sq,
                                  hipStream_t stream);
 // rows_rm[i] = image row row_ids[i] - row_base if that lies in [0, n_rows), else zero bytes
 int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const int64_t *row_ids, int64_t n_out,
                             void *rows_rm, hipStream_t stream);
+// the report of emdr2_mips_generation_stats (MIPS_GEN_WORDS = EMDR2_GEN_WORDS) over n_items items: local rows 0.. (global_rows null) or the
+// entries of global_rows that fall into [row_base, row_base + n_rows); clears the report itself
+#define MIPS_GEN_WORDS 37
+int mips_launch_generation_stats(const uint32_t *generation, int64_t n_rows, int64_t row_base, const int64_t *global_rows, int64_t n_items,
+                                 uint32_t now, uint64_t *report, hipStream_t stream);
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);

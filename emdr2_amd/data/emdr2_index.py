@@ -408,17 +408,32 @@ def audit_failures(result):
     return ", ".join(parts)
 
 
+def generation_result(words):
+    """The dict `generation_stats` returns, from the EMDR2_GEN_WORDS report words of emdr2_mips_generation_stats (Python ints): the five
+    named words, `histogram` (32 bins: bin 0 = age 0, bin b = ages in [2^(b-1), 2^b)) and `mean_age` (0.0 over no rows).  `min_age` is
+    2**64 - 1 when no row was covered."""
+    words = [int(w) & _native.AUDIT_NONE for w in words]
+    out = dict(zip(_native.GEN_NAMES, words))
+    out["histogram"] = words[len(_native.GEN_NAMES):_native.GEN_WORDS]
+    out["mean_age"] = out["sum_age"] / out["count"] if out["count"] else 0.0
+    return out
+
+
 class HipIndexShard(object):
     """One contiguous row shard resident in this process's GPU, stripe-tiled for the HIP scan.
 
     `shadow`: keep an int8 shadow image of the shard (+50 % HBM) and run the filter segments of at least `shadow_min_rows` rows of a
     129..512-query search on it (csrc/mips_scan8i.hip); results are bit-identical with and without.  The image is only allocated for
-    shards that have such a segment, and only used while it is sealed against the current fp16 image and every row is finite."""
+    shards that have such a segment, and only used while it is sealed against the current fp16 image and every row is finite.
+
+    `generations`: keep one 32-bit stamp per local row on the device (`self.generation`; 84 MB at 21 M rows) -- the number of optimizer
+    steps the weights that wrote the row had taken; every writer maintains it, the in-place writers can honour it (`newest_wins`),
+    `generation_stats` reads it.  Off (the default): nothing is allocated and every entry point behaves as it always did."""
 
     SHADOW_MIN_ROWS = 1 << 19
     _DENSE_ROWS = 8192                                             # rows of the dense first segment of a search (csrc/mips_api.hip)
 
-    def __init__(self, dim, n_rows, row_base, device=None, shadow=True, shadow_min_rows=None):
+    def __init__(self, dim, n_rows, row_base, device=None, shadow=True, shadow_min_rows=None, generations=False):
         self.lib = _native.lib()
         if not torch.cuda.is_available():
             raise _native.NativeError("HipIndexShard needs a GPU; there is no CPU fallback")
@@ -440,6 +455,24 @@ class HipIndexShard(object):
         self._refreshing = False                                   # between begin_refresh and commit_refresh
         self._block_norms = None                                   # max ||row||^2 per 256-row block of self.tiled (update_rows), built on first use
         self._scatter_ws = None                                    # workspace of update_rows_at (claim words + touched-block list), grown on demand
+        # generation stamps of self.tiled (int32 storage of the device's uint32 words: values are below 2^31), of the refresh spare, and
+        # the counter of rows that newest-wins updates left alone
+        self.generation = torch.zeros(max(self.n_rows, 1), dtype=torch.int32, device=self.device) if generations else None
+        self._spare_generation = None
+        self._kept_newer = torch.zeros(1, dtype=torch.int32, device=self.device) if generations else None
+
+    def _generation_of(self, generation, what):
+        """a writer's `generation` argument on a shard with or without stamps -> the stamp to write (None without stamps)"""
+        if self.generation is None:
+            if generation:
+                raise ValueError("%s: this shard keeps no generation stamps (HipIndexShard(..., generations=True))" % what)
+            return None
+        if generation is None:
+            raise ValueError("%s on a shard with generation stamps needs generation=" % what)
+        g = int(generation)
+        if not 0 <= g <= _native.GEN_MAX:
+            raise ValueError("generation must be in [0, 2^31)")
+        return g
 
     def _seal(self, tiled, into):
         """Build the int8 shadow of the finished fp16 image `tiled` (on the current stream) into the buffers `into` (allocated on first
@@ -456,8 +489,10 @@ class HipIndexShard(object):
                                                       bad.data_ptr(), _native.stream_ptr()), "seal_shadow")
         return into, (into if int(bad.item()) == 0 else None)
 
-    def append_rows(self, rows):
-        """rows: fp16 [n, dim] (numpy or torch, host or device); appended at the next free local row."""
+    def append_rows(self, rows, generation=0):
+        """rows: fp16 [n, dim] (numpy or torch, host or device); appended at the next free local row and, on a shard with stamps,
+        stamped `generation` (rows loaded from a file or store: 0)."""
+        generation = self._generation_of(generation, "append_rows")
         if isinstance(rows, np.ndarray):
             if rows.dtype != np.float16 or rows.ndim != 2 or rows.shape[1] != self.dim:
                 raise ValueError("rows must be float16 [n, %d]" % self.dim)
@@ -467,6 +502,8 @@ class HipIndexShard(object):
         if self._filled + n > self.n_rows:
             raise ValueError("shard overflow")
         self._shadow = None
+        if generation is not None and n:
+            self.generation[self._filled:self._filled + n].fill_(generation)
         for lo in range(0, n, _UPLOAD_ROWS):
             chunk = rows[lo:lo + _UPLOAD_ROWS]
             if isinstance(chunk, np.ndarray):                      # (a memory map: only this 1.5 GiB piece is ever resident on the host)
@@ -482,8 +519,15 @@ class HipIndexShard(object):
         return self
 
     # -- in-HBM refresh (config 5): a second image of the shard is filled while the first keeps serving searches ---------------
-    def begin_refresh(self):
-        """Allocate (once) and clear the spare stripe-tiled image; rows are then written with `refresh_rows` in any order."""
+    def begin_refresh(self, generation=0):
+        """Allocate (once) and clear the spare stripe-tiled image; rows are then written with `refresh_rows` in any order.  One
+        `generation` per pass: on a shard with stamps the spare stamp array is filled with it and swapped in by `commit_refresh` together
+        with the images."""
+        generation = self._generation_of(generation, "begin_refresh")
+        if generation is not None:
+            if self._spare_generation is None:
+                self._spare_generation = torch.empty_like(self.generation)
+            self._spare_generation.fill_(generation)
         if getattr(self, "_spare", None) is None:
             self._spare = torch.zeros_like(self.tiled)
             self._spare_emax = torch.zeros_like(self.emax_sq)
@@ -514,12 +558,14 @@ class HipIndexShard(object):
         self._shadow_buf, self._spare_shadow_buf = self._spare_shadow_buf, self._shadow_buf
         self.tiled, self._spare = self._spare, self.tiled
         self.emax_sq, self._spare_emax = self._spare_emax, self.emax_sq
+        if self.generation is not None:
+            self.generation, self._spare_generation = self._spare_generation, self.generation
         self._refreshed = 0
         self._refreshing = False
         self._block_norms = None                                   # (it described the image that has just been swapped out)
 
     # -- in-place update: rows of the image that is being searched are overwritten, nothing is swapped, no second image exists ---
-    def update_rows(self, local_row, rows):
+    def update_rows(self, local_row, rows, generation=None, newest_wins=False):
         """rows fp16 [n, dim] on this device -> rows [local_row, local_row + n) of the LIVE image, enqueued on the CURRENT stream (the
         device counterpart of the reference store's `add_block_data(..., allow_overwrite=True)`).  `emax_sq` and, when the shard has a
         sealed int8 shadow, the touched 256-row blocks of the shadow image and its table are brought to exactly what a fresh build of
@@ -528,7 +574,12 @@ class HipIndexShard(object):
         stream would see a half-written block.  The block-norm table behind `emax_sq` is built on the first call (one pass over the
         image) and again after a `commit_refresh`.  If an updated block holds an inf / NaN the shard stops using its shadow until the
         next full seal, like a shard freshly built from such rows; that flag is read back with one `.item()` per call on a shard with a
-        sealed shadow (a host synchronisation on the current stream -- the search that follows does one of its own)."""
+        sealed shadow (a host synchronisation on the current stream -- the search that follows does one of its own).
+
+        On a shard with stamps `generation` is required: every row written is stamped with it.  `newest_wins`: a row whose stamp is ABOVE
+        `generation` is left alone, image and stamp, and counted (`kept_newer`); ties write (csrc: emdr2_mips_update_rows_stamped).  The
+        result is still a fresh build of the rows the shard now holds.  On a shard without stamps both keywords raise ValueError."""
+        stamp = self._stamp_of(generation, newest_wins, "update_rows")
         self._check_update_rows(rows)
         n = rows.shape[0]
         if local_row < 0 or local_row + n > self.n_rows:
@@ -537,16 +588,24 @@ class HipIndexShard(object):
         if n == 0:
             return
         rows = rows.contiguous()
+        if stamp is not None:
+            self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows_stamped(
+                rows.data_ptr(), n, self.dim, local_row, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow, image,
+                bad, *stamp, _native.stream_ptr()), "update_rows_stamped"))
+            return
         self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows(
             rows.data_ptr(), n, self.dim, local_row, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow, image, bad,
             _native.stream_ptr()), "update_rows"))
 
-    def update_rows_at(self, local_rows, rows):
+    def update_rows_at(self, local_rows, rows, generation=None, newest_wins=False):
         """`update_rows` addressed by a list: rows fp16 [n, dim] and local_rows int64 [n], both on this device; entry i goes to row
         local_rows[i] of the LIVE image (csrc: emdr2_mips_update_rows_scattered).  Entries outside [0, n_rows) are skipped, so a list
         that also names rows of other shards needs no compaction.  Where a row is named more than once the LAST occurrence wins
         (`resolve_duplicate_rows`, on the device, no host read).  Same preconditions, same result and same non-finite read-back as
-        `update_rows`: afterwards the shard is byte for byte a fresh build of the same rows."""
+        `update_rows`: afterwards the shard is byte for byte a fresh build of the same rows.  `generation` / `newest_wins` as for
+        `update_rows` (csrc: emdr2_mips_update_rows_scattered_stamped): duplicates are resolved first, the stamp rule then applies to the
+        surviving entry; skipped entries are never counted as kept newer."""
+        stamp = self._stamp_of(generation, newest_wins, "update_rows_at")
         self._check_update_rows(rows)
         if local_rows.dtype != torch.int64 or local_rows.dim() != 1 or not local_rows.is_cuda:
             raise ValueError("local_rows must be a CUDA int64 [n] tensor")
@@ -563,9 +622,61 @@ class HipIndexShard(object):
         if self._scatter_ws is None or self._scatter_ws.numel() < nbytes.value:
             self._scatter_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         ws = self._scatter_ws
+        if stamp is not None:
+            self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows_scattered_stamped(
+                rows.data_ptr(), ids.data_ptr(), n, self.dim, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow,
+                image, bad, ws.data_ptr(), ws.numel(), *stamp, _native.stream_ptr()), "update_rows_scattered_stamped"))
+            return
         self._run_update(lambda table, shadow, image, bad: _native.check(self.lib.emdr2_mips_update_rows_scattered(
             rows.data_ptr(), ids.data_ptr(), n, self.dim, self.n_rows, self.tiled.data_ptr(), table.data_ptr(), self.emax_sq.data_ptr(), shadow, image,
             bad, ws.data_ptr(), ws.numel(), _native.stream_ptr()), "update_rows_scattered"))
+
+    def _stamp_of(self, generation, newest_wins, what):
+        """the four stamp arguments of the stamped entry points, or None on a shard without stamps (where the keywords are refused)"""
+        if self.generation is None:
+            if generation is not None or newest_wins:
+                raise ValueError("%s: generation / newest_wins need a shard with generation stamps (HipIndexShard(..., generations=True))" % what)
+            return None
+        g = self._generation_of(generation, what)
+        return self.generation.data_ptr(), g, int(bool(newest_wins)), self._kept_newer.data_ptr()
+
+    def kept_newer(self):
+        """Rows that newest-wins updates have left alone since the last call: reads and clears the device counter.  ONE host read, so it is
+        only called where a log line is printed."""
+        if self.generation is None:
+            raise ValueError("this shard keeps no generation stamps")
+        n = int(self._kept_newer.item())
+        self._kept_newer.zero_()
+        return n
+
+    def generation_report(self, now, global_rows=None):
+        """`generation_stats` without the host read: the report of emdr2_mips_generation_stats as CUDA int64 [GEN_WORDS] (bit patterns of
+        the uint64 words), enqueued on the current stream."""
+        if self.generation is None:
+            raise ValueError("this shard keeps no generation stamps")
+        now = int(now)
+        if not 0 <= now < (1 << 32):
+            raise ValueError("now must be in [0, 2^32)")
+        report = torch.empty(_native.GEN_WORDS, dtype=torch.int64, device=self.device)
+        rows_ptr, n_sel = None, 0
+        if global_rows is not None:
+            if not torch.is_tensor(global_rows) or global_rows.dtype != torch.int64 or global_rows.device != self.device:
+                raise ValueError("global_rows must be an int64 tensor on %s" % (self.device,))
+            global_rows = global_rows.contiguous()
+            rows_ptr, n_sel = global_rows.data_ptr(), global_rows.numel()
+        n_rows = self._filled if self._filled == self.n_rows else 0          # (a shard still being filled has no rows to report)
+        if global_rows is not None and n_sel == 0:
+            rows_ptr, n_rows = None, 0                                        # (an empty tensor has no pointer to tell "no list" from "an empty list")
+        _native.check(self.lib.emdr2_mips_generation_stats(self.generation.data_ptr(), n_rows, self.row_base, rows_ptr, n_sel, now,
+                                                           report.data_ptr(), _native.stream_ptr()), "generation_stats")
+        return report
+
+    def generation_stats(self, now, global_rows=None):
+        """Ages of this shard's rows at step count `now` (age = now - stamp, 0 where the stamp exceeds `now`): of all rows of the image
+        being searched, or of the entries of `global_rows` (CUDA int64 of any shape, e.g. `last_search_rows`) that fall into this shard --
+        -1 and other shards' rows are not counted, a row named twice counts twice.  One pass on the device, then ONE host read of the
+        296-byte report -> dict (`generation_result`)."""
+        return generation_result(self.generation_report(now, global_rows).tolist())
 
     def _check_update_rows(self, rows):
         if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_cuda:
@@ -832,8 +943,10 @@ class DistributedBruteForceIndex(object):
     the world group when torch.distributed is initialised, else a single shard.
     """
 
-    def __init__(self, embed_size, embed_data=None, use_gpu=False, process_group=None):
+    def __init__(self, embed_size, embed_data=None, use_gpu=False, process_group=None, generations=False):
         self.embed_size = embed_size
+        self.generations = bool(generations)                       # (extra, optional) the shard keeps generation stamps: HipIndexShard
+        self._load_generation = 0                                  # the stamp of rows that add_arrays uploads: 0, or a snapshot's iteration
         self.embed_data = embed_data
         self.use_gpu = use_gpu
         self.process_group = process_group
@@ -849,7 +962,7 @@ class DistributedBruteForceIndex(object):
         return 0, 1
 
     def _make_shard(self, dim, n_rows, row_base):
-        return HipIndexShard(dim, n_rows, row_base)
+        return HipIndexShard(dim, n_rows, row_base, generations=self.generations)
 
     # -- reference API -------------------------------------------------------------------------------
     def _set_mips_index(self):
@@ -888,8 +1001,8 @@ class DistributedBruteForceIndex(object):
         """(first global row, one past the last) of this rank's shard; row r holds doc id `ids[r]`."""
         return self.shard.row_base, self.shard.row_base + self.shard.n_rows
 
-    def begin_refresh(self):
-        self.shard.begin_refresh()
+    def begin_refresh(self, generation=0):
+        self.shard.begin_refresh(generation)
 
     def refresh_rows(self, global_row, rows):
         self.shard.refresh_rows(global_row - self.shard.row_base, rows)
@@ -897,19 +1010,50 @@ class DistributedBruteForceIndex(object):
     def commit_refresh(self):
         self.shard.commit_refresh()
 
-    def update_rows(self, global_row, rows):
+    def update_rows(self, global_row, rows, generation=None, newest_wins=False):
         """rows fp16 [n, dim] -> rows [global_row, global_row + n) of the image this rank is searching (HipIndexShard.update_rows); the
-        range must lie inside this rank's shard (`local_rows()`)."""
+        range must lie inside this rank's shard (`local_rows()`).  `generation` / `newest_wins`: the shard's stamp rule."""
         lo, hi = self.local_rows()
         if global_row < lo or global_row + rows.shape[0] > hi:
             raise ValueError("rows [%d, %d) are not all in this rank's shard [%d, %d)" % (global_row, global_row + rows.shape[0], lo, hi))
-        self.shard.update_rows(global_row - lo, rows)
+        self.shard.update_rows(global_row - lo, rows, generation=generation, newest_wins=newest_wins)
 
-    def update_rows_at(self, global_rows, rows):
+    def update_rows_at(self, global_rows, rows, generation=None, newest_wins=False):
         """rows fp16 [n, dim], global_rows int64 [n] (both on the device) -> those rows of the image this rank is searching
         (HipIndexShard.update_rows_at).  Rows of other ranks' shards, and -1, fall out of the shard's range and are skipped: every rank can
-        be handed the same gathered list.  Where a row is named twice the last occurrence wins."""
-        self.shard.update_rows_at(global_rows - self.shard.row_base, rows)
+        be handed the same gathered list.  Where a row is named twice the last occurrence wins.  `generation` / `newest_wins`: the
+        shard's stamp rule, applied to the occurrence that survived."""
+        self.shard.update_rows_at(global_rows - self.shard.row_base, rows, generation=generation, newest_wins=newest_wins)
+
+    # -- generation stamps (HipIndexShard.generation_stats over every rank's shard) ------------------------------------------------------
+    def generation_stats(self, now, global_rows=None):
+        """Ages of the index's rows at step count `now`: of all rows, or of `global_rows` (CUDA int64, the SAME tensor on every rank, e.g.
+        `last_search_rows`).  Every rank counts its own shard; the words are reduced over the index's group in at most two small
+        all-reduces -- ONE sum (count, sum of ages, rows from the future, the 32 bins) and ONE max (max age and the complement of min age)
+        -- issued by every rank whatever its shard holds, so the collective sequence stays static.  -> the same dict on every rank
+        (`generation_result`)."""
+        if self.shard is None:
+            raise RuntimeError("MIPS Index is not initialized")
+        mine = self.shard.generation_stats(now, global_rows)
+        rank, world = self._world()
+        if world == 1:
+            return mine
+        dist = torch.distributed
+        on_device = dist.get_backend(self.process_group) == "nccl"
+        place = (lambda t: t.to(self.shard.device)) if on_device else (lambda t: t)
+        sums = place(torch.tensor([mine["count"], mine["sum_age"], mine["from_future"]] + mine["histogram"], dtype=torch.int64))
+        # (ages are below 2^32; "no row" travels as the smallest complement, so one MAX reduces both extremes)
+        none = 1 << 32
+        ext = place(torch.tensor([mine["max_age"], none - min(mine["min_age"], none)], dtype=torch.int64))
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.process_group)
+        dist.all_reduce(ext, op=dist.ReduceOp.MAX, group=self.process_group)
+        sums, ext = sums.tolist(), ext.tolist()
+        min_age = _native.AUDIT_NONE if ext[1] == 0 else none - ext[1]
+        return generation_result([sums[0], sums[1], min_age, ext[0], sums[2]] + sums[3:])
+
+    def kept_newer(self):
+        """Rows of THIS rank's shard that newest-wins updates left alone since the last call (HipIndexShard.kept_newer: one host read)."""
+        return self.shard.kept_newer()
 
     def add_embed_data(self, all_embed_data):
         """Upload this rank's row shard (reference: emdr2_index.py:241-266; there: rank 0 uploads
@@ -965,7 +1109,8 @@ class DistributedBruteForceIndex(object):
     def load_flat_snapshot(self, path, audit=False):
         """Build the index from a snapshot written by `save_flat_file` at ANY world size and verify it: meta against the file's header
         and ids, then the device digest of what now stands in HBM (combined over the ranks) against the meta's.  A mismatch raises
-        ValueError.  `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
+        ValueError.  With generation stamps every row is stamped with the meta's `iteration` (0 if absent): stamps are not saved in
+        snapshots, so ages after a resume are a lower bound.  `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
         ValueError naming the non-zero words unless it is sound and canonical.  Returns the meta."""
         from emdr2_amd.data import index_snapshot as snap
         meta = snap.read_snapshot_meta(path)
@@ -974,7 +1119,11 @@ class DistributedBruteForceIndex(object):
             raise ValueError("snapshot rows have %d elements, the index %d" % (flat.dim, self.embed_size))
         if snap.ids_crc32(flat.ids) != meta.get("ids_crc32"):
             raise ValueError("index snapshot %s: the doc ids do not match the meta's checksum" % path)
-        self.add_flat_file(flat)
+        self._load_generation = min(max(int(meta.get("iteration", 0) or 0), 0), _native.GEN_MAX) if self.generations else 0
+        try:
+            self.add_flat_file(flat)
+        finally:
+            self._load_generation = 0
         got = snap.index_digest(self)
         want = (int(meta["digest_sum"], 16), int(meta["digest_xor"], 16))
         if got != want:
@@ -993,7 +1142,10 @@ class DistributedBruteForceIndex(object):
         lo, hi = shard_bounds(self.num_rows, world)[rank]
         self.shard = self._make_shard(self.embed_size, hi - lo, lo)
         if hi > lo:
-            self.shard.append_rows(rows[lo:hi])
+            if getattr(self.shard, "generation", None) is not None:
+                self.shard.append_rows(rows[lo:hi], generation=self._load_generation)
+            else:
+                self.shard.append_rows(rows[lo:hi])
             self.shard.set_ids(ids[lo:hi])
 
     def search_mips_index(self, query_embeds, top_k, reconstruct=True):

@@ -101,10 +101,14 @@ class IndexBuilder(object):
         self._barrier()
 
     # ---- MI355X-native: straight into the owning rank's spare index image ----------------------------------------------------
-    def refresh_batches(self, index):
+    def refresh_batches(self, index, generation=None):
         """Generator over this rank's work: each `next()` embeds one batch of the rank's own index rows and packs it into the spare
-        image, on the current stream.  Lets a caller interleave re-indexing with training steps (AsyncIndexBuilder)."""
-        index.begin_refresh()
+        image, on the current stream.  Lets a caller interleave re-indexing with training steps (AsyncIndexBuilder).  `generation`: the
+        stamp of the whole pass on an index that keeps generation stamps (the steps this model's weights have taken)."""
+        if generation is None:
+            index.begin_refresh()
+        else:
+            index.begin_refresh(generation=generation)
         for start, emb in self.embed_batches(index):
             index.refresh_rows(start, emb)
             yield emb.shape[0]
@@ -121,17 +125,21 @@ class IndexBuilder(object):
             self.track_and_report_progress(batch_size=end - start)
             yield start, emb
 
-    def build_into_index(self, index, in_place=False):
+    def build_into_index(self, index, in_place=False, generation=None):
         """Synchronous full refresh of this rank's shard followed by the swap (all ranks call it).  `in_place` (not in the reference):
         every embedded batch overwrites its rows of the image that is being searched (`index.update_rows`) -- no spare image, no swap;
-        a search issued between two batches would see rows of both generations."""
+        a search issued between two batches would see rows of both generations.  `generation`: the stamp of the rows on an index that
+        keeps generation stamps (required there in place; the swap stamps 0 without it)."""
         if in_place:
             for start, emb in self.embed_batches(index):
-                index.update_rows(start, emb)
+                if generation is None:
+                    index.update_rows(start, emb)
+                else:
+                    index.update_rows(start, emb, generation=generation)
             torch.cuda.current_stream().synchronize()
             self._barrier()
             return
-        for _ in self.refresh_batches(index):
+        for _ in self.refresh_batches(index, generation):
             pass
         torch.cuda.current_stream().synchronize()
         self._barrier()

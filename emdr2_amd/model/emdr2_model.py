@@ -54,7 +54,8 @@ class PreComputedEvidenceDocsRetriever(object):
             return
         self.mips_index = DistributedBruteForceIndex(embed_size=self.embedding_size, embed_data=self.evidence_embedder_obj,
                                                      use_gpu=getattr(self.args, "faiss_use_gpu", True),
-                                                     process_group=self.process_group)
+                                                     process_group=self.process_group,
+                                                     generations=bool(getattr(self.args, "index_generations", False)))
         self._barrier()
 
     def _resume_from_snapshot(self):
@@ -81,7 +82,7 @@ class PreComputedEvidenceDocsRetriever(object):
             if int(meta.get("iteration", 0)) > iteration:
                 raise ValueError("it was taken at iteration %d, the checkpoint at %d" % (int(meta.get("iteration", 0)), iteration))
             index = DistributedBruteForceIndex(embed_size=self.embedding_size, embed_data=None, use_gpu=getattr(args, "faiss_use_gpu", True),
-                                               process_group=self.process_group)
+                                               process_group=self.process_group, generations=bool(getattr(args, "index_generations", False)))
             index.load_flat_snapshot(path)
         except (OSError, ValueError) as exc:
             say("index snapshot %s not used (%s): loading %s" % (path, exc, args.embedding_path))

@@ -24,6 +24,14 @@ Snapshots (`--save-index-snapshot`, not in the reference): the reference's index
 would exist in HBM only.  With a `snapshot_writer` (data/index_snapshot.IndexSnapshotWriter, driven by train_e2eqa._train) the index just
 committed is exported to one flat file, a chunk per step boundary.  A snapshot still open when the next swap is due is finished first
 (`maybe_swap`): the image it reads becomes the spare at the swap, and the next pass clears the spare.
+
+Generations (`--index-generations`, not in the reference): on an index that keeps generation stamps every row this builder writes carries
+`snapshot_generation`, the number of optimizer steps that were complete when `start()` copied the weights.  The builder is told the step
+count at construction (`iteration=`) and by every `maybe_swap(iteration)`; the `pump()` at the top of the loop follows the previous
+boundary's `maybe_swap`, so the count it remembers is the right one when a pass ends inside `pump()` and the next snapshot is taken.  Swap
+mode stamps the whole spare image once per pass.  Rolling mode queues the generation with every staging tensor -- a pass can end while
+earlier batches are still queued -- and with `newest_wins` (--index-newest-wins) a row that holds a newer stamp, a written-back one, is
+left alone.
 """
 import copy
 
@@ -37,7 +45,8 @@ PACE_MARGIN = 0.9        # fraction of the reload interval a pass over the shard
 
 class AsyncIndexBuilder(IndexBuilder):
     def __init__(self, live_context_model, evidence_arena, index, seq_length_ret, cls_id, sep_id, pad_id=0, batch_size=128,
-                 log_interval=1000, index_reload_interval=500, batches_per_pump=None, process_group=None, in_place=False):
+                 log_interval=1000, index_reload_interval=500, batches_per_pump=None, process_group=None, in_place=False, iteration=0,
+                 newest_wins=False):
         snapshot = copy.deepcopy(live_context_model)
         for p in snapshot.parameters():
             p.requires_grad_(False)
@@ -48,7 +57,13 @@ class AsyncIndexBuilder(IndexBuilder):
         self.live = live_context_model
         self.index = index
         self.in_place = bool(in_place)
-        self._queued = []                                       # rolling mode: (first global row, staging rows, event) not yet applied
+        self.stamped = bool(getattr(index, "generations", False))  # the index keeps generation stamps: every write carries one
+        self.newest_wins = bool(newest_wins)
+        if self.newest_wins and not (self.stamped and self.in_place):
+            raise ValueError("newest_wins needs the rolling mode (in_place) and an index that keeps generation stamps")
+        self.steps_done = int(iteration)                        # optimizer steps completed, as last told (construction, maybe_swap)
+        self.snapshot_generation = self.steps_done              # ... when start() last copied the weights
+        self._queued = []                                       # rolling mode: (first global row, staging rows, event, generation) not yet applied
         self.passes = 0                                         # rolling mode: completed passes over the shard
         self.snapshot_writer = None                             # --save-index-snapshot: an IndexSnapshotWriter over `index` (train_e2eqa._train)
         self.log = lambda msg: print(msg, flush=True) if self.is_main_builder else None
@@ -75,7 +90,11 @@ class AsyncIndexBuilder(IndexBuilder):
                 for ps, pl in zip(self.model.parameters(), self.live.parameters()):
                     ps.copy_(pl)
                     ps.__dict__.pop("_emdr2_cache", None)
-            self._gen = self.embed_batches(self.index) if self.in_place else self.refresh_batches(self.index)
+            self.snapshot_generation = self.steps_done
+            if self.in_place:
+                self._gen = self.embed_batches(self.index)
+            else:
+                self._gen = self.refresh_batches(self.index, self.snapshot_generation if self.stamped else None)
         self.done_event = None
 
     def pump(self, n_batches=None):
@@ -102,6 +121,7 @@ class AsyncIndexBuilder(IndexBuilder):
         and restarted at once -- no collective: ranks finish on different steps and need not agree."""
         lo, hi = self.index.local_rows()
         staging, first, filled, finished = None, None, 0, False
+        generation = self.snapshot_generation                   # of the pass these batches belong to: start() below begins the next
         with torch.cuda.stream(self.stream):
             for _ in range(n):
                 try:
@@ -120,7 +140,7 @@ class AsyncIndexBuilder(IndexBuilder):
             if staging is not None:
                 event = torch.cuda.Event()
                 event.record(self.stream)
-                self._queued.append((first, staging[:filled], event))
+                self._queued.append((first, staging[:filled], event, generation))
         if finished:
             self.passes += 1
             self.start()
@@ -130,9 +150,12 @@ class AsyncIndexBuilder(IndexBuilder):
         """At a step boundary: everything pumped so far goes into the live image, in order, on the current stream.  What is applied at a
         step is a function of the step number alone -- never of how far the side stream happens to have got."""
         cur = torch.cuda.current_stream()
-        for first, staging, event in self._queued:
+        for first, staging, event, generation in self._queued:
             cur.wait_event(event)                               # the side stream has had the whole step: this rarely waits
-            self.index.update_rows(first, staging)
+            if self.stamped:
+                self.index.update_rows(first, staging, generation=generation, newest_wins=self.newest_wins)
+            else:
+                self.index.update_rows(first, staging)
             staging.record_stream(cur)                          # allocated on the side stream, consumed here: not reused before the update has run
         self._queued = []
 
@@ -142,6 +165,7 @@ class AsyncIndexBuilder(IndexBuilder):
     def maybe_swap(self, iteration, force=False):
         """At a step boundary: if the pass is complete (on every rank) and the reload interval has gone by, swap in the new image and
         start the next pass.  Returns True when the index was updated."""
+        self.steps_done = int(iteration)                        # (before anything below takes a weight snapshot)
         if self.in_place:
             # Rolling mode.  The rows go in at EVERY boundary; the return value keeps the reference's cadence on the rank-uniform interval
             # condition alone (the training loop logs and checkpoints on it: a collective save cannot be entered by some ranks only).

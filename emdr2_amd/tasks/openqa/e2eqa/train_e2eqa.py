@@ -203,14 +203,16 @@ def _save(iteration, model, optimizer, lr_scheduler):
                                   barrier=torch.distributed.barrier if world > 1 else None, args=args)
 
 
-def index_writeback(model, batch_size, topk):
+def index_writeback(model, batch_size, topk, generation=None, newest_wins=False):
     """--index-writeback, at a step boundary: the embeddings the step has just computed for the passages it retrieved
     (`EMDR2Model.take_writeback`) go into the index rows they were retrieved from (`update_rows_at`).  The list always has
     batch_size * topk entries, padded with row -1 (skipped): the short last batch of an epoch under --keep-last, empty retrieval slots,
     a step that kept nothing.  With more than one rank every rank gathers all ranks' lists -- ONE all-gather of the row numbers and ONE
     of the fp16 rows over the retriever's group, issued by every rank at every boundary so that the collective sequence stays static
     -- and applies the gathered list to its own shard: rows of other shards fall out of range there.  A passage retrieved by several
-    questions holds the embedding of the last (rank, question, slot) that names it, the same on every rank."""
+    questions holds the embedding of the last (rank, question, slot) that names it, the same on every rank.  `generation` (an index with
+    generation stamps: --index-generations): the stamp of the rows, the step count of the weights the forward ran with; `newest_wins`
+    (--index-newest-wins): rows that hold a newer stamp are left alone."""
     retriever = model.evidence_retriever
     dev = torch.device("cuda", torch.cuda.current_device())
     n = int(batch_size) * int(topk)
@@ -228,7 +230,33 @@ def index_writeback(model, batch_size, topk):
         # (as bytes: a gather moves bits, and not every transport knows fp16)
         torch.distributed.all_gather_into_tensor(all_embeds.view(torch.uint8), embeds.view(torch.uint8), group=retriever.process_group)
         rows, embeds = all_rows, all_embeds
-    retriever.mips_index.update_rows_at(rows, embeds)
+    if generation is None:
+        retriever.mips_index.update_rows_at(rows, embeds)
+    else:
+        retriever.mips_index.update_rows_at(rows, embeds, generation=generation, newest_wins=newest_wins)
+
+
+def writeback_generation(iteration):
+    """The stamp of the rows written back at the boundary after step `iteration`: that step's forward, which computed them, ran with the
+    weights of `iteration - 1` optimizer steps."""
+    return max(int(iteration) - 1, 0)
+
+
+def index_generation_line(index, iteration, retrieved):
+    """--index-generations, at a --log-interval boundary after every writer of the boundary: one line on rank 0.  `retrieved`: the
+    statistics of the rows the step's search returned, taken BEFORE the boundary's writers touched them, against the step count of the
+    weights the forward ran with.  The whole index is counted now, against `iteration`.  `generation_stats` is collective over the index's
+    group (two small all-reduces, at iterations that depend on --log-interval alone); `kept_newer` is one host read on this rank, and
+    the count printed is rank 0's shard's.  -> the whole-index statistics."""
+    whole = index.generation_stats(iteration)
+    kept = index.kept_newer()
+    line = "index generations at iteration %d: retrieved rows mean age %.2f max %d (%d rows) | whole index mean age %.2f max %d (%d rows) | " \
+           "kept newer %d" % (iteration, retrieved["mean_age"], retrieved["max_age"], retrieved["count"], whole["mean_age"], whole["max_age"],
+                              whole["count"], kept)
+    if whole["from_future"]:
+        line += " | %d rows stamped beyond iteration %d" % (whole["from_future"], iteration)
+    print_rank_0(line)
+    return whole
 
 
 def audit_index(index, iteration):
@@ -288,6 +316,8 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
     audited = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if audit_interval > 0 else None
     if audited is not None:
         audit_index(audited, args.iteration)          # what was loaded or restored, before the first step searches it
+    stamped = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if getattr(args, "index_generations", False) else None
+    newest_wins = bool(getattr(args, "index_newest_wins", False))
     start_epoch = args.iteration // args.train_iters_per_epoch
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
@@ -303,6 +333,11 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 indexer.pump()
             losses = train_step(forward_step, batch, model, optimizer, lr_scheduler, eos_id, guard=guard)
             iteration += 1
+            retrieved_ages = None
+            if stamped is not None and iteration % args.log_interval == 0 and stamped.last_search_rows is not None:
+                # the ages of the rows this step's search returned (the merged rows of all ranks' questions: the same list on every rank),
+                # as the search found them: before this boundary's writers, against the weights the forward ran with
+                retrieved_ages = stamped.generation_stats(iteration - 1, stamped.last_search_rows)
             if indexer is not None and indexer.maybe_swap(iteration):
                 print_rank_0("Training Group: MIPS Index Updated at iteration {}".format(iteration))
                 if args.save:
@@ -314,8 +349,18 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                     snapshots.begin(snapshot_path, {"iteration": iteration, "refreshes": indexer.refreshes,
                                                     "mode": "rolling" if indexer.in_place else "swap"})
             if getattr(args, "index_writeback", False):
-                # after the refresher's rows of this boundary (they come from an older snapshot of the weights): the write-back goes last and wins
-                index_writeback(model, args.batch_size, args.topk_retrievals)
+                # after the refresher's rows of this boundary (they come from an older snapshot of the weights): the write-back goes last and
+                # wins.  That settles ONE boundary.  Across boundaries nothing orders the two writers -- the refresher's pass reaches a
+                # written-back row tens of steps later, with weights up to a pass older -- unless --index-newest-wins: the write-back stamps
+                # iteration - 1, the weights the forward ran with, the refresher the step count of its snapshot, and either leaves a row with
+                # a higher stamp alone
+                if stamped is not None:
+                    index_writeback(model, args.batch_size, args.topk_retrievals, generation=writeback_generation(iteration),
+                                    newest_wins=newest_wins)
+                else:
+                    index_writeback(model, args.batch_size, args.topk_retrievals)
+            if retrieved_ages is not None:
+                index_generation_line(stamped, iteration, retrieved_ages)
             if audited is not None:
                 # after everything that writes the live image at this boundary, before the snapshot writer exports from it
                 maybe_audit_index(audited, iteration, audit_interval)

@@ -248,6 +248,52 @@ int emdr2_mips_update_rows_scattered(const void *rows_rm, const int64_t *row_ids
                                      void *workspace, size_t workspace_bytes, emdr2_stream_t stream);
 
 /*
+ * Generation stamps: one uint32 per local row of a shard, owned by the caller (device memory, n_rows_total words, 4-byte aligned) -- the
+ * GENERATION of a row is the number of optimizer steps the weights that produced its embedding had taken; values are below 2^31.  The
+ * library keeps no stamps of its own: a shard without them uses the entry points above, which are unchanged.
+ *   _update_rows_stamped, _update_rows_scattered_stamped   _update_rows / _update_rows_scattered with four more arguments in front of the
+ *                      stream: generation (the stamp array), gen, newest_wins, n_kept_newer (a device uint32 counter, or NULL).  For
+ *                      every destination row r -- of the range; of the list, invalid ids skipped as above and never counted --
+ *                        newest_wins == 0:  the row is written and generation[r] = gen;
+ *                        newest_wins != 0:  the row is written and stamped gen iff generation[r] <= gen; otherwise neither the image
+ *                                           row nor its stamp changes and *n_kept_newer, when given, goes up by one.
+ *                      Ties write: two writers of one generation keep "the last one wins".  The rule is non-strict on purpose: the row
+ *                      writers have one thread per 16-byte segment, and only under <= do all threads of a row take the same decision
+ *                      whether they read the stamp before or after the segment-0 thread has stored gen (csrc/mips_aux.hip).
+ *                      Everything behind the row write is the code of the unstamped forms over the same range / touched-block list
+ *                      (a block of the list form whose rows were all left alone is not listed): block norms, *emax_sq as the maximum of the
+ *                      whole table, the re-seal of the touched 256-row blocks, *nonfinite -- all recomputed from the image, so the
+ *                      contract stands: afterwards the shard is byte for byte a fresh build of the rows it now holds.  The same
+ *                      launches as the unstamped forms, nothing allocated, no host synchronisation; the counter is only ever added to
+ *                      (the caller clears and reads it).  EMDR2_E_BADARG in addition: a null or misaligned generation, a misaligned
+ *                      counter, gen >= 2^31.
+ *   _generation_stats  one pass over stamps, report = device uint64[EMDR2_GEN_WORDS], 8-byte aligned, cleared by the call itself.
+ *                      global_rows == NULL: all n_rows stamps (n_sel is ignored).  Otherwise the n_sel entries of global_rows (device
+ *                      int64) that fall into [row_base, row_base + n_rows): other entries -- negative ones, rows of other shards -- are not
+ *                      counted, a row named twice counts twice.  age = now - generation[r], taken as 0 where the stamp exceeds now.
+ *                         0  count         rows covered
+ *                         1  sum_age       sum of the ages
+ *                         2  min_age       ~0 when count == 0
+ *                         3  max_age
+ *                         4  from_future   stamps > now (should be 0: such a row claims weights that do not exist yet)
+ *                         5..36  histogram bin b = word 5 + b: bin 0 holds age 0, bin b ages in [2^(b-1), 2^b)
+ *                      Integer atomics behind per-workgroup LDS tallies: the report does not depend on the order of the visit.  Two
+ *                      launches on `stream`, nothing allocated, no host synchronisation.  n_rows == 0 or n_sel == 0: count 0, min_age ~0,
+ *                      the rest 0, nothing is read.  EMDR2_E_BADARG: a null or misaligned report, a null generation with n_rows > 0,
+ *                      n_rows < 0, row_base < 0, n_sel < 0 with a list.
+ */
+#define EMDR2_GEN_WORDS 37
+int emdr2_mips_update_rows_stamped(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, int64_t n_rows_total, void *tiled,
+                                   float *block_norm_sq, float *emax_sq, void *shadow, void *table, uint32_t *nonfinite,
+                                   uint32_t *generation, uint32_t gen, int newest_wins, uint32_t *n_kept_newer, emdr2_stream_t stream);
+int emdr2_mips_update_rows_scattered_stamped(const void *rows_rm, const int64_t *row_ids, int64_t n_upd, int dim, int64_t n_rows_total,
+                                             void *tiled, float *block_norm_sq, float *emax_sq, void *shadow, void *table,
+                                             uint32_t *nonfinite, void *workspace, size_t workspace_bytes, uint32_t *generation,
+                                             uint32_t gen, int newest_wins, uint32_t *n_kept_newer, emdr2_stream_t stream);
+int emdr2_mips_generation_stats(const uint32_t *generation, int64_t n_rows, int64_t row_base, const int64_t *global_rows, int64_t n_sel,
+                                uint32_t now, uint64_t *report, emdr2_stream_t stream);
+
+/*
  * Index audit: one streaming pass over a shard's LIVE images that re-checks the premises of the search's
  * proof from the stored bits and, separately, the "bit for bit a fresh build" contract of the derived structures -- emax_sq, the
  * block-norm table, the int8 shadow image and its {s_b, N_b, D_b} table, which pack_rows, seal_shadow, update_rows, update_rows_scattered
