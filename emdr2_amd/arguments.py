@@ -144,6 +144,14 @@ def get_parser():
                         'refresher\'s embedding from a snapshot taken up to a whole pass earlier.  Ties write, so within one generation the '
                         'last writer still wins.  A choice of semantics, not a tuning knob: without it a row holds whatever was written '
                         'LAST, with it whatever came from the NEWEST weights; the index is a fresh build of its rows either way')
+    g.add_argument('--index-refresh-oldest-first', action='store_true',
+                   help='(not in the reference; implies --index-generations; needs --async-indexer --index-refresh-in-place) the rolling '
+                        'refresher embeds, at every step, the OLDEST rows of its shard that are older than its weight snapshot -- chosen on '
+                        'the device from the generation stamps, lowest rows first among equal stamps -- instead of the next rows in row '
+                        'order.  No encoder forward is spent on a row that --index-writeback has stamped since the snapshot (which '
+                        '--index-newest-wins would refuse to overwrite anyway), and a pass ends as soon as no row is older than its '
+                        'snapshot instead of after a fixed count.  The pace (rows per step) is unchanged.  On an index with uniform '
+                        'stamps -- a fresh start, a resume -- the order is the row order.  Rank 0 prints one line per completed pass')
     g.add_argument('--context-embeddings-from-index', action='store_true',
                    help='(not in the reference; needs --no-context-embedder-training) take the embeddings of the batch-size x topk retrieved '
                         'passages from the index rows the search returned instead of running the frozen context encoder over them, in '
@@ -207,6 +215,11 @@ def parse_args(argv=None):
         if not (args.index_writeback or (args.async_indexer and args.index_refresh_in_place)):
             raise ValueError("--index-newest-wins needs an in-place writer of the index: --index-writeback or --async-indexer "
                              "--index-refresh-in-place (the swap refresher replaces whole images: there is nothing to arbitrate)")
+        args.index_generations = True
+    if args.index_refresh_oldest_first:
+        if not (args.async_indexer and args.index_refresh_in_place):
+            raise ValueError("--index-refresh-oldest-first needs the rolling refresher: --async-indexer --index-refresh-in-place (the swap "
+                             "refresher rebuilds whole images: there is no order to choose)")
         args.index_generations = True
     if args.audit_index_interval < 0:
         raise ValueError("--audit-index-interval must be >= 0")

@@ -489,6 +489,25 @@ int emdr2_mips_generation_stats(const uint32_t *generation, int64_t n_rows, int6
     return mips_launch_generation_stats(generation, n_rows, row_base, global_rows, global_rows ? n_sel : n_rows, now, report, (hipStream_t)stream);
 }
 
+// (row counts stay below 2^31: the kernels keep ranks and histogram words in 32 bits)
+int emdr2_mips_oldest_rows_workspace_bytes(int64_t n_rows, size_t *bytes)
+{
+    if (!bytes || n_rows < 0 || n_rows >= ((int64_t)1 << 31)) return EMDR2_E_BADARG;
+    *bytes = MIPS_OLDEST_WS_BYTES;
+    return EMDR2_OK;
+}
+
+int emdr2_mips_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t row_base, uint32_t below, int64_t n_want, int64_t *out_rows,
+                           uint64_t *out_info, void *workspace, size_t workspace_bytes, emdr2_stream_t stream)
+{
+    if (!out_info || ((uintptr_t)out_info & 7) || !workspace || ((uintptr_t)workspace & 15) || ((uintptr_t)generation & 3) || ((uintptr_t)out_rows & 7) ||
+        n_rows < 0 || n_rows >= ((int64_t)1 << 31) || row_base < 0 || n_want < 0 || n_want > n_rows || (n_rows > 0 && !generation) ||
+        (n_want > 0 && !out_rows))
+        return EMDR2_E_BADARG;
+    if (workspace_bytes < MIPS_OLDEST_WS_BYTES) return EMDR2_E_WORKSPACE;
+    return mips_launch_oldest_rows(generation, n_rows, row_base, below, n_want, out_rows, out_info, workspace, (hipStream_t)stream);
+}
+
 int emdr2_mips_audit(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const float *block_norm_sq,
                      const void *shadow, const void *table, uint64_t *report, emdr2_stream_t stream)
 {

@@ -93,6 +93,13 @@ int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t 
 #define MIPS_GEN_WORDS 37
 int mips_launch_generation_stats(const uint32_t *generation, int64_t n_rows, int64_t row_base, const int64_t *global_rows, int64_t n_items,
                                  uint32_t now, uint64_t *report, hipStream_t stream);
+// emdr2_mips_oldest_rows (mips_select.hip): the n_want oldest of the rows with generation[r] < below, as global rows in ascending order,
+// -1 behind them; out_info as documented in include/emdr2_mips.h.  Six launches at most, phases ordered by launch boundaries alone.
+// workspace: MIPS_OLDEST_WS_BYTES whatever n_rows is -- three digit histograms, the state words, one count pair per slab
+#define MIPS_OLDEST_MAX_SLABS 512
+#define MIPS_OLDEST_WS_BYTES ((2048 + 2048 + 1024 + 16 + 2 * MIPS_OLDEST_MAX_SLABS) * 4)
+int mips_launch_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t row_base, uint32_t below, int64_t n_want, int64_t *out_rows,
+                            uint64_t *out_info, void *workspace, hipStream_t stream);
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);

@@ -455,6 +455,7 @@ class HipIndexShard(object):
         self._refreshing = False                                   # between begin_refresh and commit_refresh
         self._block_norms = None                                   # max ||row||^2 per 256-row block of self.tiled (update_rows), built on first use
         self._scatter_ws = None                                    # workspace of update_rows_at (claim words + touched-block list), grown on demand
+        self._oldest_ws = None                                     # workspace of oldest_rows (digit histograms, per-slab counts), grown on demand
         # generation stamps of self.tiled (int32 storage of the device's uint32 words: values are below 2^31), of the refresh spare, and
         # the counter of rows that newest-wins updates left alone
         self.generation = torch.zeros(max(self.n_rows, 1), dtype=torch.int32, device=self.device) if generations else None
@@ -677,6 +678,35 @@ class HipIndexShard(object):
         -1 and other shards' rows are not counted, a row named twice counts twice.  One pass on the device, then ONE host read of the
         296-byte report -> dict (`generation_result`)."""
         return generation_result(self.generation_report(now, global_rows).tolist())
+
+    def oldest_rows(self, n, below):
+        """The `n` oldest rows of this shard among those stamped below `below` (csrc: emdr2_mips_oldest_rows) -> (rows, info): `rows`
+        CUDA int64 [n], the selected GLOBAL rows in ascending row order, -1 in every slot behind them; `info` CUDA int64 [4]: rows
+        selected, rows eligible (stamp < below), the largest stamp selected (-1: none), 0.  The oldest stamps first, the lowest rows
+        first among equal stamps -- so on a shard with uniform stamps below `below` the result is the first n rows.  `n` is clamped to
+        the shard's rows.  Enqueued on the current stream, no host read; the caller orders it against the writers of the stamps.
+        ValueError on a shard without stamps or still being filled, and for `below` outside [0, 2^31]."""
+        if self.generation is None:
+            raise ValueError("this shard keeps no generation stamps")
+        if self._filled != self.n_rows:
+            raise ValueError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
+        n, below = int(n), int(below)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if not 0 <= below <= _native.GEN_MAX + 1:
+            raise ValueError("below must be in [0, 2^31]")
+        n = min(n, self.n_rows)
+        nbytes = ctypes.c_size_t()
+        _native.check(self.lib.emdr2_mips_oldest_rows_workspace_bytes(self.n_rows, ctypes.byref(nbytes)), "oldest_rows_workspace_bytes")
+        if self._oldest_ws is None or self._oldest_ws.numel() < nbytes.value:
+            self._oldest_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        ws = self._oldest_ws
+        rows = torch.empty(n, dtype=torch.int64, device=self.device)
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        _native.check(self.lib.emdr2_mips_oldest_rows(self.generation.data_ptr(), self.n_rows, self.row_base, below, n,
+                                                      rows.data_ptr() if n else None, info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _native.stream_ptr()), "oldest_rows")
+        return rows, info
 
     def _check_update_rows(self, rows):
         if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_cuda:
@@ -1050,6 +1080,13 @@ class DistributedBruteForceIndex(object):
         sums, ext = sums.tolist(), ext.tolist()
         min_age = _native.AUDIT_NONE if ext[1] == 0 else none - ext[1]
         return generation_result([sums[0], sums[1], min_age, ext[0], sums[2]] + sums[3:])
+
+    def oldest_rows(self, n, below):
+        """The `n` oldest rows of THIS rank's shard among those stamped below `below`, as global rows in ascending order, -1 behind them,
+        and the selection's report (HipIndexShard.oldest_rows).  No collective: a rank refreshes its own rows."""
+        if self.shard is None:
+            raise RuntimeError("MIPS Index is not initialized")
+        return self.shard.oldest_rows(n, below)
 
     def kept_newer(self):
         """Rows of THIS rank's shard that newest-wins updates left alone since the last call (HipIndexShard.kept_newer: one host read)."""

@@ -32,6 +32,17 @@ boundary's `maybe_swap`, so the count it remembers is the right one when a pass 
 mode stamps the whole spare image once per pass.  Rolling mode queues the generation with every staging tensor -- a pass can end while
 earlier batches are still queued -- and with `newest_wins` (--index-newest-wins) a row that holds a newer stamp, a written-back one, is
 left alone.
+
+Oldest first (`oldest_first=True`, --index-refresh-oldest-first, not in the reference; rolling mode on a stamped index): the pass has no
+row cursor.  Every `pump()` asks the device for the `batches_per_pump * batch_size` OLDEST rows of the shard whose stamp is below the
+generation G of the pass's snapshot (`index.oldest_rows`: stamp ascending, row ascending among equal stamps, returned in ascending row
+order, -1 in the empty slots), embeds exactly those and queues them for the boundary, where `update_rows_at` writes them.  A row the
+write-back has stamped G or later is never selected, so no forward is spent on a row that newest-wins would refuse; a pass ends at the
+first boundary whose selection took every eligible row -- no row is then older than the snapshot -- instead of after a fixed count, and
+the next `pump()` takes a new snapshot.  Shapes are fixed and `pump()` reads nothing back: the empty slots of a pass's last pump are
+embedded with a valid doc id and skipped by the writer (`rows_padded`); the one host read, of the rows selected, is at the boundary,
+behind the update's own.  The selection is made from the stamps as the previous boundary's writers left them, so what a boundary writes
+is still a function of the step number alone.  On uniform stamps the order is the row order: the sequential pass.
 """
 import copy
 
@@ -46,7 +57,7 @@ PACE_MARGIN = 0.9        # fraction of the reload interval a pass over the shard
 class AsyncIndexBuilder(IndexBuilder):
     def __init__(self, live_context_model, evidence_arena, index, seq_length_ret, cls_id, sep_id, pad_id=0, batch_size=128,
                  log_interval=1000, index_reload_interval=500, batches_per_pump=None, process_group=None, in_place=False, iteration=0,
-                 newest_wins=False):
+                 newest_wins=False, oldest_first=False):
         snapshot = copy.deepcopy(live_context_model)
         for p in snapshot.parameters():
             p.requires_grad_(False)
@@ -61,10 +72,19 @@ class AsyncIndexBuilder(IndexBuilder):
         self.newest_wins = bool(newest_wins)
         if self.newest_wins and not (self.stamped and self.in_place):
             raise ValueError("newest_wins needs the rolling mode (in_place) and an index that keeps generation stamps")
+        self.oldest_first = bool(oldest_first)
+        if self.oldest_first and not (self.stamped and self.in_place):
+            raise ValueError("oldest_first needs the rolling mode (in_place) and an index that keeps generation stamps")
         self.steps_done = int(iteration)                        # optimizer steps completed, as last told (construction, maybe_swap)
         self.snapshot_generation = self.steps_done              # ... when start() last copied the weights
-        self._queued = []                                       # rolling mode: (first global row, staging rows, event, generation) not yet applied
+        # rolling mode, not yet applied: (first global row, staging rows, event, generation); oldest first: (global rows, staging rows,
+        # the selection's report, event, generation)
+        self._queued = []
         self.passes = 0                                         # rolling mode: completed passes over the shard
+        # oldest first: rows chosen / empty slots embedded for nothing, in all and in the current pass; whether the last boundary ended it
+        self.rows_selected = self.rows_padded = 0
+        self._pass_selected = self._pass_padded = 0
+        self._pass_over = False
         self.snapshot_writer = None                             # --save-index-snapshot: an IndexSnapshotWriter over `index` (train_e2eqa._train)
         self.log = lambda msg: print(msg, flush=True) if self.is_main_builder else None
         self.index_reload_interval = index_reload_interval
@@ -91,7 +111,9 @@ class AsyncIndexBuilder(IndexBuilder):
                     ps.copy_(pl)
                     ps.__dict__.pop("_emdr2_cache", None)
             self.snapshot_generation = self.steps_done
-            if self.in_place:
+            if self.oldest_first:
+                self._gen = None                                # no cursor: every pump asks the device which rows are oldest
+            elif self.in_place:
                 self._gen = self.embed_batches(self.index)
             else:
                 self._gen = self.refresh_batches(self.index, self.snapshot_generation if self.stamped else None)
@@ -119,6 +141,8 @@ class AsyncIndexBuilder(IndexBuilder):
         """Rolling mode: embed up to n batches on the side stream into ONE contiguous staging tensor and queue it, with an event, for the
         next step boundary.  Returns True when this call reached the end of the shard: the builder has then taken the next weight snapshot
         and restarted at once -- no collective: ranks finish on different steps and need not agree."""
+        if self.oldest_first:
+            return self._pump_oldest(n)
         lo, hi = self.index.local_rows()
         staging, first, filled, finished = None, None, 0, False
         generation = self.snapshot_generation                   # of the pass these batches belong to: start() below begins the next
@@ -146,9 +170,66 @@ class AsyncIndexBuilder(IndexBuilder):
             self.start()
         return finished
 
+    def _pump_oldest(self, n):
+        """Oldest first: ONE selection of the n * batch_size oldest rows below the pass's generation, on the side stream behind everything
+        the current stream has queued (the previous boundary's writers have stored the stamps it reads); their doc ids; their
+        embeddings, a batch at a time, into one staging tensor; queued with the selection's report for the next boundary.  Fixed shapes,
+        no host read: an empty slot (-1) is embedded with the shard's first doc id and skipped by the writer.  Returns False: that a
+        pass has ended is only known at the boundary (`_apply_oldest`), and the call after it takes the next snapshot."""
+        if self._pass_over:
+            self._pass_over = False
+            self.start()
+        lo, hi = self.index.local_rows()
+        shard = self.index.shard
+        generation = self.snapshot_generation
+        n_slots = min(n * self.batch_size, hi - lo)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            rows, info = self.index.oldest_rows(n_slots, below=generation)
+            local = (rows - lo).clamp_(min=0)
+            doc_ids = shard.ids[local] if shard.ids is not None else (local + (lo + 1)).to(torch.int32)
+            staging = torch.empty((n_slots, shard.dim), dtype=torch.float16, device=rows.device)
+            for b in range(0, n_slots, self.batch_size):
+                emb = self.embed(doc_ids[b:b + self.batch_size])
+                staging[b:b + emb.shape[0]].copy_(emb)
+                self.track_and_report_progress(batch_size=emb.shape[0])
+            event = torch.cuda.Event()
+            event.record(self.stream)
+            self._queued.append((rows, staging, info, event, generation))
+        return False
+
+    def _apply_oldest(self):
+        """`_apply_queued` of the oldest-first form: the selected rows go in through the scattered writer, then the selection's report is
+        read -- one host read, on a stream the update's own non-finite read-back synchronises anyway.  A selection that took EVERY
+        eligible row (always the case when it took fewer than it was asked for) leaves no row older than the pass's snapshot: the pass is
+        over.  Returns True when one ended."""
+        cur = torch.cuda.current_stream()
+        ended = False
+        for rows, staging, info, event, generation in self._queued:
+            cur.wait_event(event)
+            self.index.update_rows_at(rows, staging, generation=generation, newest_wins=self.newest_wins)
+            for t in (rows, staging, info):
+                t.record_stream(cur)
+            n_selected, n_eligible = info[:2].tolist()
+            self.rows_selected += n_selected
+            self.rows_padded += rows.shape[0] - n_selected
+            self._pass_selected += n_selected
+            self._pass_padded += rows.shape[0] - n_selected
+            if n_selected == n_eligible and not self._pass_over:
+                self._pass_over = ended = True
+                self.passes += 1
+                self.log("oldest-first pass %d complete at iteration %d: %d rows embedded, %d slots padded"
+                         % (self.passes, self.steps_done, self._pass_selected, self._pass_padded))
+                self._pass_selected = self._pass_padded = 0
+        self._queued = []
+        return ended
+
     def _apply_queued(self):
         """At a step boundary: everything pumped so far goes into the live image, in order, on the current stream.  What is applied at a
-        step is a function of the step number alone -- never of how far the side stream happens to have got."""
+        step is a function of the step number alone -- never of how far the side stream happens to have got.  Returns True when the
+        boundary ended an oldest-first pass."""
+        if self.oldest_first:
+            return self._apply_oldest()
         cur = torch.cuda.current_stream()
         for first, staging, event, generation in self._queued:
             cur.wait_event(event)                               # the side stream has had the whole step: this rarely waits
@@ -158,6 +239,7 @@ class AsyncIndexBuilder(IndexBuilder):
                 self.index.update_rows(first, staging)
             staging.record_stream(cur)                          # allocated on the side stream, consumed here: not reused before the update has run
         self._queued = []
+        return False
 
     def ready(self):
         return self._gen is None and self.done_event is not None and self.done_event.query()
@@ -172,7 +254,7 @@ class AsyncIndexBuilder(IndexBuilder):
             self._apply_queued()
             while force:                                        # drain the current pass, a pump at a time (the staging tensor stays small)
                 done = self._pump_in_place(self.batches_per_pump)
-                self._apply_queued()
+                done = self._apply_queued() or done             # (oldest first: the boundary, not the pump, finds the pass over)
                 if done:
                     break
             if not force and iteration < self.last_reload_iteration + self.index_reload_interval:

@@ -98,7 +98,8 @@ def open_retrieval_generative_qa(dataset_cls, arena=None, embed_data=None):
                                  bert_tokenizer.cls, bert_tokenizer.sep, bert_tokenizer.pad, batch_size=args.indexer_batch_size,
                                  log_interval=args.indexer_log_interval, index_reload_interval=args.index_reload_interval,
                                  in_place=args.index_refresh_in_place, iteration=args.iteration,
-                                 newest_wins=bool(getattr(args, "index_newest_wins", False)) and args.index_refresh_in_place)
+                                 newest_wins=bool(getattr(args, "index_newest_wins", False)) and args.index_refresh_in_place,
+                                 oldest_first=bool(getattr(args, "index_refresh_oldest_first", False)))
 
     return train(train_valid_datasets_provider, lambda: model_provider(args, bert_tokenizer, t5_tokenizer, arena, embed_data),
                  end_of_epoch_callback_provider=metrics_provider, end_of_training_callback_provider=metrics_provider,

@@ -294,6 +294,37 @@ int emdr2_mips_generation_stats(const uint32_t *generation, int64_t n_rows, int6
                                 uint32_t now, uint64_t *report, emdr2_stream_t stream);
 
 /*
+ * Oldest rows: which rows of a shard a refresher should embed next, chosen on the device from the stamps alone.
+ *   _oldest_rows       generation: the n_rows stamps of the shard.  A local row r is ELIGIBLE when generation[r] < below (below = the
+ *                      generation of the weights about to embed it: a row that is not older than they are gains nothing).  The eligible
+ *                      rows are ordered by (stamp ascending, row ascending), a total order; the SELECTED SET is the first
+ *                      min(n_want, n_eligible) rows of it: the oldest stamps, and among the rows that share the cut stamp the
+ *                      lowest-numbered ones.
+ *                        out_rows   device int64[n_want], 8-byte aligned: the selected set as GLOBAL rows, row_base + r, in ASCENDING ROW
+ *                                   order (the scattered writer's touched-block list stays short; with uniform stamps the list is the
+ *                                   range row_base .. row_base + n_want - 1); every slot behind the set receives -1, which
+ *                                   _update_rows_scattered skips
+ *                        out_info   device uint64[4], 8-byte aligned, cleared by the call itself:
+ *                                     0  n_selected
+ *                                     1  n_eligible
+ *                                     2  the largest stamp selected, ~0 when nothing was selected
+ *                                     3  0
+ *                      A radix select over the stamps (per-workgroup LDS histograms, integer atomics) and an ordered compaction over
+ *                      per-workgroup slabs of consecutive rows: the result is a function of the stamps alone, not of the order the
+ *                      workgroups run in nor of the grid.  No workgroup waits on another: the phases are separate launches, six at most,
+ *                      on `stream`; nothing allocated, no host synchronisation.  The caller orders the call against writers of the
+ *                      stamps.  workspace: device memory, 16-byte aligned, at least _oldest_rows_workspace_bytes(n_rows) bytes; its
+ *                      contents need not be kept, nor cleared, between calls.
+ *                      n_want == 0: the report only, out_rows may be NULL.  n_rows == 0: words 0, 1, 3 are 0 and word 2 is ~0, nothing
+ *                      is read.  below == 0: nothing is eligible.  EMDR2_E_BADARG: a null or misaligned out_info, workspace or out_rows
+ *                      (null only with n_want > 0), a misaligned generation or a null one with n_rows > 0, n_rows < 0 or >= 2^31,
+ *                      row_base < 0, n_want < 0, n_want > n_rows; EMDR2_E_WORKSPACE: workspace_bytes too small.
+ */
+int emdr2_mips_oldest_rows_workspace_bytes(int64_t n_rows, size_t *bytes);
+int emdr2_mips_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t row_base, uint32_t below, int64_t n_want,
+                           int64_t *out_rows, uint64_t *out_info, void *workspace, size_t workspace_bytes, emdr2_stream_t stream);
+
+/*
  * Index audit: one streaming pass over a shard's LIVE images that re-checks the premises of the search's
  * proof from the stored bits and, separately, the "bit for bit a fresh build" contract of the derived structures -- emax_sq, the
  * block-norm table, the int8 shadow image and its {s_b, N_b, D_b} table, which pack_rows, seal_shadow, update_rows, update_rows_scattered
