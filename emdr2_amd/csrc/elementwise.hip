@@ -594,7 +594,7 @@ __global__ void __launch_bounds__(256) embedding_bwd_kernel(const long long *ids
     for (int i = threadIdx.x; i < H; i += 256) {
         float g = bf2f(dout[t * H + i]);
         if (drop_p > 0.f) g = emdr2_keep(rh, (uint32_t)i, thr) ? g * ik : 0.f;
-        atomicAdd(&dW[id * H + i], g);
+        if (g != 0.f) atomicAdd(&dW[id * H + i], g);         // a dropped or zero element adds nothing: x + (+0.0) would turn a -0.0 into +0.0
     }
 }
 

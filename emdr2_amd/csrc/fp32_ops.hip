@@ -223,6 +223,7 @@ __global__ void __launch_bounds__(256) emb_bwd_f32_kernel(const long long *ids, 
     float *w = dW + ids[t] * H, *pp = dP + (t % S) * H, *tt = dT ? dT + types[t] * H : nullptr;
     for (int i = lane; i < H; i += 64) {
         const float g = dout[t * H + i];
+        if (g == 0.f) continue;                              // nothing to add: an element without a term keeps its bits (x + (+0.0) turns -0.0 into +0.0)
         atomicAdd(w + i, g); atomicAdd(pp + i, g);
         if (tt) atomicAdd(tt + i, g);
     }

@@ -103,8 +103,17 @@ def ln_reference(x, gamma, beta, eps, dy=None, dres=None):
     return r
 
 
-def ln_bounds(r, c=C_BF16, mant_bits=7):
-    """y, mean, rstd (+ dx, dgamma, dbeta).  c / mant_bits describe the format y and dx are stored in."""
+def ln_bounds(r, c=C_BF16, mant_bits=7, mean_terms=False, recursive_rows=0):
+    """y, mean, rstd (+ dx, dgamma, dbeta).  c / mant_bits describe the format y and dx are stored in.
+    mean_terms: weigh the two row means of dx = rstd (g - m1 - xhat m2) by the magnitudes of THEIR terms, mean |g| and mean |g xhat|,
+    instead of by their values |m1|, |m2|.  The values cancel (m1 = mean_j g_j), while whatever sums H fp32 terms errs by about
+    u mean |g|: with c = C_BF16 that is far below one store and nobody sees it, with c = C_F32 one row in a few hundred has |m1| below
+    mean |g| / 600 and the bound by value collapses under ANY fp32 sum (tests/test_elementwise_ref_cpu.py: on const0 at
+    1,031 x 768 the fp32 formula scores 167 and fp32 torch 42).  The fp32 tests pass True; the bf16 tests keep the bound as it was.
+    recursive_rows: dgamma is summed over that many rows RECURSIVELY in fp32 (one atomic per row, csrc/fp32_ops.hip), so its relative
+    constant is max(C_F32, (rows + 2) U32), the (n + 2) u bound of a recursive sum (tests/embedding_ref.py).  C_F32 = 64 U32 assumes a
+    tree: on 1,031 `alternating` rows with a constant dy the terms of a column are all alike, every add rounds the same way, and the
+    recursive sum is 90 u off -- 1.41 of C_F32's bound on the MI355X, and likewise in a row-by-row fp32 loop on the CPU."""
     rs = r.rstd[:, None]
     exh = C_CENTRE * rs * (r.x.abs() + r.mean.abs()[:, None])            # what an fp32 mean leaves uncertain in xhat
     B = {"y": c * ((r.xhat * r.gamma).abs() + r.beta.abs()) + r.gamma.abs() * exh + _floor(r.y, mant_bits),
@@ -112,12 +121,16 @@ def ln_bounds(r, c=C_BF16, mant_bits=7):
          "rstd": C_F32 * r.rstd + _floor(r.rstd, 23)}
     if r.dy is not None:
         ag = r.g.abs()
-        terms = rs * (ag + r.m1.abs() + r.xhat.abs() * r.m2.abs())
+        if mean_terms:
+            terms = rs * (ag + ag.mean(-1, keepdim=True) + r.xhat.abs() * (r.g * r.xhat).abs().mean(-1, keepdim=True))
+        else:
+            terms = rs * (ag + r.m1.abs() + r.xhat.abs() * r.m2.abs())
         if r.dres is not None:
             terms = terms + r.dres.abs()
         centre = rs * (exh * r.m2.abs() + r.xhat.abs() * (ag * exh).mean(-1, keepdim=True))
         B["dx"] = c * terms + centre + _floor(r.dx, mant_bits)
-        B["dgamma"] = C_F32 * (r.dy * r.xhat).abs().sum(0) + (r.dy.abs() * exh).sum(0) + _floor(r.dgamma, 23)
+        cg = max(C_F32, (recursive_rows + 2.0) * U32)
+        B["dgamma"] = cg * (r.dy * r.xhat).abs().sum(0) + (r.dy.abs() * exh).sum(0) + _floor(r.dgamma, 23)
         B["dbeta"] = C_F32 * r.dy.abs().sum(0) + _floor(r.dbeta, 23)
     return B
 
@@ -174,6 +187,22 @@ def ln_torch_f32(x, gamma, beta, eps, dy, dres, store_bf16=True):
     rstd = torch.rsqrt(x.float().var(-1, unbiased=False) + eps)
     rnd = bf if store_bf16 else (lambda t: t)
     return {"y": rnd(y.detach()), "mean": mean, "rstd": rstd, "dx": rnd(dx), "dgamma": g.grad, "dbeta": b.grad}
+
+
+def ln_formula_f32(x, gamma, beta, eps, dy, dres):
+    """The op as csrc/fp32_ops.hip states it, in fp32 torch: mean, centred sum of squares, dx = rstd (g - m1 - xhat m2) (+ dres), column
+    sums of dy xhat and dy.  (torch.nn.functional.layer_norm's own fp32 backward computes dx from x, not from x - mean, and leaves the
+    fp32 bounds on rows whose mean dwarfs their spread: ln_torch_f32 is the fp32 reference of the other families only.)"""
+    x, gamma, beta, dy = x.float(), gamma.float(), beta.float(), dy.float()
+    mean = x.mean(-1, keepdim=True)
+    xc = x - mean
+    rstd = torch.rsqrt((xc * xc).mean(-1, keepdim=True) + eps)
+    xhat = xc * rstd
+    g = dy * gamma
+    dx = rstd * (g - g.mean(-1, keepdim=True) - xhat * (g * xhat).mean(-1, keepdim=True))
+    if dres is not None:
+        dx = dx + dres.float()
+    return {"y": xhat * gamma + beta, "mean": mean[:, 0], "rstd": rstd[:, 0], "dx": dx, "dgamma": (dy * xhat).sum(0), "dbeta": dy.sum(0)}
 
 
 # ---- log-softmax + gather -------------------------------------------------------------------------------------------------------------

@@ -130,6 +130,72 @@ def test_torch_f32_layernorm_within_bounds_two_laps(fam):
     _report("ln %s rows=16393" % fam, R.worst_all(R.ln_torch_f32(x, gamma, beta, EPS, dy, dres), ref, R.ln_bounds(ref)))
 
 
+# fp32 constants (the validation path, tests/test_fp32_path_edges_gpu.py): c = C_F32, mant_bits = 23, mean_terms = True.  Two fp32
+# implementations are held to them: the formula as csrc/fp32_ops.hip states it (every family, every quantity), and dx of torch's own
+# fp32 layer_norm on the families whose |mean| / std is at most 8 or whose rows are constant.  torch's backward forms dx from x, not
+# from x - mean, so its error grows with that ratio, and its forward has a variance algorithm of its own (y up to 1.5 bounds, dgamma
+# 1.4): what it scores elsewhere is printed, not asserted -- it is no reference there.
+LN_TORCH_F32_FAMILIES = ("randn", "offset8", "const0", "const1", "const256", "alternating", "tiny")
+
+
+@pytest.mark.parametrize("rows", [1, 5, 1031])
+@pytest.mark.parametrize("H", [8, 63, 264, 768])
+def test_fp32_layernorm_within_the_fp32_bounds(H, rows):
+    worst_formula, worst_torch, worst_other = {}, {}, {}
+    for fam in R.LN_X_FAMILIES:
+        for dyfam in R.LN_DY_FAMILIES:
+            x, gamma, beta, dy, dres = R.ln_inputs(fam, dyfam, rows, H, _gen(rows * 7 + H))
+            for dr in (None, dres):
+                ref = R.ln_reference(x, gamma, beta, EPS, dy, dr)
+                B = R.ln_bounds(ref, R.C_F32, 23, mean_terms=True)
+                pairs = [(worst_formula, R.ln_formula_f32(x, gamma, beta, EPS, dy, dr)),
+                         (worst_torch if fam in LN_TORCH_F32_FAMILIES else worst_other, R.ln_torch_f32(x, gamma, beta, EPS, dy, dr, store_bf16=False))]
+                for into, got in pairs:
+                    for n, v in R.worst_all(got, ref, B).items():
+                        if v[0] > into.get(n, (-1.0,))[0]:
+                            into[n] = v
+    print("[ew-ref] fp32 ln rows=%d H=%d torch outside its families (not asserted): " % (rows, H) + " ".join("%s=%.2f" % (n, r[0]) for n, r in worst_other.items()))
+    _report("fp32 ln rows=%d H=%d formula" % (rows, H), worst_formula)
+    print("[ew-ref] fp32 ln rows=%d H=%d torch on its families (dx asserted): " % (rows, H) + " ".join("%s=%.2f" % (n, r[0]) for n, r in worst_torch.items()))
+    _report("fp32 ln rows=%d H=%d torch" % (rows, H), {"dx": worst_torch["dx"]})
+
+
+@pytest.mark.parametrize("fam,H", [("const0", 768), ("tiny", 768), ("const0", 8)])
+def test_dx_bound_by_the_values_of_its_means_cannot_be_met_in_fp32(fam, H):
+    """ln_bounds without mean_terms at the fp32 constant: m1 = mean_j g_j cancels on some of 1,031 rows, and both fp32 implementations miss
+    c rstd |m1| there while they stay within half the bound that weighs the mean by mean |g|."""
+    worst = {"formula": 0.0, "torch": 0.0, "formula_terms": 0.0, "torch_terms": 0.0}
+    for dyfam in R.LN_DY_FAMILIES:
+        x, gamma, beta, dy, dres = R.ln_inputs(fam, dyfam, 1031, H, _gen(1031 * 7 + H))
+        ref = R.ln_reference(x, gamma, beta, EPS, dy, dres)
+        by_value, by_terms = R.ln_bounds(ref, R.C_F32, 23)["dx"], R.ln_bounds(ref, R.C_F32, 23, mean_terms=True)["dx"]
+        for name, got in (("formula", R.ln_formula_f32(x, gamma, beta, EPS, dy, dres)), ("torch", R.ln_torch_f32(x, gamma, beta, EPS, dy, dres, store_bf16=False))):
+            worst[name] = max(worst[name], R.worst(got["dx"], ref.dx, by_value)[0])
+            worst[name + "_terms"] = max(worst[name + "_terms"], R.worst(got["dx"], ref.dx, by_terms)[0])
+    print("[ew-ref] fp32 dx %s H=%d: by value formula %.1f torch %.1f; by terms formula %.2f torch %.2f"
+          % (fam, H, worst["formula"], worst["torch"], worst["formula_terms"], worst["torch_terms"]))
+    assert worst["formula"] > 1.0 and worst["torch"] > 1.0
+    assert worst["formula_terms"] <= 0.5 and worst["torch_terms"] <= 0.5
+
+
+def test_recursive_fp32_column_sum_of_1031_like_rows_needs_the_recursive_constant():
+    """dgamma of `alternating` rows with a constant dy at H = 63: the terms of a column are all alike.  Summed row by row in fp32 (what one
+    atomic per row does) the sum leaves C_F32's bound and stays within half of max(C_F32, (rows + 2) U32); torch's pairwise sum stays
+    within C_F32's."""
+    rows, H = 1031, 63
+    x, gamma, beta, dy, dres = R.ln_inputs("alternating", "const", rows, H, _gen(rows * 7 + H))
+    ref = R.ln_reference(x, gamma, beta, EPS, dy, None)
+    got = R.ln_formula_f32(x, gamma, beta, EPS, dy, None)
+    terms = dy.float() * ((x.float() - got["mean"][:, None]) * got["rstd"][:, None])
+    acc = torch.zeros(H)
+    for i in range(rows):
+        acc = acc + terms[i]
+    tree, rec = R.ln_bounds(ref, R.C_F32, 23, mean_terms=True)["dgamma"], R.ln_bounds(ref, R.C_F32, 23, mean_terms=True, recursive_rows=rows)["dgamma"]
+    ratios = {"recursive/C_F32": R.worst(acc, ref.dgamma, tree), "recursive/recursive": R.worst(acc, ref.dgamma, rec), "pairwise/C_F32": R.worst(got["dgamma"], ref.dgamma, tree)}
+    print("[ew-ref] fp32 dgamma alternating/const 1031 x 63: " + " ".join("%s=%.3f" % (n, r[0]) for n, r in ratios.items()))
+    assert ratios["recursive/C_F32"][0] > 1.0 and ratios["recursive/recursive"][0] <= 0.5 and ratios["pairwise/C_F32"][0] <= 0.5
+
+
 LSE_CASES = [(fam, V, rows, False) for fam in R.LSE_FAMILIES for V in (1, 7, 255, 257, 1000) for rows in (1, 5)] + \
             [(fam, V, 5, True) for fam in R.LSE_FAMILIES for V in (255, 257, 1000)]
 
