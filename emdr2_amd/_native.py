@@ -55,6 +55,7 @@ SIGNATURES = {
     "emdr2_mips_seal_shadow": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "emdr2_mips_search_shadow": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_shadow_launches": (_i32, []),
+    "emdr2_mips_search_plan": (_i32, [_i64, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_block_norm_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
     "emdr2_mips_block_norms": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp]),
     "emdr2_mips_update_rows": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -198,6 +199,22 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise NativeError("%s failed: %s (%d)" % (what, _ERRORS.get(rc, "unknown error"), rc))
+
+
+SCAN_ENGINES = ("DENSE", "LOCKSTEP", "PERSISTENT_F16", "PERSISTENT_I8")        # EMDR2_SCAN_* of include/emdr2_mips.h, in code order
+PLAN_MAX_SEGMENTS = 32
+
+
+def search_plan(n_rows, n_q, dim, k, shadow_min_rows=-1, cus=0):
+    """emdr2_mips_search_plan: the segment schedule of one search pass of n_q <= 512 queries (csrc/mips_plan.h; host arithmetic, no GPU
+    needed; cus = 0: this device's) -> ([(row_begin, row_end, engine name, select_after, prog_slot), ...], pack_q8)"""
+    n, q8 = ctypes.c_int(), ctypes.c_int()
+    end = (_i64 * PLAN_MAX_SEGMENTS)()
+    eng, sel, slot = ((ctypes.c_int32 * PLAN_MAX_SEGMENTS)() for _ in range(3))
+    check(lib().emdr2_mips_search_plan(n_rows, n_q, dim, k, shadow_min_rows, cus, PLAN_MAX_SEGMENTS, ctypes.byref(n), end, eng, sel, slot,
+                                       ctypes.byref(q8)), "search_plan")
+    begin = [0] + list(end[:n.value])
+    return [(begin[i], end[i], SCAN_ENGINES[eng[i]], bool(sel[i]), slot[i]) for i in range(n.value)], bool(q8.value)
 
 
 def stream_ptr(stream=None):

@@ -29,7 +29,7 @@
 #define EXP_ENV_INT(name, dflt) (dflt)
 #define EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
 #define EXP_MIPS_COUPLE() true
-#define EXP_MIPS_SCAN_VARIANT(mode, variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc) if (false) {} else
+#define EXP_MIPS_SCAN_VARIANT(variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc)   /* may take a LOCKSTEP segment */
 #define EXP_SCAN8_TAU(p, tauv, qt)
 #define EXP_SCAN8_LATE_START(P, hq)
 #endif

@@ -31,7 +31,43 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Tuning / ablation switches are read from the environment ONLY in -DEMDR2_EXPERIMENTS builds (`make exp`, used by tools/); the production
 // library always runs the defaults, so a stray variable cannot change (or, with the ablations, corrupt) results.
-#define env_int(name, dflt) EXP_ENV_INT(name, dflt)           /* the product build: the default, always */
+// `product`: the defaults in either build (emdr2_mips_search_plan).  false: a knob out of range.
+bool search_knobs(SearchKnobs *kn, bool product = false)
+{
+#define KNOB(name, dflt) (product ? (dflt) : EXP_ENV_INT(name, dflt))
+    kn->seg0 = KNOB("EMDR2_MIPS_SEG0", 8192) / 512 * 512;
+    kn->growth = KNOB("EMDR2_MIPS_GROWTH", 8);               // r04: 8 (was 16): with cheaper selects a tighter threshold for the next segment pays (tools/mips_timeline.py)
+    kn->growth_i8 = KNOB("EMDR2_MIPS_GROWTH_I8", 2);
+    kn->margin_i8 = (float)KNOB("EMDR2_MIPS_MARGIN_PCT", 25) * 0.01f;
+    kn->force_variant = KNOB("EMDR2_MIPS_VARIANT", -1);
+    kn->cus = KNOB("EMDR2_MIPS_GRID", cu_count());
+    kn->scan_kernel = KNOB("EMDR2_MIPS_KERNEL", 1);          // 1 = lockstep v1, 2 = ping-pong
+    kn->ablate = KNOB("EMDR2_MIPS_ABLATE", 0);
+    kn->tune = KNOB("EMDR2_MIPS_TUNE", 17);
+    kn->couple = product || EXP_MIPS_COUPLE();
+#undef KNOB
+    return kn->seg0 >= 512 && kn->seg0 <= (int)CAPQ - 512 && kn->growth >= 2 && kn->growth_i8 >= 2;
+}
+
+// the timing bracket of one scan segment (emdr2_mips_set_timing): one event pair and the segment's row count
+int timing_begin(hipStream_t stream, bool *timed)
+{
+    *timed = g_timing.enabled && g_timing.n < TIMING_SLOTS;
+    if (!*timed) return 0;
+    while (g_timing.created <= g_timing.n) {
+        if (hipEventCreate(&g_timing.ev[2 * g_timing.created]) != hipSuccess || hipEventCreate(&g_timing.ev[2 * g_timing.created + 1]) != hipSuccess)
+            return EMDR2_E_LAUNCH;
+        ++g_timing.created;
+    }
+    return hipEventRecord(g_timing.ev[2 * g_timing.n], stream) == hipSuccess ? 0 : EMDR2_E_LAUNCH;
+}
+
+int timing_end(hipStream_t stream, int64_t rows)
+{
+    if (hipEventRecord(g_timing.ev[2 * g_timing.n + 1], stream) != hipSuccess) return EMDR2_E_LAUNCH;
+    g_timing.rows[g_timing.n++] = rows;
+    return 0;
+}
 
 struct Workspace {
     char *q_frag;
@@ -39,6 +75,13 @@ struct Workspace {
     float *qnorm, *tau;
     unsigned *count;       // [512] main-list counts, then [8][512] sub-list counts, [512] pending counts, then the pair-progress counters
     uint2 *cand, *cand8, *pend;
+    unsigned *count8() const { return count + 512; }
+    unsigned *pcount() const { return count + 9 * 512; }
+    unsigned *prog0() const { return count + 10 * 512; }
+    // the int8 query image and the per-query constants live where the fragment-tiled query image of the experiment kernels would (half its
+    // size + 8 KiB)
+    char *q8_tiled() const { return q_frag; }
+    float *qc(int dim) const { return (float *)(q_frag + (size_t)(dim / 64) * 512 * 64); }
 };
 
 size_t carve(char *base, int dim, Workspace *w)
@@ -150,10 +193,93 @@ int emdr2_mips_workspace_bytes(int n_q, int dim, int k, size_t *bytes)
     return EMDR2_OK;
 }
 
-static int variant_for(int nq) { return nq <= 128 ? 2 : (nq <= 256 ? 1 : 0); }
-static const int kBM[3] = {128, 256, 512};
-static const int kBN[3] = {512, 256, 128};
+// The start of a pass: query images and norms; thresholds, counts, flags -- and the sub-list counts, pending counts and pair-progress counters
+// of the persistent scan launches -- in one launch
+static int prepare_pass(const SearchPlan &plan, const SearchKnobs &kn, const Workspace &w, const uint16_t *qp, int nqp, int dim, uint32_t *flags,
+                        hipStream_t stream)
+{
+    PrepareParams pp;
+    pp.queries = qp;
+    pp.n_q = nqp;
+    pp.dim = dim;
+    pp.bn = plan.bn;
+    pp.q_tiled = w.q_tiled;
+    pp.qnorm = w.qnorm;
+    pp.tau = w.tau;
+    pp.count = w.count;
+    pp.flags = flags;
+    pp.dense_count = (unsigned)plan.seg[0].row_end;
+    pp.zero = w.count8();
+    pp.n_zero = 9 * 512 + (plan.variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0);
+    pp.q8_tiled = plan.pack_q8 ? w.q8_tiled() : nullptr;
+    pp.qc = w.qc(dim);
+    int rc;
+    if ((rc = mips_launch_prepare(pp, stream))) return rc;
+    EXP_MIPS_PACK_QUERIES_FRAG(plan.variant, kn.scan_kernel, qp, nqp, dim, w, stream, rc)
+    return 0;
+}
 
+// The segments of a pass as planned: each on its engine, a triage launch behind an int8 segment, a select launch where the plan says so.
+// A launcher that answers -4 for the engine the plan chose contradicts the plan, which asked the launcher's own predicate: an error like any other.
+static int scan_segments(const SearchPlan &plan, const SearchKnobs &kn, const Workspace &w, const void *tiled, int64_t n_rows, int dim, const uint16_t *qp,
+                         int nqp, uint32_t *flags, const Shadow *shadow, hipStream_t stream)
+{
+    ScanParams sp;
+    sp.e_tiled = (const char *)tiled;
+    sp.q_tiled = w.q_tiled;
+    sp.tau = w.tau;
+    sp.cand = w.cand;
+    sp.count = w.count;
+    sp.flags = flags;
+    sp.dense_out = nullptr;
+    sp.nch = dim / 32;
+    sp.n_rows = (int)n_rows;
+    sp.n_q = nqp;
+    sp.capq = CAPQ;
+    sp.cand8 = w.cand8;
+    sp.count8 = w.count8();
+    sp.dense_row0 = 0;
+    sp.tune = kn.tune;
+    sp.trace = (unsigned long long *)w.cand + (size_t)511 * CAPQ; // scratch tail of the candidate area (ABL 9 only)
+    for (int i = 0; i < plan.n_segments; ++i) {
+        const SearchSegment &s = plan.seg[i];
+        sp.tile_begin = (int)(s.row_begin / plan.bm);
+        sp.tile_end = (int)((s.row_end + plan.bm - 1) / plan.bm);
+        const int tiles = sp.tile_end - sp.tile_begin;
+        const int grid = tiles < kn.cus ? tiles : kn.cus;
+        unsigned *const prog = s.prog_slot >= 0 ? w.prog0() + (size_t)SCAN8_PROG_UINTS * s.prog_slot : nullptr;
+        bool timed;
+        int rc;
+        if ((rc = timing_begin(stream, &timed))) return rc;
+        switch (s.engine) {
+        case DENSE:
+            rc = mips_launch_scan(plan.variant, 1, sp, grid, stream);
+            break;
+        case LOCKSTEP:
+            EXP_MIPS_SCAN_VARIANT(plan.variant, kn.ablate, kn.scan_kernel, sp, w, grid, s.row_end, n_rows, s.row_begin, stream, rc)
+            rc = mips_launch_scan(plan.variant, 0, sp, grid, stream);
+            break;
+        case PERSISTENT_F16:
+            rc = mips_launch_scan8(sp, plan.bn, s.row_begin, s.row_end, kn.cus, prog, stream);
+            break;
+        case PERSISTENT_I8:
+            rc = mips_launch_scan8i(sp, shadow->image, shadow->table, w.q8_tiled(), w.qc(dim), plan.bn, s.row_begin, s.row_end, kn.cus, prog, stream);
+            if (rc == 0) ++g_shadow_launches;
+            break;
+        }
+        if (rc) return rc;
+        if (timed && (rc = timing_end(stream, s.row_end - s.row_begin))) return rc;
+        // survivors of an int8 segment carry integer sums: the likely winners get their fp32 scores before the select reads them, the others
+        // wait in the pending list behind an upper bound
+        if (s.engine == PERSISTENT_I8 &&
+            (rc = mips_launch_triage(sp, qp, (unsigned)plan.kp, shadow->table, w.qc(dim), w.pend, w.pcount(), kn.margin_i8, stream)))
+            return rc;
+        if (s.select_after && (rc = mips_launch_select(w.cand, w.count, w.cand8, w.count8(), w.tau, flags, CAPQ, plan.kp, nqp, stream))) return rc;
+    }
+    return 0;
+}
+
+// One search = per pass of up to 512 queries: plan (mips_plan.h), prepare, the plan's segments, finalize.
 static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq,
                        const void *queries, int n_q, int k, const int32_t *ids, void *out_dist, int32_t *out_idx,
                        int64_t *out_row, uint32_t *out_flags, void *workspace, size_t workspace_bytes,
@@ -166,130 +292,17 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
     Workspace w;
     if (carve((char *)workspace, dim, &w) > workspace_bytes) return EMDR2_E_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
-    const int kp = k <= 56 ? 64 : 128;
-    const int seg0 = env_int("EMDR2_MIPS_SEG0", 8192) / 512 * 512;
-    const int growth = env_int("EMDR2_MIPS_GROWTH", 8);    // r04: 8 (was 16): with cheaper selects a tighter threshold for the next segment pays (tools/mips_timeline.py)
-    const int growth_i8 = env_int("EMDR2_MIPS_GROWTH_I8", 2); // ... of the segments that run on the int8 shadow image
-    // an int8 survivor is re-scored right after its segment iff estimate + margin * eps reaches tau (mips_scan8i.hip triage_kernel): speed only
-    const float margin_i8 = (float)env_int("EMDR2_MIPS_MARGIN_PCT", 25) * 0.01f;
-    if (seg0 < 512 || seg0 > (int)CAPQ - 512 || growth < 2 || growth_i8 < 2) return EMDR2_E_BADARG;
-    const int force_variant = env_int("EMDR2_MIPS_VARIANT", -1);
-    const int cus = env_int("EMDR2_MIPS_GRID", cu_count());
-    const int scan_kernel = env_int("EMDR2_MIPS_KERNEL", 1); // 1 = lockstep v1, 2 = ping-pong
-    const int ablate = env_int("EMDR2_MIPS_ABLATE", 0);      // timing experiments only
+    SearchKnobs kn;
+    if (!search_knobs(&kn)) return EMDR2_E_BADARG;
 
     for (int q0 = 0; q0 < n_q; q0 += EMDR2_MAX_QUERIES_PER_PASS) {
         const int nqp = (n_q - q0) < EMDR2_MAX_QUERIES_PER_PASS ? (n_q - q0) : EMDR2_MAX_QUERIES_PER_PASS;
-        int variant = variant_for(nqp);
-        if (force_variant >= 0 && force_variant <= 2 && kBN[force_variant] >= nqp) variant = force_variant;
-        const int BM = kBM[variant], BN = kBN[variant];
         const uint16_t *qp = (const uint16_t *)queries + (size_t)q0 * dim;
         int rc;
-        const int64_t dense_rows = n_rows < seg0 ? n_rows : seg0;
-        unsigned *const count8 = w.count + 512, *const pcount = count8 + 8 * 512, *const prog0 = pcount + 512;
-        // the int8 query image and the per-query constants live where the fragment-tiled query image of the experiment kernels would
-        // (half its size + 8 KiB); packed only if some segment of this search can take the int8 path
-        const bool shadow_ok = shadow && variant <= 1 && scan_kernel == 1 && (dim % 256) == 0 && n_rows - dense_rows >= shadow->min_rows;
-        char *const q8_tiled = w.q_frag;
-        float *const qc = (float *)(w.q_frag + (size_t)(dim / 64) * 512 * 64);
-        // query images and norms; thresholds, counts, flags -- and the sub-list counts, pending counts and pair-progress counters of the
-        // persistent scan launches -- in one launch
-        PrepareParams pp;
-        pp.queries = qp;
-        pp.n_q = nqp;
-        pp.dim = dim;
-        pp.bn = BN;
-        pp.q_tiled = w.q_tiled;
-        pp.qnorm = w.qnorm;
-        pp.tau = w.tau;
-        pp.count = w.count;
-        pp.flags = out_flags + q0;
-        pp.dense_count = (unsigned)dense_rows;
-        pp.zero = count8;
-        pp.n_zero = 9 * 512 + (variant == 0 ? 8 * (size_t)SCAN8_PROG_UINTS : 0);
-        pp.q8_tiled = shadow_ok ? q8_tiled : nullptr;
-        pp.qc = qc;
-        if ((rc = mips_launch_prepare(pp, stream))) return rc;
-        EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc)
-
-        ScanParams sp;
-        sp.e_tiled = (const char *)tiled;
-        sp.q_tiled = w.q_tiled;
-        sp.tau = w.tau;
-        sp.cand = w.cand;
-        sp.count = w.count;
-        sp.flags = out_flags + q0;
-        sp.dense_out = nullptr;
-        sp.nch = dim / 32;
-        sp.n_rows = (int)n_rows;
-        sp.n_q = nqp;
-        sp.capq = CAPQ;
-        sp.cand8 = w.cand8;
-        sp.count8 = count8;
-        sp.dense_row0 = 0;
-        sp.tune = env_int("EMDR2_MIPS_TUNE", 17);
-        sp.trace = (unsigned long long *)w.cand + (size_t)511 * CAPQ; // scratch tail of the candidate area (ABL 9 only)
-
-        int scan8_launches = 0;                              // (fp16 and int8 launches share the progress counters zeroed above: both count)
-        const bool couple = EXP_MIPS_COUPLE();
-        int64_t done = 0, seg_end = dense_rows;
-        int mode = 1;
-        bool pending = false;                                // some int8 segment has run: its deferred survivors wait in w.pend
-        while (done < n_rows) {
-            sp.tile_begin = (int)(done / BM);
-            sp.tile_end = (int)((seg_end + BM - 1) / BM);
-            const int tiles = sp.tile_end - sp.tile_begin;
-            const int grid = tiles < cus ? tiles : cus;
-            const bool timed = g_timing.enabled && g_timing.n < TIMING_SLOTS;
-            if (timed) {
-                while (g_timing.created <= g_timing.n) {
-                    if (hipEventCreate(&g_timing.ev[2 * g_timing.created]) != hipSuccess ||
-                        hipEventCreate(&g_timing.ev[2 * g_timing.created + 1]) != hipSuccess)
-                        return EMDR2_E_LAUNCH;
-                    ++g_timing.created;
-                }
-                if (hipEventRecord(g_timing.ev[2 * g_timing.n], stream) != hipSuccess) return EMDR2_E_LAUNCH;
-            }
-            bool int8_segment = false;
-            EXP_MIPS_SCAN_VARIANT(mode, variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc)
-            {
-                rc = -4;
-                if (mode == 0 && variant <= 1 && scan_kernel == 1) {
-                    unsigned *prog = (couple && scan8_launches < 8) ? prog0 + (size_t)SCAN8_PROG_UINTS * scan8_launches : nullptr;
-                    if (shadow_ok && seg_end - done >= shadow->min_rows) {
-                        rc = mips_launch_scan8i(sp, shadow->image, shadow->table, q8_tiled, qc, BN, done, seg_end, cus, prog, stream);
-                        if (rc == 0) { int8_segment = true; ++g_shadow_launches; }
-                    }
-                    if (rc == -4) rc = mips_launch_scan8(sp, BN, done, seg_end, cus, prog, stream);
-                    if (rc == 0) ++scan8_launches;
-                }
-                if (rc == -4) rc = mips_launch_scan(variant, mode, sp, grid, stream);
-            }
-            if (rc) return rc;
-            if (timed) {
-                if (hipEventRecord(g_timing.ev[2 * g_timing.n + 1], stream) != hipSuccess) return EMDR2_E_LAUNCH;
-                g_timing.rows[g_timing.n] = seg_end - done;
-                ++g_timing.n;
-            }
-            // survivors of an int8 segment carry integer sums: the likely winners get their fp32 scores before the select reads them, the others
-            // wait in the pending list behind an upper bound
-            if (int8_segment) {
-                if ((rc = mips_launch_triage(sp, qp, (unsigned)kp, shadow->table, qc, w.pend, pcount, margin_i8, stream))) return rc;
-                pending = true;
-            }
-            // (the select after the LAST segment runs inside the finalize launch -- after a select of its own when something is pending: the
-            // deferred pass, the first thing that launch does then, wants the tightest tau)
-            if ((seg_end < n_rows || pending) &&
-                (rc = mips_launch_select(w.cand, w.count, w.cand8, count8, w.tau, out_flags + q0, CAPQ, kp, nqp, stream)))
-                return rc;
-            done = seg_end;
-            // the next segment ends at `growth` times the rows done so far -- at `growth_i8` times once a segment of that length runs on the int8
-            // image: its survivors are ~6 x the fp16 filter's and each costs a 1.5 KB gather in the re-score, so a fresher threshold pays there
-            const int64_t next_boundary = done * ((shadow_ok && done * (growth_i8 - 1) >= shadow->min_rows) ? growth_i8 : growth);
-            seg_end = next_boundary < n_rows ? next_boundary : n_rows;
-            if (n_rows - seg_end < seg_end / 2) seg_end = n_rows; // do not leave a short tail for a last launch (a launch + a select cost ~70 us)
-            mode = 0;
-        }
+        SearchPlan plan;
+        if (mips_plan_search(n_rows, nqp, dim, k, shadow ? shadow->min_rows : -1, kn, &plan)) return EMDR2_E_UNSUPPORTED;
+        if ((rc = prepare_pass(plan, kn, w, qp, nqp, dim, out_flags + q0, stream))) return rc;
+        if ((rc = scan_segments(plan, kn, w, tiled, n_rows, dim, qp, nqp, out_flags + q0, shadow, stream))) return rc;
 
         FinalizeParams fp;
         fp.e_tiled = (const char *)tiled;
@@ -297,7 +310,7 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         fp.cand = w.cand;
         fp.count = w.count;
         fp.cand8 = w.cand8;
-        fp.count8 = count8;
+        fp.count8 = w.count8();
         fp.tau = w.tau;
         fp.qnorm = w.qnorm;
         fp.emax_sq = emax_sq;
@@ -313,12 +326,35 @@ static int search_impl(const void *tiled, int64_t n_rows, int dim, int64_t row_b
         fp.dim = dim;
         fp.n_q = nqp;
         fp.k = k;
-        fp.kp = kp;
+        fp.kp = plan.kp;
         fp.capq = CAPQ;
-        fp.pend = pending ? w.pend : nullptr;
-        fp.pcount = pcount;
+        fp.pend = plan.any_pending ? w.pend : nullptr;
+        fp.pcount = w.pcount();
         if ((rc = mips_launch_finalize(fp, true, stream))) return rc;
     }
+    return EMDR2_OK;
+}
+
+static_assert(DENSE == EMDR2_SCAN_DENSE && LOCKSTEP == EMDR2_SCAN_LOCKSTEP && PERSISTENT_F16 == EMDR2_SCAN_PERSISTENT_F16 &&
+              PERSISTENT_I8 == EMDR2_SCAN_PERSISTENT_I8, "the engine codes of include/emdr2_mips.h");
+int emdr2_mips_search_plan(int64_t n_rows, int n_q, int dim, int k, int64_t shadow_min_rows, int cus, int max_segments, int *n_segments,
+                           int64_t *row_end, int32_t *engine, int32_t *select_after, int32_t *prog_slot, int *pack_q8)
+{
+    if (!n_segments || !row_end || !engine || !select_after || !prog_slot || !pack_q8) return EMDR2_E_BADARG;
+    if (n_q < 1 || n_q > EMDR2_MAX_QUERIES_PER_PASS || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(n_rows, dim) || cus < 0) return EMDR2_E_BADARG;
+    SearchKnobs kn;
+    SearchPlan plan;
+    search_knobs(&kn, true);
+    if (cus) kn.cus = cus;
+    if (mips_plan_search(n_rows, n_q, dim, k, shadow_min_rows, kn, &plan) || plan.n_segments > max_segments) return EMDR2_E_BADARG;
+    for (int i = 0; i < plan.n_segments; ++i) {
+        row_end[i] = plan.seg[i].row_end;
+        engine[i] = plan.seg[i].engine;
+        select_after[i] = plan.seg[i].select_after;
+        prog_slot[i] = plan.seg[i].prog_slot;
+    }
+    *n_segments = plan.n_segments;
+    *pack_q8 = plan.pack_q8;
     return EMDR2_OK;
 }
 
@@ -620,10 +656,8 @@ int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const vo
     Workspace w;
     if (carve((char *)workspace, dim, &w) > workspace_bytes) return EMDR2_E_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
-    int variant = variant_for(n_q);
-    const int force_variant = env_int("EMDR2_MIPS_VARIANT", -1);
-    if (force_variant >= 0 && force_variant <= 2 && kBN[force_variant] >= n_q) variant = force_variant;
-    const int BM = kBM[variant], BN = kBN[variant];
+    const int variant = mips_scan_variant(n_q, EXP_ENV_INT("EMDR2_MIPS_VARIANT", -1));
+    const int BM = kMipsBM[variant], BN = kMipsBN[variant];
     int rc;
     PrepareParams pp = {};                                   // (the query image alone: a dense scan has no thresholds and no lists)
     pp.queries = queries;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mips_device.h"
+#include "mips_plan.h"
 
 #define CAPQ 16384u /* candidate slots per query (8 B each) */
 #define SUBCAP 1024u /* ... plus 8 sub-lists of this many per query, one per XCD, filled by the persistent scan (mips_scan8.hip) */
@@ -31,6 +32,7 @@ struct ScanParams {
 // variant: 0 = 128 rows x 512 queries, 1 = 256 x 256, 2 = 512 x 128 ; mode: see mips_scan.hip
 int mips_launch_scan(int variant, int mode, const ScanParams &p, int grid, hipStream_t stream);
 // production filter scan (mode 0) for 256- / 512-row query images in the persistent-GEMM pipeline (mips_scan8.hip); -4 = not covered
+// (mips_persistent_covers, and mips_int8_covers for mips_launch_scan8i: mips_plan.h)
 // `prog`: SCAN8_PROG_UINTS zeroed uints per launch (pair progress counters, one 256-byte line each) or nullptr
 #define SCAN8_PROG_UINTS (256 * 64)
 int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t row_end, int cus, unsigned *prog, hipStream_t stream);

@@ -357,21 +357,19 @@ __global__ void __launch_bounds__(512) mips_scan8_kernel(typename OPS::Params P)
 }
 
 // Launch of one instance on rows [row_begin, row_end) for a query image of `bn` = 256 or 512 rows.  The caller has filled P.s (and what its
-// Params adds); the item partition is made here.  -4 = not covered
+// Params adds); the item partition is made here.  -4 = not covered (mips_plan.h)
 template <class OPS>
 int s8_launch(typename OPS::Params &P, int bn, int64_t row_begin, int64_t row_end, int cus, unsigned *prog, hipStream_t stream)
 {
     const ScanParams &p = P.s;
-    if ((bn != 256 && bn != 512) || (p.nch & 3) || p.nch < 4 || (row_begin & 255) || row_end <= row_begin || !p.cand8 || !p.count8) return -4;
+    if (!mips_persistent_covers(bn, p.nch, cus, row_begin, row_end) || !p.cand8 || !p.count8) return -4;   // (short segments stay on the non-persistent kernel)
     P.prog = prog;
     P.bn = bn; P.halves = bn / 256;
     P.t_begin = (int)(row_begin >> 8);
     P.t_end = (int)((row_end + 255) >> 8);
     P.last_stripe = (int)((p.n_rows + STRIPE_ROWS - 1) / STRIPE_ROWS) - 1;
     P.total = (P.t_end - P.t_begin) * P.halves;
-    int grid = cus & ~15;                                     // a multiple of 8 XCDs x an even number of workgroups each
-    if (grid < 16) grid = 16;
-    if (P.total < grid) return -4;                            // short segments stay on the non-persistent kernel
+    const int grid = mips_persistent_grid(cus);
     P.per = ((P.total + 7) >> 3);
     P.per = (P.per + 1) & ~1;                                 // both halves of a tile on the same XCD
     constexpr int LDS = 2 * S8_BUF + S8_QCAP * 16 + 128;

@@ -43,7 +43,7 @@ struct Scan8Fp16 {
 
 } // namespace
 
-// Filter scan (mode 0) of rows [row_begin, row_end) for a query image of `bn` = 256 or 512 rows; -4 = not covered (the caller uses mips_scan.hip)
+// Filter scan (mode 0) of rows [row_begin, row_end) for a query image of `bn` = 256 or 512 rows; -4 = not covered (mips_persistent_covers, mips_plan.h: the plan gives such a segment to mips_scan.hip)
 int mips_launch_scan8(const ScanParams &p, int bn, int64_t row_begin, int64_t row_end, int cus, unsigned *prog, hipStream_t stream)
 {
     Scan8Params P;

@@ -214,11 +214,11 @@ int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, c
 }
 
 // Filter scan (mode 0) of rows [row_begin, row_end) on the shadow image, for a query image of `bn` = 256 or 512 rows; `p` is the fp16 scan's
-// parameter block (p.nch = dim / 32).  -4 = not covered (the caller uses the fp16 kernels)
+// parameter block (p.nch = dim / 32).  -4 = not covered (mips_int8_covers, mips_plan.h: the plan gives such a segment to the fp16 kernels)
 int mips_launch_scan8i(const ScanParams &p, const void *e8_tiled, const float *blk, const void *q8_tiled, const float *qc, int bn, int64_t row_begin,
                        int64_t row_end, int cus, unsigned *prog, hipStream_t stream)
 {
-    if (p.nch & 7) return -4;
+    if (!mips_int8_covers(bn, p.nch, cus, row_begin, row_end)) return -4;
     Scan8iParams P;
     P.s = p;
     P.s.e_tiled = (const char *)e8_tiled;

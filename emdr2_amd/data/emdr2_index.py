@@ -431,7 +431,6 @@ class HipIndexShard(object):
     `generation_stats` reads it.  Off (the default): nothing is allocated and every entry point behaves as it always did."""
 
     SHADOW_MIN_ROWS = 1 << 19
-    _DENSE_ROWS = 8192                                             # rows of the dense first segment of a search (csrc/mips_api.hip)
 
     def __init__(self, dim, n_rows, row_base, device=None, shadow=True, shadow_min_rows=None, generations=False):
         self.lib = _native.lib()
@@ -448,7 +447,8 @@ class HipIndexShard(object):
         self._xws = None
         self._filled = 0
         self.shadow_min_rows = int(self.SHADOW_MIN_ROWS if shadow_min_rows is None else shadow_min_rows)
-        self._want_shadow = bool(shadow) and self.dim % 256 == 0 and self.n_rows - self._DENSE_ROWS >= self.shadow_min_rows >= 1
+        # (whether a full pass would pack the int8 query image: the search's own plan, csrc/mips_plan.h)
+        self._want_shadow = bool(shadow) and self.shadow_min_rows >= 1 and _native.search_plan(self.n_rows, 512, self.dim, 1, self.shadow_min_rows)[1]
         self._shadow = None                                        # (int8 image, block table) sealed against self.tiled, or None
         self._shadow_buf = self._spare_shadow_buf = None           # their storage (kept across seals), for self.tiled / the refresh spare
         self._spare = None                                         # the second fp16 image of a swap refresh (begin_refresh)

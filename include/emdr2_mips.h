@@ -207,6 +207,22 @@ int emdr2_mips_search_shadow(const void *tiled, int64_t n_rows, int dim, int64_t
 int emdr2_mips_shadow_launches(void);
 
 /*
+ * The segment schedule of one search pass, read-only (host arithmetic alone: no launch, no GPU needed): what emdr2_mips_search and its
+ * siblings would run for n_q queries (1..EMDR2_MAX_QUERIES_PER_PASS: one pass) over n_rows rows, as planned by csrc/mips_plan.h with the
+ * library's built-in knobs.  shadow_min_rows < 0: a shard without a shadow image, else the argument of _search_shadow.  cus: the compute
+ * units to plan for, 0 = those of the current device.  Segment i covers rows [row_end[i-1], row_end[i]) (from 0; the last ends at n_rows)
+ * on engine[i], select_after[i] != 0: a select launch follows it, prog_slot[i]: the set of pair-progress counters a persistent launch
+ * uses, or -1.  *pack_q8 != 0: the int8 query image is packed, i.e. the shard needs its shadow image.  n_rows == 0: no segments.
+ * EMDR2_E_BADARG, with nothing written: a null output, a shape no search takes, cus < 0, or more segments than max_segments (32 always do).
+ */
+#define EMDR2_SCAN_DENSE 0           /* the first segment: every score written */
+#define EMDR2_SCAN_LOCKSTEP 1        /* the filter scan of mips_scan.hip */
+#define EMDR2_SCAN_PERSISTENT_F16 2  /* the persistent filter scan (mips_scan8.hip) */
+#define EMDR2_SCAN_PERSISTENT_I8 3   /* ... on the int8 shadow image (mips_scan8i.hip) */
+int emdr2_mips_search_plan(int64_t n_rows, int n_q, int dim, int k, int64_t shadow_min_rows, int cus, int max_segments, int *n_segments,
+                           int64_t *row_end, int32_t *engine, int32_t *select_after, int32_t *prog_slot, int *pack_q8);
+
+/*
  * In-place row updates of a FINISHED shard (the device counterpart of the reference store's add_block_data(..., allow_overwrite=True)):
  * every derived structure is left exactly as a fresh build of the same rows would leave it.
  *   _block_norm_bytes  size of the block-norm table: one float per 256-row block of the padded image

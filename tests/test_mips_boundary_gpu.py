@@ -6,7 +6,8 @@ Every case compares a shard with a shadow image with the same shard fp16-only on
 
 Dimension 256, a 16,384-row int8 threshold, row_base != 0, permuted ids.  A filter segment runs on the int8 image only if it also has at
 least as many work items (256 rows x 256 queries) as the persistent scan has workgroups; `_int8_segments` restates the schedule of
-csrc/mips_api.hip for the device's CU count and every case asserts the number of int8 launches it predicts.  On a 256-CU device:
+csrc/mips_plan.h for the device's CU count and every case asserts the number of int8 launches it predicts, which is also the number of
+PERSISTENT_I8 segments in the library's own plan (emdr2_mips_search_plan).  On a 256-CU device:
   24,575 rows (8,192 + 16,383): the rest behind the dense segment is one row short of the threshold -- no int8 image is packed, nothing pends;
   24,581 rows (8,192 + 16,384 + 5): the int8 query image IS packed, but the one segment (65 row tiles) is too short for the persistent scan;
   73,733 rows (8,192 + 65,536 + 5): exactly one int8 segment at every query count -- its triage is the only one, the finish follows directly;
@@ -113,6 +114,9 @@ def _check(sa, sb, q, k, n):
     torch.cuda.synchronize()
     ran, want = _launches() - n0, _int8_segments(n, q.shape[0])
     assert ran == want, "int8 scan launches: %d, the schedule says %d" % (ran, want)
+    from emdr2_amd import _native
+    planned = sum(s[2] == "PERSISTENT_I8" for s in _native.search_plan(n, q.shape[0], DIM, k, MIN_ROWS, _native.lib().emdr2_device_cu_count())[0])
+    assert planned == want == ran, "int8 segments: the plan says %d, the restated schedule %d, %d ran" % (planned, want, ran)
     b = sb.search(q, k, exact_fallback=False)
     over = torch.nonzero(b[3] & 2).flatten().tolist()
     assert not over, "the fp16-only shard overflowed (queries %s): the case tests the fallback, not the boundaries" % over

@@ -47,11 +47,12 @@ static inline int exp_env_int(const char *name, int dflt) { const char *v = gete
 #define EXP_MIPS_PACK_QUERIES_FRAG(variant, scan_kernel, qp, nqp, dim, w, stream, rc) \
     if (variant == 0 && scan_kernel == 5 && (rc = mips_launch_pack_queries_frag(qp, nqp, dim, (w).q_frag, stream))) return rc;
 #define EXP_MIPS_COUPLE() (exp_env_int("EMDR2_MIPS_COUPLE", 1) != 0)
-#define EXP_MIPS_SCAN_VARIANT(mode, variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc) \
-    if (mode == 0 && variant == 0 && ablate > 0) rc = mips_launch_scan_ablate(ablate, sp, grid, stream); \
-    else if (mode == 0 && variant == 0 && scan_kernel == 5) { ScanParams sq = sp; sq.q_tiled = (w).q_frag; rc = mips_launch_scan_q8(ablate == 53 ? 3 : 0, sq, grid, stream); } \
-    else if (mode == 0 && scan_kernel == 2) rc = mips_launch_scan_pp(variant, 3, sp, grid, stream); \
-    else if (mode == 0 && scan_kernel == 4) rc = mips_launch_scan_pp(variant, seg_end == n_rows && done >= n_rows / 16 ? 4 : 3, sp, grid, stream); \
+// (in front of the launch of a LOCKSTEP segment of the plan: with any of these switches set, mips_plan.h gives every segment behind the dense one that engine)
+#define EXP_MIPS_SCAN_VARIANT(variant, ablate, scan_kernel, sp, w, grid, seg_end, n_rows, done, stream, rc) \
+    if (variant == 0 && ablate > 0) rc = mips_launch_scan_ablate(ablate, sp, grid, stream); \
+    else if (variant == 0 && scan_kernel == 5) { ScanParams sq = sp; sq.q_tiled = (w).q_frag; rc = mips_launch_scan_q8(ablate == 53 ? 3 : 0, sq, grid, stream); } \
+    else if (scan_kernel == 2) rc = mips_launch_scan_pp(variant, 3, sp, grid, stream); \
+    else if (scan_kernel == 4) rc = mips_launch_scan_pp(variant, seg_end == n_rows && done >= n_rows / 16 ? 4 : 3, sp, grid, stream); \
     else
 #define EXP_SCAN8_TAU(p, tauv, qt) if ((p).tune & 128) tauv[qt] = __builtin_inff();        /* timing experiment: the filter never fires */
 #define EXP_SCAN8_LATE_START(P, hq) if (hq == 1) for (int i = 0; i < (P).s.tune >> 8; ++i) __builtin_amdgcn_s_sleep(32);   /* EMDR2_MIPS_TUNE bits 8..: late start of the second half */
