@@ -132,8 +132,9 @@ def get_parser():
     g.add_argument('--index-generations', action='store_true',
                    help='(not in the reference) the evidence index keeps one 32-bit generation stamp per row on the device (84 MB at 21 M '
                         'rows): the number of optimizer steps the weights that wrote the row had taken -- 0 for rows loaded from '
-                        '--embedding-path, the snapshot\'s iteration for rows restored from an index snapshot (stamps are not saved: ages '
-                        'after a resume are a lower bound).  Every writer stamps what it writes.  At every --log-interval rank 0 prints one '
+                        '--embedding-path; rows restored from an index snapshot get the stamps the snapshot saved with them '
+                        '(--save-index-snapshot), or, from a snapshot without stamps, its iteration -- ages are then a lower bound.  '
+                        'Every writer stamps what it writes.  At every --log-interval rank 0 prints one '
                         'line: mean / max age, in steps, of the rows the last step retrieved (as its search found them), mean / max age of '
                         'the whole index, and the rows that newest-wins updates have left alone since the last line.  One small device pass '
                         'and two small all-reduces per statistic, at iterations that depend on --log-interval alone.  No search result changes')
@@ -151,7 +152,8 @@ def get_parser():
                         'order.  No encoder forward is spent on a row that --index-writeback has stamped since the snapshot (which '
                         '--index-newest-wins would refuse to overwrite anyway), and a pass ends as soon as no row is older than its '
                         'snapshot instead of after a fixed count.  The pace (rows per step) is unchanged.  On an index with uniform '
-                        'stamps -- a fresh start, a resume -- the order is the row order.  Rank 0 prints one line per completed pass')
+                        'stamps -- a fresh start, a resume from a snapshot without stamps -- the order is the row order.  Rank 0 prints '
+                        'one line per completed pass')
     g.add_argument('--context-embeddings-from-index', action='store_true',
                    help='(not in the reference; needs --no-context-embedder-training) take the embeddings of the batch-size x topk retrieved '
                         'passages from the index rows the search returned instead of running the frozen context encoder over them, in '

@@ -186,6 +186,15 @@ int emdr2_mips_digest_rows(const void *tiled, int64_t n_rows_total, int dim, int
     return mips_launch_digest_rows(tiled, dim, row_offset, n_chunk, row_base, digest, (hipStream_t)stream);
 }
 
+int emdr2_mips_digest_stamps(const uint32_t *generation, int64_t n_rows_total, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                             uint64_t *digest, emdr2_stream_t stream)
+{
+    if (!digest || ((uintptr_t)digest & 7) || ((uintptr_t)generation & 3) || n_rows_total < 0 || n_chunk < 0 || row_offset < 0 ||
+        row_offset + n_chunk > n_rows_total || row_base < 0 || (n_chunk > 0 && !generation))
+        return EMDR2_E_BADARG;
+    return mips_launch_digest_stamps(generation, row_offset, n_chunk, row_base, digest, (hipStream_t)stream);
+}
+
 int emdr2_mips_workspace_bytes(int n_q, int dim, int k, size_t *bytes)
 {
     if (!bytes || n_q < 1 || k < 1 || k > EMDR2_MAX_TOPK || bad_shape(0, dim)) return EMDR2_E_BADARG;

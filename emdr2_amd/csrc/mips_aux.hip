@@ -384,6 +384,63 @@ int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int6
     return CHECK_LAUNCH();
 }
 
+// The digest of the generation stamps of rows [row_lo, row_hi) (emdr2_mips_digest_stamps): h(r) of include/emdr2_mips.h, summed and xor-ed.
+// The stamp array is only 4-byte aligned and a range starts at any row, so the range is cut in three: the at most three rows in front of
+// the first 16-byte boundary, whole uint4 vectors, and the at most three rows behind the last one.  The vectors are walked grid-stride
+// (the grid is capped like generation_stats_kernel's: the workgroups end in two atomics on the same two words); the up to six loose rows go
+// to the first threads of workgroup 0.  Per-thread partials, a wave and an LDS reduction, ONE 64-bit add and ONE 64-bit xor per workgroup;
+// no workgroup waits on another.
+#define DIGEST_STAMP_TAG (0x47454E53ull << 32)
+__device__ __forceinline__ uint64_t digest_stamp(uint32_t g, int64_t number)
+{
+    return digest_mix(digest_mix((uint64_t)g | DIGEST_STAMP_TAG) ^ ((uint64_t)(number + 1) * 0x9E3779B97F4A7C15ull));
+}
+
+__global__ void __launch_bounds__(256) digest_stamps_kernel(const uint32_t *__restrict__ generation, int64_t row_lo, int64_t row_hi, int64_t body_lo,
+                                                            int64_t n_vec, int64_t row_base, unsigned long long *__restrict__ digest)
+{
+    __shared__ uint64_t sh_sum[4], sh_xor[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t sum = 0, x = 0;
+    const uint4 *body = (const uint4 *)(generation + body_lo);         // (16-byte aligned: the launcher chose body_lo so)
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t v = (int64_t)blockIdx.x * 256 + tid; v < n_vec; v += stride) {
+        const uint4 s = body[v];
+        const int64_t number = row_base + body_lo + v * 4;
+        const uint64_t h0 = digest_stamp(s.x, number), h1 = digest_stamp(s.y, number + 1), h2 = digest_stamp(s.z, number + 2),
+                       h3 = digest_stamp(s.w, number + 3);
+        sum += h0 + h1 + h2 + h3; x ^= h0 ^ h1 ^ h2 ^ h3;
+    }
+    if (blockIdx.x == 0 && tid < 6) {                                  // the head [row_lo, body_lo) and the tail [body_hi, row_hi): < 4 rows each
+        const int64_t n_head = body_lo - row_lo, body_hi = body_lo + n_vec * 4;
+        const int64_t r = tid < n_head ? row_lo + tid : body_hi + (tid - n_head);
+        if (r < row_hi) { const uint64_t h = digest_stamp(generation[r], row_base + r); sum += h; x ^= h; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sum += shfl_xor_u64(sum, o); x ^= shfl_xor_u64(x, o); }
+    if (lane == 0) { sh_sum[wave] = sum; sh_xor[wave] = x; }
+    __syncthreads();
+    if (tid == 0) {
+        atomicAdd(&digest[0], (unsigned long long)(sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3]));
+        atomicXor(&digest[1], (unsigned long long)(sh_xor[0] ^ sh_xor[1] ^ sh_xor[2] ^ sh_xor[3]));
+    }
+}
+
+int mips_launch_digest_stamps(const uint32_t *generation, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream)
+{
+    if (n_chunk == 0) return 0;
+    const int64_t row_hi = row_offset + n_chunk;
+    // the first row at or behind row_offset whose stamp sits on a 16-byte boundary (the array itself is 4-byte aligned)
+    int64_t body_lo = row_offset + (int64_t)((4 - ((((uintptr_t)generation >> 2) + (uint64_t)row_offset) & 3)) & 3);
+    if (body_lo > row_hi) body_lo = row_hi;
+    const int64_t n_vec = (row_hi - body_lo) >> 2;
+    int64_t blocks = (n_vec + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
+    hipLaunchKernelGGL(digest_stamps_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, generation, row_offset, row_hi, body_lo, n_vec, row_base,
+                       (unsigned long long *)digest);
+    return CHECK_LAUNCH();
+}
+
 // ------------------------------------------------------------------------------------------------
 // query packing: [n_q, dim] row-major -> per chunk a [bn rows x 64 B] swizzled block (zero padded)
 // ------------------------------------------------------------------------------------------------

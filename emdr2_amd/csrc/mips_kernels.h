@@ -105,6 +105,8 @@ int mips_launch_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t 
 // index snapshots: image rows [row_offset, row_offset + n_chunk) -> row-major fp16; their digest added / xor-ed into digest[0] / digest[1]
 int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, void *rows_rm, hipStream_t stream);
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
+// the digest of the generation stamps of local rows [row_offset, row_offset + n_chunk), folded into digest[0] / digest[1] the same way
+int mips_launch_digest_stamps(const uint32_t *generation, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
 // index audit (mips_audit.hip): the report of emdr2_mips_audit for the padded image of n_rows rows; e8 / table null: no shadow;
 // sealed_blocks = ceil(n_rows / 256), the blocks a seal covers; block_norm_sq may be null
 struct AuditParams {

@@ -176,6 +176,26 @@ def digest_rows(rows, first_row_number=0):
     return int(total), int(x)
 
 
+_STAMP_TAG = 0x47454E53 << 32
+
+
+def digest_stamps(stamps, first_row_number=0):
+    """(sum, xor) over the generation stamps `stamps` (uint32 or int32 [n], bit patterns) of h(r), stamp i belonging to row
+    `first_row_number + i` -- the numpy restatement of emdr2_mips_digest_stamps (include/emdr2_mips.h); Python ints below 2^64."""
+    stamps = np.asarray(stamps)
+    if stamps.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or stamps.ndim != 1:
+        raise ValueError("stamps must be uint32 or int32 [n]")
+    total, x = _U64(0), _U64(0)
+    with np.errstate(over='ignore'):
+        for lo in range(0, stamps.shape[0], 1 << 22):
+            block = np.ascontiguousarray(stamps[lo:lo + (1 << 22)]).view(np.uint32).astype(_U64)
+            number = np.arange(first_row_number + lo + 1, first_row_number + lo + 1 + block.shape[0], dtype=np.int64).astype(_U64)
+            h = _digest_mix(_digest_mix(block | _U64(_STAMP_TAG)) ^ (number * _U64(0x9E3779B97F4A7C15)))
+            total = total + h.sum(dtype=_U64)
+            x = x ^ np.bitwise_xor.reduce(h)
+    return int(total), int(x)
+
+
 def combine_digests(pairs):
     """Digests of disjoint row sets -> the digest of their union: sums add mod 2^64, xors xor."""
     total, x = 0, 0
@@ -929,6 +949,59 @@ class HipIndexShard(object):
         s, x = acc.tolist()
         return s & (2 ** 64 - 1), x & (2 ** 64 - 1)
 
+    # -- the stamps' way out of HBM and back (emdr2_mips_digest_stamps); every call reads `self.generation` as it stands: commit_refresh swaps it
+    def _check_stamp_range(self, local_row, n):
+        if self.generation is None:
+            raise ValueError("this shard keeps no generation stamps")
+        self._check_range(local_row, n)
+
+    def export_stamps(self, local_row, n, out=None):
+        """The stamps of rows [local_row, local_row + n) as CUDA int32 [n] (the storage of the device's uint32 words), copied on the
+        current stream.  `out`: a contiguous CUDA int32 buffer of at least n words to write into (its first n are returned)."""
+        local_row, n = int(local_row), int(n)
+        self._check_stamp_range(local_row, n)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.dim() != 1 or out.shape[0] < n or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA int32 [>= %d] tensor" % n)
+        out = out[:n]
+        if n:
+            out.copy_(self.generation[local_row:local_row + n])
+        return out
+
+    def digest_stamps_into(self, acc, local_row=0, n=None):
+        """Fold the digest of the stamps of rows [local_row, local_row + n) into `acc` (CUDA int64 [2], zeroed by the caller) on the
+        current stream; no readback.  Rows are numbered `row_base + local row`, as for `digest_into`."""
+        n = self.n_rows - local_row if n is None else int(n)
+        self._check_stamp_range(int(local_row), n)
+        if acc.dtype != torch.int64 or acc.numel() != 2 or not acc.is_cuda or not acc.is_contiguous():
+            raise ValueError("acc must be a contiguous CUDA int64 [2] tensor")
+        if n:
+            _native.check(self.lib.emdr2_mips_digest_stamps(self.generation.data_ptr(), self.n_rows, int(local_row), n, self.row_base,
+                                                            acc.data_ptr(), _native.stream_ptr()), "digest_stamps")
+        return acc
+
+    def digest_stamps(self, local_row=0, n=None):
+        """(sum, xor) digest of the stamps of rows [local_row, local_row + n) (default: the whole shard) as Python ints; equals the
+        host `digest_stamps` of the same stamps under the same numbering.  One readback."""
+        acc = self.digest_stamps_into(torch.zeros(2, dtype=torch.int64, device=self.device), local_row, n)
+        s, x = acc.tolist()
+        return s & (2 ** 64 - 1), x & (2 ** 64 - 1)
+
+    def set_stamps(self, local_row, stamps):
+        """`stamps` (host uint32 or int32 [n], every value below 2^31) -> the stamps of rows [local_row, local_row + n) of the live image
+        (a snapshot's sidecar, after its rows are in).  The copy is enqueued on the current stream."""
+        stamps = np.ascontiguousarray(stamps)
+        if stamps.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or stamps.ndim != 1:
+            raise ValueError("stamps must be a host uint32 or int32 [n] array")
+        local_row, n = int(local_row), stamps.shape[0]
+        self._check_stamp_range(local_row, n)
+        if n == 0:
+            return
+        if int(stamps.view(np.uint32).max()) > _native.GEN_MAX:
+            raise ValueError("generation stamps must be below 2^31")
+        self.generation[local_row:local_row + n].copy_(torch.from_numpy(np.array(stamps.view(np.int32), copy=True)))
+
 
 def merge_shard_results(dist, idx, row):
     """[S, Q, k] per-shard canonical lists (device; dist fp16, or fp32 for the FaissMIPSIndex-style scores) -> merged [Q, k] via the HIP
@@ -977,6 +1050,7 @@ class DistributedBruteForceIndex(object):
         self.embed_size = embed_size
         self.generations = bool(generations)                       # (extra, optional) the shard keeps generation stamps: HipIndexShard
         self._load_generation = 0                                  # the stamp of rows that add_arrays uploads: 0, or a snapshot's iteration
+        self.stamps_restored = False                               # the last load_flat_snapshot set every row's own stamp from the sidecar
         self.embed_data = embed_data
         self.use_gpu = use_gpu
         self.process_group = process_group
@@ -1136,8 +1210,9 @@ class DistributedBruteForceIndex(object):
     def save_flat_file(self, path, meta=None):
         """Write the index as it stands in HBM to the `FlatEmbeddingFile` `path` plus `path + '.meta'` (JSON: format, n, dim, world, the
         DEVICE digest of what was exported, ids_crc32, and the caller's `meta`: iteration / refreshes / mode).  Collective and synchronous;
-        the file appears atomically and a data file without a meta is an incomplete snapshot.  After `IndexBuilder.build_into_index` this
-        is the fast offline indexer."""
+        the file appears atomically and a data file without a meta is an incomplete snapshot.  An index with generation stamps also
+        writes every row's stamp to the sidecar `path + '.gen'` and their device digest to the meta's `stamps`.  After
+        `IndexBuilder.build_into_index` this is the fast offline indexer."""
         from emdr2_amd.data.index_snapshot import IndexSnapshotWriter
         writer = IndexSnapshotWriter(self, chunk_rows=min(_UPLOAD_ROWS, 1 << 18))
         writer.begin(path, meta)
@@ -1146,11 +1221,16 @@ class DistributedBruteForceIndex(object):
     def load_flat_snapshot(self, path, audit=False):
         """Build the index from a snapshot written by `save_flat_file` at ANY world size and verify it: meta against the file's header
         and ids, then the device digest of what now stands in HBM (combined over the ranks) against the meta's.  A mismatch raises
-        ValueError.  With generation stamps every row is stamped with the meta's `iteration` (0 if absent): stamps are not saved in
-        snapshots, so ages after a resume are a lower bound.  `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
+        ValueError.  Generation stamps, on an index that keeps them: a snapshot taken from a stamped index carries every row's stamp in
+        its sidecar (`path + '.gen'`, named by the meta's `stamps`); each rank sets its own slice after its rows are in, and the device
+        digest of the stamps, combined over the ranks, is checked against the meta's like the rows' -- ages after the resume are the true
+        ones.  A snapshot without stamps stamps every row with the meta's `iteration` (0 if absent), and ages are then a lower bound.  An
+        index without stamps ignores the sidecar.  `self.stamps_restored` says which of the two happened.
+        `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
         ValueError naming the non-zero words unless it is sound and canonical.  Returns the meta."""
         from emdr2_amd.data import index_snapshot as snap
         meta = snap.read_snapshot_meta(path)
+        self.stamps_restored = False
         flat = FlatEmbeddingFile(path)
         if flat.dim != self.embed_size:
             raise ValueError("snapshot rows have %d elements, the index %d" % (flat.dim, self.embed_size))
@@ -1165,6 +1245,14 @@ class DistributedBruteForceIndex(object):
         want = (int(meta["digest_sum"], 16), int(meta["digest_xor"], 16))
         if got != want:
             raise ValueError("index snapshot %s: digest %016x %016x in HBM, %016x %016x in the meta" % ((path,) + got + want))
+        if self.generations and meta.get("stamps") is not None:   # (the meta and the flag are the same on every rank: so is the collective)
+            lo, hi = self.local_rows()
+            self.shard.set_stamps(0, snap.StampFile(snap.stamps_path(path)).stamps[lo:hi])
+            got = snap.index_stamp_digest(self)
+            want = (int(meta["stamps"]["digest_sum"], 16), int(meta["stamps"]["digest_xor"], 16))
+            if got != want:
+                raise ValueError("index snapshot %s: stamp digest %016x %016x in HBM, %016x %016x in the meta" % ((path,) + got + want))
+            self.stamps_restored = True
         if audit:
             bad = audit_failures(self.audit())
             if bad:

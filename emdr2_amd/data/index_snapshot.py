@@ -12,11 +12,24 @@ out.  Protocol (`IndexSnapshotWriter`; `DistributedBruteForceIndex.save_flat_fil
 
 A data file without a meta is therefore an incomplete snapshot and is refused (`read_snapshot_meta`).  Any world size reads a snapshot
 written by any other: the file is the whole index in global row order, and the digest does not depend on how the rows were cut.
+
+Generation stamps.  A snapshot of an index whose shards keep stamps (`shard.generation`) also stores every row's stamp, in the sidecar
+`<path>.gen` (`StampFile`):
+
+    8-byte magic "EMDR2GEN" | u32 version = 1 | u32 0 | u64 n | n little-endian uint32 stamps in GLOBAL row order
+
+In step 1 rank 0 creates `<tmp>.gen` at full size as well; in step 2 a chunk's stamps are taken on the same stream, between the same two
+neighbours, as its rows, and their device digest (emdr2_mips_digest_stamps) is folded into a second accumulator; step 3 gathers both
+digests in the one all-gather; step 4 becomes: remove the old meta, rename the sidecar, rename the data file, write the meta, which gains
+the one key `"stamps": {"digest_sum": hex, "digest_xor": hex}`.  A meta that names stamps without a matching sidecar is an incomplete
+snapshot.  A snapshot of an index without stamps has neither the key nor a sidecar (a stale one is removed), and its meta and data file
+are what they always were; `"format"` stays 1 either way.
 """
 import json
 import os
 import queue
 import socket
+import struct
 import threading
 import uuid
 import zlib
@@ -42,6 +55,56 @@ def meta_path(path):
     return path + '.meta'
 
 
+def stamps_path(path):
+    return path + '.gen'
+
+
+STAMPS_MAGIC = b'EMDR2GEN'
+_STAMPS_HEADER = 24
+
+
+class StampFile(object):
+    """The sidecar of a snapshot with generation stamps: header (module docstring) + `stamps`, uint32 [n] in global row order, memory-mapped.
+    ValueError for another magic or version, or a file shorter than its header says."""
+
+    def __init__(self, path, mode='r'):
+        self.path = path
+        with open(path, 'rb') as f:
+            head = f.read(_STAMPS_HEADER)
+        if len(head) < _STAMPS_HEADER or head[:8] != STAMPS_MAGIC:
+            raise ValueError("not a generation stamp file: %s" % path)
+        version, _, self.n = struct.unpack('<IIQ', head[8:])
+        if version != 1:
+            raise ValueError("unsupported generation stamp file version %d" % version)
+        if os.path.getsize(path) < _STAMPS_HEADER + 4 * self.n:
+            raise ValueError("generation stamp file is shorter than its header says: %s" % path)
+        # (numpy cannot map zero bytes)
+        self.stamps = np.memmap(path, dtype='<u4', mode=mode, offset=_STAMPS_HEADER, shape=(self.n,)) if self.n else np.empty((0,), '<u4')
+
+    @classmethod
+    def create(cls, path, n):
+        """Header + a file of full size (zeros), opened writable: several processes fill disjoint slices through maps of their own."""
+        with open(path, 'wb') as f:
+            f.write(STAMPS_MAGIC)
+            f.write(struct.pack('<IIQ', 1, 0, int(n)))
+            f.truncate(_STAMPS_HEADER + 4 * int(n))
+        return cls(path, mode='r+')
+
+    @staticmethod
+    def write(path, stamps):
+        stamps = np.ascontiguousarray(stamps)
+        if stamps.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or stamps.ndim != 1:
+            raise ValueError("stamps must be uint32 or int32 [n]")
+        with open(path, 'wb') as f:
+            f.write(STAMPS_MAGIC)
+            f.write(struct.pack('<IIQ', 1, 0, stamps.shape[0]))
+            f.write(stamps.view(np.uint32).astype('<u4').tobytes())
+
+    def flush(self):
+        if isinstance(self.stamps, np.memmap):
+            self.stamps.flush()
+
+
 def ids_crc32(ids):
     crc = 0
     for lo in range(0, ids.shape[0], 1 << 22):
@@ -51,7 +114,9 @@ def ids_crc32(ids):
 
 def read_snapshot_meta(path):
     """The meta of the snapshot at `path`, validated against the data file's header -> dict.  Raises ValueError for a data file without
-    a meta (an incomplete snapshot), an unknown format, or a header that disagrees; FileNotFoundError when there is no data file."""
+    a meta (an incomplete snapshot), an unknown format, or a header that disagrees; FileNotFoundError when there is no data file.  A meta
+    that names `stamps` needs its sidecar: a missing one, one whose header holds another n, or one shorter than its header says is an
+    incomplete snapshot too."""
     from emdr2_amd.data.emdr2_index import FlatEmbeddingFile
     if not os.path.exists(path):
         raise FileNotFoundError("no index snapshot at %s" % path)
@@ -66,6 +131,14 @@ def read_snapshot_meta(path):
         raise ValueError("snapshot meta says %r x %r, the file %d x %d" % (meta.get("n"), meta.get("dim"), flat.n, flat.dim))
     for key in ("digest_sum", "digest_xor"):
         int(meta[key], 16)
+    if meta.get("stamps") is not None:
+        for key in ("digest_sum", "digest_xor"):
+            int(meta["stamps"][key], 16)
+        if not os.path.exists(stamps_path(path)):
+            raise ValueError("%s names stamps and has no %s: an incomplete snapshot" % (path, os.path.basename(stamps_path(path))))
+        n = StampFile(stamps_path(path)).n
+        if n != flat.n:
+            raise ValueError("snapshot stamp file holds %d stamps, the data file %d rows" % (n, flat.n))
     return meta
 
 
@@ -100,22 +173,32 @@ class _Collective(object):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MIN, group=self.group)
         return int(t.item())
 
-    def gather_digests(self, pair):
+    def gather_digests(self, pair, *more):
         """This rank's (sum, xor) -> the digest over all ranks: the pairs travel as int64 bit patterns in one all-gather and are combined
-        on the host mod 2^64 (an all-reduce would add int64s: signed overflow, and no XOR over every transport)."""
+        on the host mod 2^64 (an all-reduce would add int64s: signed overflow, and no XOR over every transport).  With `more` pairs (the
+        stamps' next to the rows'): all of them in the SAME all-gather -> the list of their digests."""
         from emdr2_amd.data.emdr2_index import combine_digests
+        pairs = (pair,) + more
         if not self.on:
-            return combine_digests([pair])
-        mine = torch.tensor([_to_i64(pair[0]), _to_i64(pair[1])], dtype=torch.int64, device=self.device)
-        out = torch.empty((self.world * 2,), dtype=torch.int64, device=self.device)
-        torch.distributed.all_gather_into_tensor(out, mine, group=self.group)
-        flat = out.tolist()
-        return combine_digests([(flat[2 * r] & _MASK, flat[2 * r + 1] & _MASK) for r in range(self.world)])
+            flat, world = [w for p in pairs for w in p], 1
+        else:
+            mine = torch.tensor([_to_i64(w) for p in pairs for w in p], dtype=torch.int64, device=self.device)
+            out = torch.empty((self.world * mine.numel(),), dtype=torch.int64, device=self.device)
+            torch.distributed.all_gather_into_tensor(out, mine, group=self.group)
+            flat, world = out.tolist(), self.world
+        k = 2 * len(pairs)
+        digests = [combine_digests([(flat[k * r + 2 * i] & _MASK, flat[k * r + 2 * i + 1] & _MASK) for r in range(world)]) for i in range(len(pairs))]
+        return digests if more else digests[0]
 
 
 def index_digest(index):
     """Device digest of the whole index, combined over the ranks that share it (collective; one readback per rank)."""
     return _Collective(index).gather_digests(index.shard.digest())
+
+
+def index_stamp_digest(index):
+    """Device digest of the generation stamps of the whole index, combined over the ranks that share it (collective; one readback per rank)."""
+    return _Collective(index).gather_digests(index.shard.digest_stamps())
 
 
 class IndexSnapshotWriter(object):
@@ -131,7 +214,12 @@ class IndexSnapshotWriter(object):
     that of exactly the exported bits.  The device-to-host copy into one of two pinned buffers runs on a side stream behind an event; ONE
     background thread waits for that event (its only GPU call) and writes the slice through the file's memory map.  With no free buffer
     `pump()` does nothing this step.  In swap mode the live image does not change between swaps, so the file equals the committed image;
-    in rolling mode it is a mix of generations, as the live index is."""
+    in rolling mode it is a mix of generations, as the live index is.
+
+    A shard with generation stamps: the chunk's stamps are copied and digested on the current stream right next to its rows, with no
+    writer between the four calls -- a stamped update enqueued before the pump is in both the row and its stamp, one enqueued after it in
+    neither.  `shard.generation` is read at every pump (`commit_refresh` swaps the array).  The stamps ride the same side stream, the same
+    event and the same buffer cycle to the host, and the background thread writes them to the sidecar (module docstring)."""
 
     def __init__(self, index, chunk_rows=None, log=None):
         self.index = index
@@ -156,24 +244,32 @@ class IndexSnapshotWriter(object):
         self.coll = _Collective(index)
         self.path, self.meta = path, dict(meta or {})
         self._tmp = self.coll.share(path + '.part.' + _unique())
+        self._stamped = getattr(shard, "generation", None) is not None      # (every rank's shard keeps stamps, or none does)
         err = None
         if self.coll.rank == 0:
             try:
                 FlatEmbeddingFile.create(self._tmp, index.num_rows, index.embed_size)
+                if self._stamped:
+                    StampFile.create(stamps_path(self._tmp), index.num_rows)
             except Exception as exc:                               # the peers are waiting at the barrier: meet them first, then raise
                 err = exc
-        if self.coll.minimum(0 if err is not None else 1) == 0:    # (also the barrier "the file exists")
+                self._remove_parts()
+        if self.coll.minimum(0 if err is not None else 1) == 0:    # (also the barrier "the files exist")
             raise err if err is not None else RuntimeError("rank 0 could not create %s" % self._tmp)
         self._file = FlatEmbeddingFile(self._tmp, mode='r+')
+        self._gen_file = StampFile(stamps_path(self._tmp), mode='r+') if self._stamped else None
         self._n, self._cursor = shard.n_rows, 0
         self._chunk = max(1, int(chunk_rows or self.chunk_rows or SNAPSHOT_ROWS))
         self._chunk = min(self._chunk, max(self._n, 1))
         self._cuda = bool(getattr(shard, "tiled", None) is not None and shard.tiled.is_cuda)
-        self._host_digest = (0, 0)
+        self._host_digest = self._host_stamp_digest = (0, 0)
         if self._cuda:
-            self._acc = torch.zeros(2, dtype=torch.int64, device=shard.device)
+            self._acc = torch.zeros(4, dtype=torch.int64, device=shard.device)      # the rows' (sum, xor), then the stamps'
             self._dev = [torch.empty((self._chunk, shard.dim), dtype=torch.float16, device=shard.device) for _ in range(2)]
             self._pinned = [torch.empty((self._chunk, shard.dim), dtype=torch.float16).pin_memory() for _ in range(2)]
+            if self._stamped:
+                self._gen_dev = [torch.empty(self._chunk, dtype=torch.int32, device=shard.device) for _ in range(2)]
+                self._gen_pinned = [torch.empty(self._chunk, dtype=torch.int32).pin_memory() for _ in range(2)]
             self._side = torch.cuda.Stream(device=shard.device)
         ids = shard.ids if shard.ids is not None else np.arange(shard.row_base, shard.row_base + self._n, dtype=np.int32)
         ids = ids.cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids, dtype=np.int32)
@@ -200,17 +296,22 @@ class IndexSnapshotWriter(object):
                 if item is None:
                     if self._error is None:
                         self._file.flush()
+                        if self._gen_file is not None:
+                            self._gen_file.flush()
                     return
                 if self._error is not None:
                     continue
                 if item[0] == "ids":
                     self._file.ids[base:base + self._n] = item[1]
                 else:
-                    _, buf, lo, m, event, host = item
+                    _, buf, lo, m, event, host, stamps = item
                     if event is not None:
                         event.synchronize()
                         host = self._pinned[buf][:m].numpy()
+                        stamps = self._gen_pinned[buf][:m].numpy().view(np.uint32) if self._stamped else None
                     self._file.rows[base + lo:base + lo + m] = host
+                    if stamps is not None:
+                        self._gen_file.stamps[base + lo:base + lo + m] = stamps
             except BaseException as exc:                           # surfaces from finish() / maybe_finalize()
                 self._error = exc
             finally:
@@ -225,9 +326,13 @@ class IndexSnapshotWriter(object):
         if not self._cuda:
             # a host stand-in for the shard (CPU tests): its rows are already on the host, nothing to overlap
             rows = shard.export_rows(lo, m)
-            from emdr2_amd.data.emdr2_index import combine_digests
+            from emdr2_amd.data.emdr2_index import combine_digests, digest_stamps
             self._host_digest = combine_digests([self._host_digest, shard.digest(lo, m)])
-            self._work.put(("rows", None, lo, m, None, np.array(rows, dtype=np.float16, copy=True)))
+            stamps = None
+            if self._stamped:
+                stamps = np.array(np.asarray(shard.generation)[lo:lo + m], copy=True).view(np.uint32)
+                self._host_stamp_digest = combine_digests([self._host_stamp_digest, digest_stamps(stamps, shard.row_base + lo)])
+            self._work.put(("rows", None, lo, m, None, np.array(rows, dtype=np.float16, copy=True), stamps))
         else:
             try:
                 buf = self._free.get(block=block)
@@ -235,15 +340,20 @@ class IndexSnapshotWriter(object):
                 return False
             cur = torch.cuda.current_stream(shard.device)
             shard.export_rows(lo, m, out=self._dev[buf])
-            shard.digest_into(self._acc, lo, m)
+            shard.digest_into(self._acc[:2], lo, m)
+            if self._stamped:                                      # (the same stream point: no writer is enqueued between these four)
+                shard.export_stamps(lo, m, out=self._gen_dev[buf])
+                shard.digest_stamps_into(self._acc[2:], lo, m)
             exported = torch.cuda.Event()
             exported.record(cur)
             self._side.wait_event(exported)
             with torch.cuda.stream(self._side):
                 self._pinned[buf][:m].copy_(self._dev[buf][:m], non_blocking=True)
+                if self._stamped:
+                    self._gen_pinned[buf][:m].copy_(self._gen_dev[buf][:m], non_blocking=True)
                 copied = torch.cuda.Event()
                 copied.record(self._side)
-            self._work.put(("rows", buf, lo, m, copied, None))
+            self._work.put(("rows", buf, lo, m, copied, None, None))
         self._cursor += m
         if self._cursor >= self._n:
             self._work.put(None)
@@ -292,32 +402,42 @@ class IndexSnapshotWriter(object):
         """Steps 3 and 4 of the protocol; every rank's slice is written (or one has failed, and all raise)."""
         self._join()
         error, self.active = self._error, False
-        digest = None
+        digest = stamp_digest = None
         if not failed:
-            mine = self._host_digest
+            mine, stamps = self._host_digest, self._host_stamp_digest
             if self._cuda:
-                s, x = self._acc.tolist()                           # the one readback: everything exported has long run
-                mine = (s & _MASK, x & _MASK)
-            digest = self.coll.gather_digests(mine)                 # (also the barrier "every slice is on disk")
-        self._file = self._dev = self._pinned = None
+                s, x, gs, gx = self._acc.tolist()                   # the one readback: everything exported has long run
+                mine, stamps = (s & _MASK, x & _MASK), (gs & _MASK, gx & _MASK)
+            # (also the barrier "every slice is on disk"; `_stamped` is the same on every rank, so the gather has one width everywhere)
+            if self._stamped:
+                digest, stamp_digest = self.coll.gather_digests(mine, stamps)
+            else:
+                digest = self.coll.gather_digests(mine)
+        self._file = self._gen_file = self._dev = self._pinned = self._gen_dev = self._gen_pinned = None
         if failed:
             if self.coll.rank == 0:
-                try:
-                    os.remove(self._tmp)
-                except OSError:
-                    pass
+                self._remove_parts()
             raise error if error is not None else RuntimeError("index snapshot %s failed on another rank" % self.path)
         err = None
         if self.coll.rank == 0:
             try:
-                self._publish(digest)
+                self._publish(digest, stamp_digest)
             except Exception as exc:
                 err = exc
         if self.coll.minimum(0 if err is not None else 1) == 0:    # nobody returns before the meta is in place
             raise err if err is not None else RuntimeError("rank 0 could not publish %s" % self.path)
-        self.log("index snapshot: %d x %d rows in %s (digest %016x %016x)" % (self.index.num_rows, self.index.embed_size, self.path, digest[0], digest[1]))
+        self.log("index snapshot: %d x %d rows in %s (digest %016x %016x%s)"
+                 % (self.index.num_rows, self.index.embed_size, self.path, digest[0], digest[1],
+                    "" if stamp_digest is None else "; generation stamps, digest %016x %016x" % stamp_digest))
 
-    def _publish(self, digest):
+    def _remove_parts(self):
+        for part in (self._tmp, stamps_path(self._tmp)):
+            try:
+                os.remove(part)
+            except OSError:
+                pass
+
+    def _publish(self, digest, stamp_digest=None):
         from emdr2_amd.data.emdr2_index import FlatEmbeddingFile
         try:
             os.remove(meta_path(self.path))                        # from here until the new meta is written there is no valid snapshot
@@ -326,10 +446,19 @@ class IndexSnapshotWriter(object):
         flat = FlatEmbeddingFile(self._tmp)
         crc = ids_crc32(flat.ids)
         del flat
+        if stamp_digest is not None:
+            os.replace(stamps_path(self._tmp), stamps_path(self.path))
+        else:
+            try:
+                os.remove(stamps_path(self.path))                  # a stale sidecar of an earlier snapshot with stamps
+            except FileNotFoundError:
+                pass
         os.replace(self._tmp, self.path)
         meta = dict(self.meta)
         meta.update(format=SNAPSHOT_FORMAT, n=int(self.index.num_rows), dim=int(self.index.embed_size), world=int(self.coll.world),
                     digest_sum="%016x" % digest[0], digest_xor="%016x" % digest[1], ids_crc32=crc)
+        if stamp_digest is not None:
+            meta["stamps"] = {"digest_sum": "%016x" % stamp_digest[0], "digest_xor": "%016x" % stamp_digest[1]}
         tmp = meta_path(self.path) + '.tmp.' + _unique()
         with open(tmp, 'w') as fh:
             json.dump(meta, fh, indent=1, sort_keys=True)

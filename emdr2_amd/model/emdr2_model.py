@@ -89,8 +89,16 @@ class PreComputedEvidenceDocsRetriever(object):
             return False
         index.embed_data = self.evidence_embedder_obj           # (`update_index()` still reloads --embedding-path, like the reference)
         self.mips_index = index
-        say("index snapshot %s loaded: the index of iteration %s (%s mode, digest %s %s)"
-            % (path, meta.get("iteration"), meta.get("mode"), meta["digest_sum"], meta["digest_xor"]))
+        say("index snapshot %s loaded: the index of iteration %s (%s mode, digest %s %s%s)"
+            % (path, meta.get("iteration"), meta.get("mode"), meta["digest_sum"], meta["digest_xor"],
+               "; generation stamps restored, digest %s %s" % (meta["stamps"]["digest_sum"], meta["stamps"]["digest_xor"])
+               if index.stamps_restored else ""))
+        if index.stamps_restored:
+            # a rolling snapshot that finished after its checkpoint holds rows written back by weights the checkpoint does not have; this
+            # only reports them (collective: every rank restored stamps or none did)
+            future = index.generation_stats(iteration)["from_future"]
+            if future > 0:
+                say("index snapshot %s: %d rows are stamped beyond the checkpoint's iteration %d" % (path, future, iteration))
         self._barrier()
         return True
 

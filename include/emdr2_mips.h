@@ -341,6 +341,25 @@ int emdr2_mips_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t r
                            int64_t *out_rows, uint64_t *out_info, void *workspace, size_t workspace_bytes, emdr2_stream_t stream);
 
 /*
+ * Index snapshots with stamps: the digest of the generation stamps of a row range, the companion of _digest_rows.
+ *   _digest_stamps     generation: the n_rows_total stamps of the shard (4-byte aligned, nothing more is assumed).  For every local row r in
+ *                      [row_offset, row_offset + n_chunk), with mix as for _digest_rows and all arithmetic on uint64, mod 2^64:
+ *                          h(r) = mix( mix( generation[r] | (0x47454E53 << 32) ) ^ ((row_base + r + 1) * 0x9E3779B97F4A7C15) )
+ *                      digest[0] += h(r) (wrap-around), digest[1] ^= h(r); digest is a device uint64[2], 8-byte aligned, zeroed by the
+ *                      caller before the first range.  The tag keeps a stamp word apart from every row word of _digest_rows.  Bits are
+ *                      hashed, not values.  A sum and an XOR over rows: the digest of a shard's stamps does not depend on how it is cut
+ *                      into ranges or ranks (row_base = the global number of local row 0), and integer atomics give the same bits in
+ *                      any order.  One launch on `stream` (scalar head and tail around 16-byte vector loads, grid-stride under a
+ *                      workgroup cap, one 64-bit add and one 64-bit xor per workgroup); nothing allocated, no host synchronisation.  The
+ *                      caller orders the call against writers of the stamps: on one stream, between the same two neighbours as the
+ *                      _export_rows / _digest_rows of the same range, it hashes the stamps that belong to exactly the exported rows.
+ *                      n_chunk == 0 is a no-op returning 0.  EMDR2_E_BADARG: a null or misaligned digest, a misaligned generation or a
+ *                      null one with n_chunk > 0, a range outside [0, n_rows_total], row_base < 0.
+ */
+int emdr2_mips_digest_stamps(const uint32_t *generation, int64_t n_rows_total, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                             uint64_t *digest, emdr2_stream_t stream);
+
+/*
  * Index audit: one streaming pass over a shard's LIVE images that re-checks the premises of the search's
  * proof from the stored bits and, separately, the "bit for bit a fresh build" contract of the derived structures -- emax_sq, the
  * block-norm table, the int8 shadow image and its {s_b, N_b, D_b} table, which pack_rows, seal_shadow, update_rows, update_rows_scattered

@@ -9,6 +9,9 @@
              WITH a paced snapshot (`IndexSnapshotWriter.pump` + `maybe_finalize` at every step boundary, chunk = the default pace of a
              500-step reload interval), alternating blocks of steps in one process.  Without the writer the step runs no snapshot code: it is
              the parent's step.
+4. stamps    (only when asked for) generation stamps in snapshots: `emdr2_mips_digest_stamps` over the 2,626,916 stamps of an N/8 shard next
+             to `emdr2_mips_generation_stats` and a copy of the same words, and one pump at the N/8 shard's paced chunk on a shard without
+             and with stamps, alternating (`--what stamps --out profiles/index_snapshot_stamps.txt`).
 usage: python tools/index_snapshot_bench.py [--what kernels save step] [--calls 10] [--out profiles/index_snapshot.txt]"""
 import argparse
 import hashlib
@@ -187,14 +190,102 @@ def step_cost(dir_, blocks, steps):
     return lines
 
 
+def stamps(dir_, calls, parent_module=None):
+    """Generation stamps in snapshots: the stamp digest over an N/8 shard's stamps next to `generation_stats` and a copy of the same words;
+    one pump at the N/8 shard's paced chunk on a shard without and with stamps, alternating (without stamps a pump makes exactly the calls
+    it made before there were stamps in snapshots).  `parent_module`: a copy of the PARENT commit's emdr2_amd/data/index_snapshot.py
+    (`git show HEAD~1:emdr2_amd/data/index_snapshot.py > FILE`); its writer pumps a third shard, without stamps, in the same alternation."""
+    import importlib.util
+    from emdr2_amd.data.emdr2_index import DistributedBruteForceIndex
+    arms = [("this commit, shard without stamps", snap, False), ("this commit, shard with stamps", snap, True)]
+    if parent_module:
+        spec = importlib.util.spec_from_file_location("parent_index_snapshot", parent_module)
+        parent = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(parent)
+        arms.insert(0, ("the parent commit's writer, shard without stamps", parent, False))
+    lib = _native.lib()
+    gen = torch.randint(0, 1 << 31, (SHARD_ROWS,), dtype=torch.int64, device="cuda").to(torch.int32)
+    twin = torch.empty_like(gen)
+    acc = torch.zeros(2, dtype=torch.int64, device="cuda")
+    report = torch.empty(_native.GEN_WORDS, dtype=torch.int64, device="cuda")
+    stream = _native.stream_ptr()
+    fns = (("digest", lambda: _native.check(lib.emdr2_mips_digest_stamps(gen.data_ptr(), SHARD_ROWS, 0, SHARD_ROWS, 0, acc.data_ptr(), stream), "digest_stamps")),
+           ("digest+1", lambda: _native.check(lib.emdr2_mips_digest_stamps(gen.data_ptr(), SHARD_ROWS, 1, SHARD_ROWS - 2, 0, acc.data_ptr(), stream), "digest_stamps")),
+           ("stats", lambda: _native.check(lib.emdr2_mips_generation_stats(gen.data_ptr(), SHARD_ROWS, 0, None, 0, 1 << 31, report.data_ptr(), stream), "generation_stats")),
+           ("copy", lambda: twin.copy_(gen)))
+    t = {name: [] for name, _ in fns}
+    for i in range(WARMUP + 2 * calls):
+        for name, fn in fns:
+            ms = timed_ms(fn)
+            if i >= WARMUP:
+                t[name].append(ms * 1e3)
+    us = lambda name, v: "  %-58s median %8.1f us  min %8.1f  max %8.1f  (%d calls)" % (name, statistics.median(v), min(v), max(v), len(v))
+    lines = ["%d stamps (%.1f MB), device events around one call" % (SHARD_ROWS, SHARD_ROWS * 4 / 1e6),
+             us("emdr2_mips_digest_stamps, the whole shard", t["digest"]),
+             us("emdr2_mips_digest_stamps, rows 1 .. n - 2 (scalar head and tail)", t["digest+1"]),
+             us("emdr2_mips_generation_stats, the whole shard", t["stats"]),
+             us("device-to-device copy of the stamps", t["copy"])]
+    # one pump: a shard of 40 paced chunks, 768 wide (the chunk, not the shard's length, sets a pump's work)
+    chunk = snap.IndexSnapshotWriter.paced_chunk_rows(SHARD_ROWS, 500)
+    n_rows = 40 * chunk
+    writers, paths = [], []
+    for k, (_, mod, stamped) in enumerate(arms):
+        index = DistributedBruteForceIndex(DIM, None, use_gpu=True, generations=stamped)
+        sh = HipIndexShard(DIM, n_rows, 0, shadow=False, generations=stamped)
+        for blk in bench.synth_rows(0, n_rows):
+            sh.append_rows(blk)
+        if stamped:
+            sh.generation.copy_(gen[:n_rows])
+        index.shard, index.num_rows = sh, n_rows
+        writers.append(mod.IndexSnapshotWriter(index, chunk_rows=chunk))
+        paths.append(os.path.join(dir_, "index_snapshot_bench_stamps%d.flat" % k))
+        writers[-1].begin(paths[-1], {"mode": "rolling"})
+    dev, host = [[] for _ in arms], [[] for _ in arms]
+    try:
+        for i in range(WARMUP + min(calls, 30)):
+            for k, writer in enumerate(writers):
+                torch.cuda.synchronize()                         # (both buffers free again: the pump below exports)
+                while writer._free.qsize() < 2:
+                    time.sleep(0.001)
+                before = writer._cursor
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                t0 = time.perf_counter()
+                writer.pump()
+                wall = (time.perf_counter() - t0) * 1e3
+                b.record()
+                b.synchronize()
+                ms = a.elapsed_time(b)
+                assert writer._cursor == before + chunk
+                if i >= WARMUP:
+                    dev[k].append(ms * 1e3); host[k].append(wall * 1e3)
+        lines.append("one pump of %d rows x %d (%.1f MB of rows, %.1f KB of stamps), alternating; device events around pump() on the step's stream "
+                     "(the device-to-host copies run on the side stream behind it), and the host's wall time of the call, which only enqueues"
+                     % (chunk, DIM, chunk * DIM * 2 / 1e6, chunk * 4 / 1e3))
+        for k, (name, _, _) in enumerate(arms):
+            lines.append(us("%s, on the stream" % name, dev[k]))
+            lines.append(us("%s, host time of the call" % name, host[k]))
+        lines.append("  with - without stamps on this commit, medians: %+.1f us on the stream, %+.1f us of host time"
+                     % (statistics.median(dev[-1]) - statistics.median(dev[-2]), statistics.median(host[-1]) - statistics.median(host[-2])))
+    finally:
+        for writer in writers:
+            writer.finish()
+        for p in paths:
+            for q in (p, snap.meta_path(p), snap.stamps_path(p)):
+                if os.path.exists(q):
+                    os.remove(q)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["kernels", "save", "step"], choices=["kernels", "save", "step"])
+    ap.add_argument("--what", nargs="+", default=["kernels", "save", "step"], choices=["kernels", "save", "step", "stamps"])
     ap.add_argument("--rows", type=int, nargs="+", default=[SHARD_ROWS, FULL_ROWS])
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=3)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--dir", default=tempfile.gettempdir())
+    ap.add_argument("--parent-module", default=None, help="--what stamps: a copy of the parent commit's emdr2_amd/data/index_snapshot.py")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_snapshot.txt"))
     args = ap.parse_args()
     with open(_native.LIB_PATH, "rb") as fh:
@@ -213,6 +304,8 @@ def main():
         torch.cuda.empty_cache()
     if "step" in args.what:
         emit(step_cost(args.dir, args.blocks, args.steps))
+    if "stamps" in args.what:
+        emit(stamps(args.dir, args.calls, args.parent_module))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         fh.write("\n".join(text) + "\n")
