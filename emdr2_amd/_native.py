@@ -68,6 +68,9 @@ SIGNATURES = {
     "emdr2_mips_oldest_rows_workspace_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
     "emdr2_mips_oldest_rows": (_i32, [_vp, _i64, _i64, ctypes.c_uint32, _i64, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_digest_stamps": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "emdr2_mips_row_keys": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "emdr2_mips_changed_rows_workspace_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
+    "emdr2_mips_changed_rows": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "emdr2_mips_audit": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emdr2_mips_debug_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "emdr2_mips_set_timing": (_i32, [_i32]),

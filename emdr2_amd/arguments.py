@@ -172,6 +172,15 @@ def get_parser():
                         'change between swaps, so a resumed run searches exactly what the uninterrupted run searched at that step; the '
                         'refresher\'s in-flight pass is not saved and restarts.  With --index-refresh-in-place the snapshot is a mix of '
                         'embedding generations, as the live index is, and the pass cursor is not saved')
+    g.add_argument('--save-index-deltas', action='store_true',
+                   help='(not in the reference; needs --save-index-snapshot) incremental snapshots: the snapshot writer also keeps a 64-bit '
+                        'key per exported row, and every checkpoint save that is not itself an index update is followed by '
+                        '<save>/evidence_index.flat.delta (+ .delta.meta): the rows whose key differs from the published snapshot\'s, '
+                        'found on the device in one pass over the live image at the step boundary, after the refresher\'s rows and the '
+                        'write-back.  The delta is cumulative (always relative to the published snapshot, one file, overwritten '
+                        'atomically) and is dropped when a new snapshot is published.  With --index-writeback and no --async-indexer one '
+                        'synchronous snapshot is taken at the first checkpoint save.  With --load, the snapshot plus a delta that is not '
+                        'newer than the checkpoint is the index the checkpointed run was searching.  Rank 0 prints one line per delta')
     g.add_argument('--audit-index-interval', type=int, default=0,
                    help='(not in the reference) N > 0: audit the evidence index in HBM (DistributedBruteForceIndex.audit: the premises of '
                         'the search\'s exactness proof and the "byte for byte a fresh build" contract, one streaming pass over the live '
@@ -208,6 +217,8 @@ def parse_args(argv=None):
         raise ValueError("--load and --ict-load are exclusive (indexer_emdr2.py:47)")
     if args.save_index_snapshot and not args.save:
         raise ValueError("--save-index-snapshot needs --save (the snapshot lives next to the checkpoints)")
+    if args.save_index_deltas and not args.save_index_snapshot:
+        raise ValueError("--save-index-deltas needs --save-index-snapshot (a delta is relative to the published snapshot)")
     if args.index_writeback and not args.disable_retriever_dropout:
         raise ValueError("--index-writeback needs --disable-retriever-dropout (a training-mode context tower would write dropout noise into the index)")
     if args.index_writeback and args.async_indexer and not args.index_refresh_in_place:

@@ -553,6 +553,34 @@ int emdr2_mips_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t r
     return mips_launch_oldest_rows(generation, n_rows, row_base, below, n_want, out_rows, out_info, workspace, (hipStream_t)stream);
 }
 
+int emdr2_mips_row_keys(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                        const uint32_t *generation, uint64_t *keys, emdr2_stream_t stream)
+{
+    if (!tiled || !keys || ((uintptr_t)keys & 7) || ((uintptr_t)generation & 3) || bad_shape(n_rows_total, dim) || n_chunk < 0 || row_offset < 0 ||
+        row_offset + n_chunk > n_rows_total || row_base < 0)
+        return EMDR2_E_BADARG;
+    return mips_launch_row_keys(tiled, dim, row_offset, n_chunk, row_base, generation, keys, (hipStream_t)stream);
+}
+
+// (row counts stay below 2^31, as for _oldest_rows)
+int emdr2_mips_changed_rows_workspace_bytes(int64_t n_rows, size_t *bytes)
+{
+    if (!bytes || n_rows < 0 || n_rows >= ((int64_t)1 << 31)) return EMDR2_E_BADARG;
+    *bytes = mips_changed_rows_workspace_bytes(n_rows);
+    return EMDR2_OK;
+}
+
+int emdr2_mips_changed_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const uint32_t *generation, const uint64_t *base_keys,
+                            int64_t cap, int64_t *out_rows, uint64_t *out_info, void *workspace, size_t workspace_bytes, emdr2_stream_t stream)
+{
+    if (!out_info || ((uintptr_t)out_info & 7) || !workspace || ((uintptr_t)workspace & 15) || ((uintptr_t)generation & 3) ||
+        ((uintptr_t)base_keys & 7) || ((uintptr_t)out_rows & 7) || n_rows >= ((int64_t)1 << 31) || bad_shape(n_rows, dim) || row_base < 0 || cap < 0 ||
+        cap > n_rows || (n_rows > 0 && (!tiled || !base_keys)) || (cap > 0 && !out_rows))
+        return EMDR2_E_BADARG;
+    if (workspace_bytes < mips_changed_rows_workspace_bytes(n_rows)) return EMDR2_E_WORKSPACE;
+    return mips_launch_changed_rows(tiled, n_rows, dim, row_base, generation, base_keys, cap, out_rows, out_info, workspace, (hipStream_t)stream);
+}
+
 int emdr2_mips_audit(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const float *emax_sq, const float *block_norm_sq,
                      const void *shadow, const void *table, uint64_t *report, emdr2_stream_t stream)
 {

@@ -3,6 +3,7 @@
 #include "mips_device.h"
 #include "mips_kernels.h"
 #include "mips_derived.h"
+#include "mips_digest.h"
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
 
@@ -322,49 +323,27 @@ int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int6
     return CHECK_LAUNCH();
 }
 
-// splitmix64's finaliser (include/emdr2_mips.h states the digest in full)
-__device__ __forceinline__ uint64_t digest_mix(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
-    return ((uint64_t)hi << 32) | lo;
-}
+// g(r), h(r) and the stripe walk are stated once, in mips_digest.h; here the walk's sink folds the rows of [row_lo, row_hi) into the
+// workgroup's sum and xor.  One workgroup per 128-row stripe; each row is finished once, and the workgroup issues ONE 64-bit add and ONE
+// 64-bit xor.  Rows outside [row_lo, row_hi) -- the rest of a partly covered stripe, the zero padding past the shard's end -- are read and
+// left out.
+struct DigestFoldSink {
+    int64_t row_lo, row_hi;
+    uint64_t sum, x;
+    __device__ __forceinline__ void row(int64_t r, uint64_t g)
+    {
+        if (r >= row_lo && r < row_hi) { sum += g; x ^= g; }
+    }
+};
 
-// One workgroup per 128-row stripe, walking it in storage order: chunk after chunk, one contiguous 8 KiB block each (thread t takes the
-// 16-byte slots t and t + 256: rows t / 4 and 64 + t / 4).  acc(r) is a sum over position-tagged words, so a thread keeps one partial sum
-// for each of its two rows across all chunks, whatever slot the swizzle hands it; the four lanes of a row then fold their partial sums,
-// each row is finished once, and the workgroup issues ONE 64-bit add and ONE 64-bit xor.  Rows outside [row_lo, row_hi) -- the rest of a
-// partly covered stripe, the zero padding past the shard's end -- are read and left out.
 __global__ void __launch_bounds__(256) digest_rows_kernel(const char *__restrict__ tiled, int nch, int64_t first_stripe, int64_t row_lo, int64_t row_hi,
                                                           int64_t row_base, unsigned long long *__restrict__ digest)
 {
     __shared__ uint64_t sh_sum[4], sh_xor[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t stripe = first_stripe + blockIdx.x;
-    const uint4 *block = (const uint4 *)(tiled + (size_t)stripe * nch * STRIPE_CHUNK_BYTES);
-    const int ri = tid >> 2, sp = tid & 3;                            // (row 64 + ri has the same swizzle: bits 2..3 of the row agree)
-    const int s = sp ^ ((ri >> 2) & 3);
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll 2
-    for (int c = 0; c < nch; ++c) {
-        const uint4 a = block[(size_t)c * 512 + tid], b = block[(size_t)c * 512 + 256 + tid];
-        const uint64_t tag = (uint64_t)((c * 4 + s) * 4 + 1) << 32;    // word j of the row carries (j + 1) << 32
-        acc0 += digest_mix(a.x | tag) + digest_mix(a.y | (tag + (1ull << 32))) + digest_mix(a.z | (tag + (2ull << 32))) + digest_mix(a.w | (tag + (3ull << 32)));
-        acc1 += digest_mix(b.x | tag) + digest_mix(b.y | (tag + (1ull << 32))) + digest_mix(b.z | (tag + (2ull << 32))) + digest_mix(b.w | (tag + (3ull << 32)));
-    }
-    acc0 += shfl_xor_u64(acc0, 1); acc0 += shfl_xor_u64(acc0, 2);
-    acc1 += shfl_xor_u64(acc1, 1); acc1 += shfl_xor_u64(acc1, 2);
-    uint64_t sum = 0, x = 0;
-    if (sp == 0) {
-        const int64_t r0 = stripe * STRIPE_ROWS + ri, r1 = r0 + 64;
-        if (r0 >= row_lo && r0 < row_hi) { const uint64_t g = digest_mix(acc0 ^ ((uint64_t)(row_base + r0 + 1) * 0x9E3779B97F4A7C15ull)); sum += g; x ^= g; }
-        if (r1 >= row_lo && r1 < row_hi) { const uint64_t g = digest_mix(acc1 ^ ((uint64_t)(row_base + r1 + 1) * 0x9E3779B97F4A7C15ull)); sum += g; x ^= g; }
-    }
+    DigestFoldSink sink = {row_lo, row_hi, 0, 0};
+    digest_stripe_walk(tiled, nch, first_stripe + blockIdx.x, row_base, sink);
+    uint64_t sum = sink.sum, x = sink.x;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { sum += shfl_xor_u64(sum, o); x ^= shfl_xor_u64(x, o); }
     if (lane == 0) { sh_sum[wave] = sum; sh_xor[wave] = x; }
@@ -390,12 +369,6 @@ int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int6
 // (the grid is capped like generation_stats_kernel's: the workgroups end in two atomics on the same two words); the up to six loose rows go
 // to the first threads of workgroup 0.  Per-thread partials, a wave and an LDS reduction, ONE 64-bit add and ONE 64-bit xor per workgroup;
 // no workgroup waits on another.
-#define DIGEST_STAMP_TAG (0x47454E53ull << 32)
-__device__ __forceinline__ uint64_t digest_stamp(uint32_t g, int64_t number)
-{
-    return digest_mix(digest_mix((uint64_t)g | DIGEST_STAMP_TAG) ^ ((uint64_t)(number + 1) * 0x9E3779B97F4A7C15ull));
-}
-
 __global__ void __launch_bounds__(256) digest_stamps_kernel(const uint32_t *__restrict__ generation, int64_t row_lo, int64_t row_hi, int64_t body_lo,
                                                             int64_t n_vec, int64_t row_base, unsigned long long *__restrict__ digest)
 {

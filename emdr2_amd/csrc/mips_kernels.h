@@ -107,6 +107,16 @@ int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int6
 int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
 // the digest of the generation stamps of local rows [row_offset, row_offset + n_chunk), folded into digest[0] / digest[1] the same way
 int mips_launch_digest_stamps(const uint32_t *generation, int64_t row_offset, int64_t n_chunk, int64_t row_base, uint64_t *digest, hipStream_t stream);
+// incremental snapshots (mips_delta.hip): keys[r] = g(r) (+ h(r) with stamps) for local rows [row_offset, row_offset + n_chunk); and
+// emdr2_mips_changed_rows: the rows whose key differs from base_keys[r], as global rows in ascending order, -1 behind them; out_info as
+// documented in include/emdr2_mips.h.  Three launches (one with n_rows == 0), phases ordered by launch boundaries alone.
+// workspace: mips_changed_rows_workspace_bytes(n_rows) -- per stripe a mask, a count and four digest words; five words per slab
+#define MIPS_DELTA_MAX_SLABS 512
+size_t mips_changed_rows_workspace_bytes(int64_t n_rows);
+int mips_launch_row_keys(const void *tiled, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base, const uint32_t *generation, uint64_t *keys,
+                         hipStream_t stream);
+int mips_launch_changed_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const uint32_t *generation, const uint64_t *base_keys,
+                             int64_t cap, int64_t *out_rows, uint64_t *out_info, void *workspace, hipStream_t stream);
 // index audit (mips_audit.hip): the report of emdr2_mips_audit for the padded image of n_rows rows; e8 / table null: no shadow;
 // sealed_blocks = ceil(n_rows / 256), the blocks a seal covers; block_norm_sq may be null
 struct AuditParams {

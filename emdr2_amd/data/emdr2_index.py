@@ -196,6 +196,34 @@ def digest_stamps(stamps, first_row_number=0):
     return int(total), int(x)
 
 
+def row_keys(rows, stamps=None, first_row_number=0):
+    """The per-row keys of an incremental snapshot -> uint64 [n]: g(r) of fp16 `rows` [n, dim], plus (mod 2^64) h(r) of `stamps` (uint32 or
+    int32 [n]) when given, row i numbered `first_row_number + i` -- the numpy restatement of emdr2_mips_row_keys (include/emdr2_mips.h).
+    Their sum and xor are `digest_rows` (+ / ^ `digest_stamps`).  A test and offline instrument, like `digest_rows`."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.float16 or rows.ndim != 2 or rows.shape[1] % 2:
+        raise ValueError("rows must be float16 [n, even dim]")
+    n = rows.shape[0]
+    if stamps is not None:
+        stamps = np.asarray(stamps)
+        if stamps.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or stamps.shape != (n,):
+            raise ValueError("stamps must be uint32 or int32 [%d]" % n)
+    keys = np.empty(n, dtype=_U64)
+    tags = np.arange(1, rows.shape[1] // 2 + 1, dtype=_U64) << _U64(32)
+    with np.errstate(over='ignore'):
+        for lo in range(0, n, _DIGEST_BLOCK_ROWS):
+            block = np.ascontiguousarray(rows[lo:lo + _DIGEST_BLOCK_ROWS])
+            acc = _digest_mix(block.view('<u4').astype(_U64) | tags).sum(axis=1, dtype=_U64)
+            number = np.arange(first_row_number + lo + 1, first_row_number + lo + 1 + block.shape[0], dtype=np.int64).astype(_U64)
+            number = number * _U64(0x9E3779B97F4A7C15)
+            key = _digest_mix(acc ^ number)
+            if stamps is not None:
+                word = np.ascontiguousarray(stamps[lo:lo + block.shape[0]]).view(np.uint32).astype(_U64)
+                key = key + _digest_mix(_digest_mix(word | _U64(_STAMP_TAG)) ^ number)
+            keys[lo:lo + block.shape[0]] = key
+    return keys
+
+
 def combine_digests(pairs):
     """Digests of disjoint row sets -> the digest of their union: sums add mod 2^64, xors xor."""
     total, x = 0, 0
@@ -476,6 +504,7 @@ class HipIndexShard(object):
         self._block_norms = None                                   # max ||row||^2 per 256-row block of self.tiled (update_rows), built on first use
         self._scatter_ws = None                                    # workspace of update_rows_at (claim words + touched-block list), grown on demand
         self._oldest_ws = None                                     # workspace of oldest_rows (digit histograms, per-slab counts), grown on demand
+        self._delta_ws = None                                      # workspace of changed_rows (per-stripe masks, counts, digests), grown on demand
         # generation stamps of self.tiled (int32 storage of the device's uint32 words: values are below 2^31), of the refresh spare, and
         # the counter of rows that newest-wins updates left alone
         self.generation = torch.zeros(max(self.n_rows, 1), dtype=torch.int32, device=self.device) if generations else None
@@ -1002,6 +1031,76 @@ class HipIndexShard(object):
             raise ValueError("generation stamps must be below 2^31")
         self.generation[local_row:local_row + n].copy_(torch.from_numpy(np.array(stamps.view(np.int32), copy=True)))
 
+    def set_stamps_at(self, local_rows, stamps):
+        """A scattered `set_stamps`: `stamps` (host uint32 or int32 [n], every value below 2^31) -> the stamps of the rows `local_rows`
+        (int64 [n], host or this device; every entry in [0, n_rows), no row named twice) -- an incremental snapshot's stamps, after its
+        rows are in.  One indexed copy, enqueued on the current stream."""
+        stamps = np.ascontiguousarray(stamps)
+        if stamps.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or stamps.ndim != 1:
+            raise ValueError("stamps must be a host uint32 or int32 [n] array")
+        local_rows = torch.as_tensor(local_rows)
+        if local_rows.dtype != torch.int64 or local_rows.dim() != 1 or local_rows.shape[0] != stamps.shape[0]:
+            raise ValueError("local_rows must be int64 [%d]" % stamps.shape[0])
+        self._check_stamp_range(0, 0)
+        if stamps.shape[0] == 0:
+            return
+        if int(stamps.view(np.uint32).max()) > _native.GEN_MAX:
+            raise ValueError("generation stamps must be below 2^31")
+        if not local_rows.is_cuda and (int(local_rows.min()) < 0 or int(local_rows.max()) >= self.n_rows):
+            raise ValueError("local_rows outside this shard's [0, %d)" % self.n_rows)
+        values = torch.from_numpy(np.array(stamps.view(np.int32), copy=True)).to(self.device)
+        self.generation.index_copy_(0, local_rows.to(self.device), values)
+
+    # -- incremental snapshots: per-row keys and the rows whose key differs from a base's (emdr2_mips_row_keys / _changed_rows) ------------
+    def row_keys(self, local_row=0, n=None, out=None):
+        """The keys of rows [local_row, local_row + n) of the live image (default: the whole shard): g(r), plus h(r) on a shard with
+        stamps -- the host `row_keys` of the same rows and stamps, bit for bit.  -> CUDA int64 [n_rows] (the uint64 keys' bit patterns)
+        whose slots [local_row, local_row + n) have been written on the current stream; `out`: such a tensor to write into (the other
+        slots are left alone; without `out` they are uninitialised)."""
+        local_row = int(local_row)
+        n = self.n_rows - local_row if n is None else int(n)
+        self._check_range(local_row, n)
+        if out is None:
+            out = torch.empty(self.n_rows, dtype=torch.int64, device=self.device)
+        elif out.dtype != torch.int64 or out.dim() != 1 or out.shape[0] != self.n_rows or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA int64 [%d] tensor" % self.n_rows)
+        if n:
+            _native.check(self.lib.emdr2_mips_row_keys(self.tiled.data_ptr(), self.n_rows, self.dim, local_row, n, self.row_base,
+                                                       None if self.generation is None else self.generation.data_ptr(), out.data_ptr(),
+                                                       _native.stream_ptr()), "row_keys")
+        return out
+
+    def changed_rows(self, base_keys, cap):
+        """The rows of this shard whose key differs from `base_keys` (CUDA int64 [n_rows], as `row_keys` gave them for a base snapshot;
+        read, never written) -> (rows, info): `rows` CUDA int64 [cap], the changed GLOBAL rows in ascending order, the first `cap` of
+        them, -1 in every slot behind; `info` CUDA int64 [8] (bit patterns of uint64 words): rows changed, rows stored, the (sum, xor)
+        of `digest()` and of `digest_stamps()` (0, 0 without stamps) of the whole shard at this stream point, the smallest changed global
+        row (-1: none), 0.  One pass over the image and two small launches on the current stream, no host read; the caller orders it
+        against the shard's writers.  `cap` is clamped to the shard's rows.  A shard being filled or refreshed is refused."""
+        if self._filled != self.n_rows:
+            raise ValueError("shard not fully populated (%d of %d rows)" % (self._filled, self.n_rows))
+        if self._refreshing:
+            raise ValueError("a swap refresh is in progress (begin_refresh without commit_refresh): the live image is about to be replaced")
+        if (not torch.is_tensor(base_keys) or base_keys.dtype != torch.int64 or base_keys.dim() != 1 or base_keys.shape[0] != self.n_rows
+                or base_keys.device != self.device or not base_keys.is_contiguous()):
+            raise ValueError("base_keys must be a contiguous CUDA int64 [%d] tensor" % self.n_rows)
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        cap = min(cap, self.n_rows)
+        nbytes = ctypes.c_size_t()
+        _native.check(self.lib.emdr2_mips_changed_rows_workspace_bytes(self.n_rows, ctypes.byref(nbytes)), "changed_rows_workspace_bytes")
+        if self._delta_ws is None or self._delta_ws.numel() < nbytes.value:
+            self._delta_ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=self.device)
+        ws = self._delta_ws
+        rows = torch.empty(cap, dtype=torch.int64, device=self.device)
+        info = torch.empty(8, dtype=torch.int64, device=self.device)
+        _native.check(self.lib.emdr2_mips_changed_rows(self.tiled.data_ptr(), self.n_rows, self.dim, self.row_base,
+                                                       None if self.generation is None else self.generation.data_ptr(),
+                                                       base_keys.data_ptr() if self.n_rows else None, cap, rows.data_ptr() if cap else None,
+                                                       info.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr()), "changed_rows")
+        return rows, info
+
 
 def merge_shard_results(dist, idx, row):
     """[S, Q, k] per-shard canonical lists (device; dist fp16, or fp32 for the FaissMIPSIndex-style scores) -> merged [Q, k] via the HIP
@@ -1051,6 +1150,8 @@ class DistributedBruteForceIndex(object):
         self.generations = bool(generations)                       # (extra, optional) the shard keeps generation stamps: HipIndexShard
         self._load_generation = 0                                  # the stamp of rows that add_arrays uploads: 0, or a snapshot's iteration
         self.stamps_restored = False                               # the last load_flat_snapshot set every row's own stamp from the sidecar
+        self.delta_base = None                                     # {"keys", "base", "path"}: the row keys and digests of the published base snapshot (save_delta)
+        self.delta_applied = None                                  # the meta of the delta the last load_flat_snapshot(delta=True) applied
         self.embed_data = embed_data
         self.use_gpu = use_gpu
         self.process_group = process_group
@@ -1207,18 +1308,30 @@ class DistributedBruteForceIndex(object):
         return audit_result(words, counts[12] > 0, counts[13] > 0)
 
     # -- snapshots (data/index_snapshot.py) ----------------------------------------------------------------------------------------------
-    def save_flat_file(self, path, meta=None):
+    def save_flat_file(self, path, meta=None, track_deltas=False):
         """Write the index as it stands in HBM to the `FlatEmbeddingFile` `path` plus `path + '.meta'` (JSON: format, n, dim, world, the
         DEVICE digest of what was exported, ids_crc32, and the caller's `meta`: iteration / refreshes / mode).  Collective and synchronous;
         the file appears atomically and a data file without a meta is an incomplete snapshot.  An index with generation stamps also
         writes every row's stamp to the sidecar `path + '.gen'` and their device digest to the meta's `stamps`.  After
-        `IndexBuilder.build_into_index` this is the fast offline indexer."""
+        `IndexBuilder.build_into_index` this is the fast offline indexer.  `track_deltas`: also keep the key of every exported row; the
+        snapshot becomes `self.delta_base`, the base of later `save_delta`s."""
         from emdr2_amd.data.index_snapshot import IndexSnapshotWriter
-        writer = IndexSnapshotWriter(self, chunk_rows=min(_UPLOAD_ROWS, 1 << 18))
+        writer = IndexSnapshotWriter(self, chunk_rows=min(_UPLOAD_ROWS, 1 << 18), track_deltas=track_deltas)
         writer.begin(path, meta)
         writer.finish()
 
-    def load_flat_snapshot(self, path, audit=False):
+    def save_delta(self, path, meta=None, max_fraction=0.5, log=None):
+        """Write the rows that differ from the base snapshot at `path` -- the one `self.delta_base` describes: the last tracked
+        `save_flat_file` / `IndexSnapshotWriter`, or the base a `load_flat_snapshot(delta=True)` loaded -- to `path + '.delta'` plus
+        `path + '.delta.meta'` (data/index_snapshot.py).  A row is changed exactly when its key (row hash, plus stamp hash on a stamped
+        index) differs from the base's, whoever wrote it; the detection pass runs on the current stream at one point in time, then ONE
+        host read of its report.  Cumulative: always relative to the base, one file, replaced atomically.  Collective and synchronous.
+        If any rank has more than `max_fraction` of its rows changed, or there is no base, nothing is written, a stale delta is removed
+        and None is returned.  -> the delta's meta."""
+        from emdr2_amd.data import index_snapshot as snap
+        return snap.save_delta(self, path, meta, max_fraction, log)
+
+    def load_flat_snapshot(self, path, audit=False, delta=False, max_iteration=None):
         """Build the index from a snapshot written by `save_flat_file` at ANY world size and verify it: meta against the file's header
         and ids, then the device digest of what now stands in HBM (combined over the ranks) against the meta's.  A mismatch raises
         ValueError.  Generation stamps, on an index that keeps them: a snapshot taken from a stamped index carries every row's stamp in
@@ -1227,7 +1340,12 @@ class DistributedBruteForceIndex(object):
         ones.  A snapshot without stamps stamps every row with the meta's `iteration` (0 if absent), and ages are then a lower bound.  An
         index without stamps ignores the sidecar.  `self.stamps_restored` says which of the two happened.
         `audit`: then run `audit()` as well (the digest covers the fp16 rows only, not emax_sq or the int8 shadow) and raise
-        ValueError naming the non-zero words unless it is sound and canonical.  Returns the meta."""
+        ValueError naming the non-zero words unless it is sound and canonical.  Returns the meta.
+        `delta`: the verified base becomes `self.delta_base` (its keys are taken from the shard), so this index's own `save_delta` stays
+        relative to the same base; then a delta next to the snapshot that belongs to it, and whose `iteration` is at most
+        `max_iteration` (None: any), is applied and the result verified against the delta's meta (`index_snapshot.apply_delta`):
+        `self.delta_applied` holds its meta.  A delta that is not this base's, is damaged or is newer than `max_iteration` is skipped --
+        the base alone is a valid index -- and the returned meta says why under `"delta_skipped"`."""
         from emdr2_amd.data import index_snapshot as snap
         meta = snap.read_snapshot_meta(path)
         self.stamps_restored = False
@@ -1253,6 +1371,21 @@ class DistributedBruteForceIndex(object):
             if got != want:
                 raise ValueError("index snapshot %s: stamp digest %016x %016x in HBM, %016x %016x in the meta" % ((path,) + got + want))
             self.stamps_restored = True
+        self.delta_applied = None
+        if delta:                                                  # (what is decided below is read from files: the same on every rank)
+            self.delta_base = {"keys": snap.shard_keys(self.shard), "base": snap.base_of(meta), "path": os.path.abspath(path)}
+            try:
+                dmeta = snap.read_delta_meta(path, meta)
+                if max_iteration is not None and int(dmeta["iteration"]) > int(max_iteration):
+                    meta["delta_skipped"] = "the delta is of iteration %d, beyond %d" % (int(dmeta["iteration"]), int(max_iteration))
+                    dmeta = None
+            except FileNotFoundError:
+                dmeta = None
+            except ValueError as exc:
+                meta["delta_skipped"], dmeta = str(exc), None
+            if dmeta is not None:
+                snap.apply_delta(self, path, dmeta)
+                self.delta_applied = dmeta
         if audit:
             bad = audit_failures(self.audit())
             if bad:

@@ -62,7 +62,9 @@ class PreComputedEvidenceDocsRetriever(object):
         """--save-index-snapshot with --load: build the index from `<load>/evidence_index.flat` -- the index the checkpointed run was
         searching -- when its meta is valid, fits the evidence and is not newer than the checkpoint.  Every rank reads the same files and
         the digest check is combined over the ranks, so all decide alike.  Returns False (after one log line saying why) when
-        `--embedding-path` is to be loaded as without the flag."""
+        `--embedding-path` is to be loaded as without the flag.  With --save-index-deltas the snapshot is the BASE: a delta next to it
+        that belongs to it and is not newer than the checkpoint is applied and verified (`load_flat_snapshot(delta=True)`), and one more
+        log line says which iteration's delta that was, or why none was applied."""
         import os
         from emdr2_amd import checkpointing
         from emdr2_amd.data.index_snapshot import SNAPSHOT_NAME, read_snapshot_meta
@@ -83,7 +85,10 @@ class PreComputedEvidenceDocsRetriever(object):
                 raise ValueError("it was taken at iteration %d, the checkpoint at %d" % (int(meta.get("iteration", 0)), iteration))
             index = DistributedBruteForceIndex(embed_size=self.embedding_size, embed_data=None, use_gpu=getattr(args, "faiss_use_gpu", True),
                                                process_group=self.process_group, generations=bool(getattr(args, "index_generations", False)))
-            index.load_flat_snapshot(path)
+            if getattr(args, "save_index_deltas", False):      # base + the delta of a checkpoint that is not newer than the one being loaded
+                meta = index.load_flat_snapshot(path, delta=True, max_iteration=iteration)
+            else:
+                index.load_flat_snapshot(path)
         except (OSError, ValueError) as exc:
             say("index snapshot %s not used (%s): loading %s" % (path, exc, args.embedding_path))
             return False
@@ -93,6 +98,13 @@ class PreComputedEvidenceDocsRetriever(object):
             % (path, meta.get("iteration"), meta.get("mode"), meta["digest_sum"], meta["digest_xor"],
                "; generation stamps restored, digest %s %s" % (meta["stamps"]["digest_sum"], meta["stamps"]["digest_xor"])
                if index.stamps_restored else ""))
+        if getattr(args, "save_index_deltas", False):
+            applied = index.delta_applied
+            if applied is not None:
+                say("index snapshot %s: delta of iteration %d applied, %d rows (digest %s %s)"
+                    % (path, int(applied["iteration"]), applied["m"], applied["result"]["digest_sum"], applied["result"]["digest_xor"]))
+            else:
+                say("index snapshot %s: no delta applied (%s)" % (path, meta.get("delta_skipped", "there is none")))
         if index.stamps_restored:
             # a rolling snapshot that finished after its checkpoint holds rows written back by weights the checkpoint does not have; this
             # only reports them (collective: every rank restored stamps or none did)

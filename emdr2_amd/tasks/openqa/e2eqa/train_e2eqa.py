@@ -259,6 +259,18 @@ def index_generation_line(index, iteration, retrieved):
     return whole
 
 
+def save_index_delta(index, path, iteration, take_base):
+    """--save-index-deltas, after a checkpoint save that is not an index update: the rows that differ from the published snapshot go to
+    `path + '.delta'` (`DistributedBruteForceIndex.save_delta`; collective, one line on rank 0).  `take_base`: no refresher ever begins a
+    snapshot (--index-writeback alone), so the first call takes one, synchronously, and later calls write deltas against it."""
+    base = index.delta_base
+    if take_base and (base is None or base.get("path") != os.path.abspath(path)):
+        index.save_flat_file(path, {"iteration": iteration, "refreshes": 0, "mode": "writeback"}, track_deltas=True)
+        print_rank_0("index delta: base snapshot taken at iteration {}".format(iteration))
+        return None
+    return index.save_delta(path, {"iteration": iteration}, log=print_rank_0)
+
+
 def audit_index(index, iteration):
     """--audit-index-interval: one audit of the evidence index (`DistributedBruteForceIndex.audit`: every rank its own shard, the counters
     reduced over the index's group, so every rank holds the same result and takes the same decision).  Rank 0 prints one line; an index
@@ -310,8 +322,27 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
         from emdr2_amd.data.index_snapshot import SNAPSHOT_NAME, IndexSnapshotWriter
         lo, hi = indexer.index.local_rows()
         snapshots = indexer.snapshot_writer = IndexSnapshotWriter(
-            indexer.index, chunk_rows=IndexSnapshotWriter.paced_chunk_rows(hi - lo, args.index_reload_interval), log=print_rank_0)
+            indexer.index, chunk_rows=IndexSnapshotWriter.paced_chunk_rows(hi - lo, args.index_reload_interval), log=print_rank_0,
+            track_deltas=bool(getattr(args, "save_index_deltas", False)))
         snapshot_path = os.path.join(args.save, SNAPSHOT_NAME)
+    # --save-index-deltas: the index whose changed rows follow every checkpoint save but the one an index update takes -- there the next
+    # snapshot has just been begun.  (A swap refresher replaces whole images and the live one does not change between swaps: there is
+    # nothing for a delta to hold.)
+    deltas = None
+    if getattr(args, "save_index_deltas", False) and args.save and (indexer.in_place if indexer is not None else getattr(args, "index_writeback", False)):
+        from emdr2_amd.data.index_snapshot import SNAPSHOT_NAME
+        deltas = indexer.index if indexer is not None else getattr(getattr(model, "evidence_retriever", None), "mips_index", None)
+        snapshot_path = os.path.join(args.save, SNAPSHOT_NAME)
+
+    def checkpoint(iteration, finish=False):
+        _save(iteration, model, optimizer, lr_scheduler)
+        if finish and snapshots is not None and deltas is not None:
+            # (a no-op when none is open.)  Before the delta: publishing a snapshot drops the delta of the one it replaces, and a delta
+            # against the snapshot just finished brings the chunks it exported steps ago up to this boundary
+            snapshots.finish()
+        if deltas is not None:
+            # after this boundary's writers (refresher rows, write-back) and the snapshot writer's pump, before the next step
+            save_index_delta(deltas, snapshot_path, iteration, take_base=indexer is None)
     audit_interval = int(getattr(args, "audit_index_interval", 0) or 0)
     audited = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if audit_interval > 0 else None
     if audited is not None:
@@ -379,19 +410,19 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 print_rank_0(msg)
                 sums = {}
             if args.save and args.save_interval and iteration % args.save_interval == 0:
-                _save(iteration, model, optimizer, lr_scheduler)
+                checkpoint(iteration)
             if args.eval_interval and iteration % args.eval_interval == 0 and end_of_epoch_callback is not None:
                 end_of_epoch_callback(model, iteration)
                 end_of_epoch_callback2(model, iteration)
             if args.exit_interval and iteration % args.exit_interval == 0:                    # train_e2eqa.py:526-540
                 print_rank_0('exiting the program at iteration {}'.format(iteration))
                 if args.save:
-                    _save(iteration, model, optimizer, lr_scheduler)
+                    checkpoint(iteration, finish=True)
                 if snapshots is not None:
                     snapshots.finish()
                 return iteration
         if args.save:
-            _save(iteration, model, optimizer, lr_scheduler)
+            checkpoint(iteration, finish=True)
         if snapshots is not None:
             snapshots.finish()                        # (a no-op when none is open)
         if end_of_epoch_callback is not None:

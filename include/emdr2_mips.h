@@ -360,6 +360,47 @@ int emdr2_mips_digest_stamps(const uint32_t *generation, int64_t n_rows_total, i
                              uint64_t *digest, emdr2_stream_t stream);
 
 /*
+ * Incremental index snapshots: which rows of a shard differ from the rows a base snapshot holds, found from per-row keys.
+ *   key(r) = g(r)                       on a shard without stamps (generation == NULL)
+ *   key(r) = g(r) + h(r)  mod 2^64      on one with stamps
+ * g is the row hash of _digest_rows and h the stamp hash of _digest_stamps, both numbered row_base + r: a row is CHANGED exactly when its
+ * key differs from the key it had in the base, whoever wrote it -- a re-write of the same bits under a newer stamp included.  An
+ * "unchanged" verdict is wrong only on a 64-bit collision.
+ *   _row_keys          keys: device uint64[n_rows_total], 8-byte aligned; the slots [row_offset, row_offset + n_chunk) receive the keys of
+ *                      those local rows, every other slot is left alone.  One launch on `stream`.  On one stream, between the same two
+ *                      neighbours as the _export_rows / _digest_rows (/ _digest_stamps) of the same range, the keys are those of exactly
+ *                      the exported bits.  n_chunk == 0 is a no-op returning 0.
+ *   _changed_rows      ONE pass over the live image (it streams the shard once, like _digest_rows), then two small launches.
+ *                        base_keys  device uint64[n_rows], 8-byte aligned: read, never written
+ *                        out_rows   device int64[cap], 8-byte aligned: the GLOBAL rows row_base + r with key(r) != base_keys[r], in
+ *                                   ASCENDING row order, the first min(n_changed, cap) of them; every slot behind receives -1
+ *                        out_info   device uint64[8], 8-byte aligned; every word is written by the call:
+ *                                     0     n_changed
+ *                                     1     n_stored = min(n_changed, cap)
+ *                                     2, 3  sum and xor of g(r) over ALL rows of the shard as they stand: the bits _digest_rows gives for
+ *                                           the whole shard at the same stream point
+ *                                     4, 5  the same for h(r) (_digest_stamps); 0 without stamps
+ *                                     6     the smallest changed global row, ~0 when none
+ *                                     7     0
+ *                      The pass leaves per 128-row stripe a changed mask, a count and its digest words in the workspace; per-slab sums and
+ *                      an ordered expansion of the masks at their global ranks follow.  Every workspace word a launch reads was stored by
+ *                      one workgroup of the launch before: no atomics on global memory, nothing to clear, no workgroup waits on another,
+ *                      and the output is a function of the image, the stamps and the keys alone -- not of the grid nor of the order the
+ *                      workgroups run in.  Nothing allocated, no host synchronisation; the caller orders the call against writers of the
+ *                      shard.  The zero padding past n_rows is read and never counted.  workspace: device memory, 16-byte aligned, at
+ *                      least _changed_rows_workspace_bytes(n_rows) bytes; its contents need not be kept, nor cleared, between calls.
+ *                      cap == 0: the report only, out_rows may be NULL.  n_rows == 0: zeros, word 6 is ~0, nothing is read.
+ * EMDR2_E_BADARG: null or misaligned pointers (generation may be NULL: no stamps), a dim outside the layout's envelope, a range outside
+ * the shard, row_base < 0, n_rows >= 2^31, cap < 0 or cap > n_rows; EMDR2_E_WORKSPACE: workspace_bytes too small.
+ */
+int emdr2_mips_row_keys(const void *tiled, int64_t n_rows_total, int dim, int64_t row_offset, int64_t n_chunk, int64_t row_base,
+                        const uint32_t *generation, uint64_t *keys, emdr2_stream_t stream);
+int emdr2_mips_changed_rows_workspace_bytes(int64_t n_rows, size_t *bytes);
+int emdr2_mips_changed_rows(const void *tiled, int64_t n_rows, int dim, int64_t row_base, const uint32_t *generation,
+                            const uint64_t *base_keys, int64_t cap, int64_t *out_rows, uint64_t *out_info, void *workspace,
+                            size_t workspace_bytes, emdr2_stream_t stream);
+
+/*
  * Index audit: one streaming pass over a shard's LIVE images that re-checks the premises of the search's
  * proof from the stored bits and, separately, the "bit for bit a fresh build" contract of the derived structures -- emax_sq, the
  * block-norm table, the int8 shadow image and its {s_b, N_b, D_b} table, which pack_rows, seal_shadow, update_rows, update_rows_scattered
