@@ -202,6 +202,35 @@ def test_fp32_validation_entry_points_validate_their_arguments(lib):
     assert lib.emdr2_f32_retriever_prior_bwd(one, one, one, one, one, None, 2, 4, 16, 1.0, None) == -1
 
 
+def test_assemble_evidence_validates_its_arguments(lib):
+    """include/emdr2_assembly.h: null pointers, shapes the kernel cannot lay out and a null table inside the arena struct are refused (-1)
+    before any launch."""
+    from emdr2_amd import _native
+    one = ctypes.c_void_p(4096)
+    arena = _native.EvidenceArenaStruct()
+    tables = [f[0] for f in arena._fields_ if f[0] != "n_docs"]
+    assert len(tables) == 8
+    for t in tables:
+        setattr(arena, t, 4096)
+    arena.n_docs = 10
+
+    def call(arena_p=ctypes.byref(arena), ptrs=(one,) * 9, n_b=2, k_retrieved=4, topk=3, q_stride=8, s_ret=12, s=24):
+        ids, uid, q, ql, ctx, typ, ext, one_, kept = ptrs
+        return lib.emdr2_assemble_evidence(arena_p, ids, n_b, k_retrieved, topk, uid, q, q_stride, ql, s_ret, s, 2, 3, 0, ctx, typ, ext, one_, kept, None)
+    assert call(arena_p=None) == -1
+    for i in range(9):                                                   # topk_ids, query_uid, query_t5, query_len and the five outputs
+        assert call(ptrs=tuple(None if j == i else one for j in range(9))) == -1, i
+    assert call(k_retrieved=2) == -1                                     # k_retrieved < topk
+    assert call(topk=0, k_retrieved=0) == -1
+    assert call(s=1) == -1 and call(s_ret=1) == -1                       # a row holds at least one token and the closing [SEP]
+    assert call(q_stride=0) == -1
+    assert call(n_b=0) == -1 and call(n_b=-3) == -1
+    for t in tables:                                                     # a null table inside the arena struct
+        setattr(arena, t, None)
+        assert call() == -1, t
+        setattr(arena, t, 4096)
+
+
 def test_vector_cast_entry_points_reject_odd_lengths_and_misaligned_pointers(lib):
     """The four-elements-per-thread kernels (gradient exchange casts, flat Adam) take n % 4 == 0, 16-byte aligned fp32 and 8-byte aligned
     bf16 pointers: anything else is refused (-1) before a launch; LayerNorm backward + mask takes H = 768 only (-4)."""

@@ -36,3 +36,13 @@ def test_case_covers_every_branch():
     assert mains == {0, 1, -1} and sizes == {1, 2, 3}
     assert ao.get_neighbour_paragraphs([5, 6], 6) == ([6], -1)        # doc_row[-1:2]
     assert int(case["query_uid"][2]) in case["topk_ids"][2].tolist()
+    # which truncation branch each of the 30 rows takes (labels of tests/assembly_edges.py).  The golden case does NOT reach: ctx
+    # cut_in_title, cut_at_sep; one eq, cut_in_query, cut_in_title, cut_at_sep; ext overlong, single_eq, single_cut, main_cut_by1,
+    # first_fit_3, first_eq_2, first_eq_3, last_eq, mid_leftcut_by1, mid_lefteq_righteq -- tests/test_assembly_edges_gpu.py does.
+    from tests import assembly_edges as ae
+    (ctx, one, ext), rows = ae.label_counts([dict(case, cfg=assembly_cases.CFG)])
+    reached = lambda d: {k for k, v in d.items() if v}
+    assert rows == 30
+    assert reached(ctx) == {"fit", "eq", "cut_in_passage"} and reached(one) == {"fit", "cut_in_passage"}
+    assert reached(ext) == {"single", "main_cut", "first_fit_2", "first_cut_2", "first_cut_3", "last_fit", "last_cut", "last_cut_skipwhole",
+                            "mid_leftcut", "mid_rightfit", "mid_righteq", "mid_rightcut", "mid_lefteq_rightcut"}
