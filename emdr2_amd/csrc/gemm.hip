@@ -14,6 +14,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "gemm_common.h"
+#include "tile_order.h"
+#include "device_attr.h"
 #include "exp_hooks.h"
 #include "ops_timing.h"
 
@@ -37,8 +39,8 @@ struct GemmParams {
     float drop_p;             // dropout on (acc*alpha + bias [gelu]) before the residual add: bias_dropout_add (transformer.py:397-413)
     uint32_t seed;            // keep bit = emdr2_keep(row_hash(seed, m), n, thr)
     int ablate;               // -DEMDR2_EXPERIMENTS builds only (EMDR2_GEMM_ABLATE): 1 = no epilogue, 2 = no k-loop, 3 = epilogue without global stores
-    int ngroup;               // n-tiles per L2-resident group of B panels (order >= 1)
-    int tiles_m, tiles_n, order; // order 1: 1-D grid, n-tiles fastest inside a per-XCD contiguous tile range (operand A read once from HBM)
+    TileOrder tiles;          // order 1: 1-D grid walking this tile order (tile_order.h); order 0: 2-D grid, blockIdx is the tile
+    int order;
     int splitk;               // > 1: blockIdx.z also enumerates K slices; fp32 output accumulated with atomics (C pre-zeroed)
 };
 
@@ -61,19 +63,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
 
     int tm = blockIdx.x, tn = blockIdx.y;
     if (p.order >= 1) {
-        // Workgroup ids are dealt round-robin to the 8 XCDs, each with its own 4 MB L2.  Give every XCD one contiguous range of the tile
-        // sequence, and order the sequence so that what is shared stays in that L2: n-tiles are taken in groups of `ngroup` B panels
-        // that fit the L2 (a 256 x K panel of the weight matrix each), and inside a group the walk is n-fastest, so the tiles sharing an
-        // A panel run back to back.  A then leaves HBM once per group (N = 3072, K = 768: twice instead of 12 times) and B stays
-        // L2-resident instead of cycling through a working set larger than the cache.
-        const int total = p.tiles_m * p.tiles_n, id = blockIdx.x;
-        const int per = (total + 7) >> 3;
-        int t = (id & 7) * per + (id >> 3);
-        if (t >= total) return;                                        // ragged tail of the last XCD ranges (grid is padded to 8 * per)
-        const int full = p.ngroup * p.tiles_m;                         // tiles in one full n-group
-        const int g = t / full, r = t - g * full;
-        const int gsize = (g + 1) * p.ngroup <= p.tiles_n ? p.ngroup : p.tiles_n - g * p.ngroup;   // the last group may be narrower
-        tm = r / gsize; tn = g * p.ngroup + (r - tm * gsize);
+        int t;
+        if (!xcd_item(p.tiles.tiles_m * p.tiles.tiles_n, t)) return;
+        tile_order_coords(p.tiles, t, tm, tn);
     }
     const int m0 = tm * BM, n0 = tn * BN;
     const int zb = blockIdx.z / p.splitk, zs = blockIdx.z % p.splitk;
@@ -207,9 +199,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                     const long long o = coff + (long long)m * p.ldc + ncol;
                     if (affine) {
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = v[j] * p.alpha + bv[j];
+                        for (int j = 0; j < 8; ++j) v[j] = epi_affine(v[j], p.alpha, bv[j]);
                     }
-                    if (p.gelu == 2) {                                   // activation + its derivative (the derivative goes to C2)
+                    if (p.gelu == 2) {                                  // activation + its derivative (the derivative goes to C2)
                         float d[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) v[j] = gelu_erf_with_grad(v[j], d[j]);
@@ -241,16 +233,12 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                     }
                     if (p.R) {
                         const uint32_t rw[4] = {rr[g].x, rr[g].y, rr[g].z, rr[g].w};
-                        // the value meets the residual as the bf16 the reference's F.linear would have stored (and as gemm8.hip, whose staging
-                        // buffer holds bf16, sees it): one rounding before the add, one after -- the same in every GEMM kernel of the library
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = bf16_to_f32(f32_to_bf16(v[j]));
+                        for (int j = 0; j < 8; ++j) v[j] = round_to_stored_bf16(v[j]);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float r0 = bf16_to_f32((uint16_t)(rw[j] & 0xffff)), r1 = bf16_to_f32((uint16_t)(rw[j] >> 16));
-                            if (p.rmode == 0) { v[2 * j] += r0; v[2 * j + 1] += r1; }
-                            else if (p.rmode == 2) { v[2 * j] *= r0; v[2 * j + 1] *= r1; }
-                            else { v[2 * j] *= gelu_erf_grad(r0); v[2 * j + 1] *= gelu_erf_grad(r1); }
+                            const floatx2_t x = epi_residual_pair(floatx2_t{v[2 * j], v[2 * j + 1]}, rw[j], p.rmode);
+                            v[2 * j] = x[0]; v[2 * j + 1] = x[1];
                         }
                     }
                     uint32_t w[4];
@@ -280,7 +268,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                 const int m = mrow0 + mi * 32 + (r & 3) + 8 * (r >> 2);
                 if (m >= p.M) continue;
                 const long long o = coff + (long long)m * p.ldc + n;
-                float v = acc[mi][ni][r] * p.alpha + bias;
+                float v = epi_affine(acc[mi][ni][r], p.alpha, bias);
                 if (p.gelu == 2) { float d; v = gelu_erf_with_grad(v, d); ((uint16_t *)p.C2)[o] = f32_to_bf16(d); }
                 else {
                     if (p.C2) ((uint16_t *)p.C2)[o] = f32_to_bf16(v);
@@ -289,8 +277,8 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                 if (p.drop_p > 0.f) v = emdr2_keep(emdr2_row_hash(p.seed, (unsigned long long)m), (uint32_t)n, emdr2_drop_thr(p.drop_p)) ? v * emdr2_keep_scale(p.drop_p) : 0.f;
                 if (p.R) {
                     const float rv = bf16_to_f32(((const uint16_t *)p.R)[o]);
-                    if (!p.out_f32) v = bf16_to_f32(f32_to_bf16(v));          // as above: bf16 before it meets the residual
-                    v = p.rmode == 0 ? v + rv : (p.rmode == 2 ? v * rv : v * gelu_erf_grad(rv));
+                    if (!p.out_f32) v = round_to_stored_bf16(v);          // (an fp32 output was never stored as bf16)
+                    v = p.rmode == 0 ? v + rv : (p.rmode == 2 ? v * rv : v * gelu_erf_grad(rv));   // epi_residual_pair's combine on this lane's one element
                 }
                 if (p.splitk > 1) atomicAdd(&((float *)p.C)[o], v);
                 else if (p.out_f32) ((float *)p.C)[o] = v;
@@ -306,28 +294,16 @@ static int launch_gemm_v(const GemmParams &p, int batch, hipStream_t stream)
     constexpr int BM = WM * 32 * MI, BN = WN * 128;
     constexpr int RING = GNST * (BM + BN) * 64, STAGING = WM * WN * 32 * 132 * 4;
     constexpr int LDS = (VEC && STAGING > RING) ? STAGING : RING;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)gemm_nt_kernel<WM, WN, VEC, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
+    if (lds_opt_in<gemm_nt_kernel<WM, WN, VEC, MI>>(LDS) != LDS_OPT_IN_OK) return -3;
     GemmParams q = p;
-    q.tiles_m = (p.M + BM - 1) / BM; q.tiles_n = (p.N + BN - 1) / BN;
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     EXP_GEMM_TILE_ORDER(order_env, ablate_env, l2_env)
     q.ablate = ablate_env;
-    q.order = (order_env >= 1 && q.tiles_n > 1 && q.tiles_m > 8) ? 1 : 0;
-    // B panels of BN x K bf16 that fit about half of a 4 MB L2 (the rest holds the A panels in flight and the output lines in transit)
-    const long long panel = (long long)BN * p.K * 2;
-    int ng = (int)((long long)l2_env * 1024 / (panel > 0 ? panel : 1));
-    if (ng < 1) ng = 1;
-    if (ng > q.tiles_n || order_env == 2 || 2 * ng < q.tiles_n || (long long)p.N * p.K * 2 <= (4ll << 20)) ng = q.tiles_n;   // one group = plain n-fastest: EMDR2_GEMM_ORDER=2, or B panels so
-                                                                                  // large (K = 3072) that grouping would re-read A 3+ times, or a B that fits the 4 MB L2 whole
-                                                                                  // (N = 2304, K = 768: measured 1.7 % better ungrouped; N = 3072: 2.3 % better grouped)
-    // balance the groups: e.g. 9 n-tiles with room for 6 -> 5 + 4 rather than 6 + 3
-    const int groups = (q.tiles_n + ng - 1) / ng;
-    q.ngroup = (q.tiles_n + groups - 1) / groups;
-    dim3 grid(q.tiles_m, q.tiles_n, batch * p.splitk);
-    if (q.order == 1) grid = dim3(((q.tiles_m * q.tiles_n + 7) / 8) * 8, 1, batch * p.splitk);
+    // (2^24 tiles and more: outside what the reciprocals of the tile order are stated for -- and outside any memory)
+    q.order = (order_env >= 1 && tiles_n > 1 && tiles_m > 8 && (long long)tiles_m * tiles_n < (1ll << 24)) ? 1 : 0;
+    q.tiles = tile_order_plan(tiles_m, tiles_n, BN, p.K, p.N, l2_env, 4096, order_env == 2 ? tiles_n : 0);   // EMDR2_GEMM_ORDER=2: one group
+    dim3 grid(tiles_m, tiles_n, batch * p.splitk);
+    if (q.order == 1) grid = dim3(8 * xcd_per(tiles_m * tiles_n), 1, batch * p.splitk);
     hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, VEC, MI>), grid, dim3(WM * WN * 64), LDS, stream, q);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -20,7 +20,7 @@
 //    so the matrix pipe of a SIMD alternates between its two waves instead of both stalling on the same barrier.
 //  * persistent: the DMA stream runs on across tile seams (the next tile's first six half-tiles are in flight during the epilogue), the
 //    epilogue stages through its own 32 KiB of LDS (the ring stays live), both wave halves run their epilogues in the same barrier interval.
-//  * XCD-aware tile order as in gemm.hip: each XCD walks one contiguous range of the n-fastest tile sequence, its 32 CUs take consecutive
+//  * XCD-aware tile order (tile_order.h): each XCD walks one contiguous range of the n-fastest tile sequence, its 32 CUs take consecutive
 //    tiles, so the A panel shared by the n-tiles of an m-row leaves HBM once and stays in that XCD's L2.
 // Epilogue: alpha, + bias[n], optional pre-activation output, exact-erf GELU, dropout (csrc/rng.h), then through LDS into row order:
 // + residual[m, n] (or * gelu'(residual): the fused GELU backward), bf16, 16-byte streaming stores of whole 128-byte row segments.
@@ -28,6 +28,8 @@
 // each row's 256-column tile to (max, sum exp) and picks the gold logit, so the [tokens, vocab] matrix never reaches HBM.
 #include "../../include/emdr2_ops.h"
 #include "gemm_common.h"
+#include "tile_order.h"
+#include "device_attr.h"
 #include "exp_hooks.h"
 #include "ops_timing.h"
 #include <stdlib.h>
@@ -46,8 +48,8 @@ struct G8Params {
     int gelu;
     float drop_p;
     uint32_t seed;
-    int tiles_m, tiles_n, ngroup, total, per;   // tile order: `per` consecutive sequence positions per XCD
-    uint32_t mg_full, mg_group, mg_last;        // ceil(2^32 / d) for d = ngroup * tiles_m, ngroup, width of the last group (tile_coords corrects the +1)
+    TileOrder order;           // tile_order.h
+    int total, per;            // tiles; `per` consecutive sequence positions per XCD
     // LSE mode (lse_part != nullptr): nothing is stored to C; per (row, n-tile) partial max / sum-exp and the gold logit are written instead
     float *lse_max, *lse_sum, *lse_gold;
     const long long *labels;
@@ -55,24 +57,6 @@ struct G8Params {
     int ablate;                // -DEMDR2_EXPERIMENTS builds only (EMDR2_G8_ABLATE): 1 = no epilogue, 2 = epilogue without global stores
     int nt_a;                  // A half-tiles with the non-temporal cache policy (an A panel is used by the n-tiles of ONE round of its XCD, then never again)
 };
-
-__device__ __forceinline__ void tile_coords(const G8Params &p, int pos, int &tm, int &tn)
-{
-    // n-tiles in groups of `ngroup` B panels that fit the L2; inside a group the walk is n-fastest (gemm.hip has the rationale)
-    const int full = p.ngroup * p.tiles_m;
-    // quotient by the rounded-up reciprocal ceil(2^32 / d): never too small, and too large by at most one (the excess is < pos / 2^32 < 1) --
-    // which it IS once pos * (mg * d - 2^32) reaches 2^32, e.g. from tile 59,075 on for d = 6 x 12,800 tiles (M = 3.3M rows, N = 3072: top-k
-    // 100): one compare puts it right for every pos < 2^32
-    int g = (int)__umulhi((uint32_t)pos, p.mg_full);
-    if (g * full > pos) --g;
-    const int r = pos - g * full;
-    const bool whole = (g + 1) * p.ngroup <= p.tiles_n;
-    const int gsize = whole ? p.ngroup : p.tiles_n - g * p.ngroup;
-    const uint32_t mg = whole ? p.mg_group : p.mg_last;
-    tm = mg ? (int)__umulhi((uint32_t)r, mg) : r;             // mg == 0 encodes a divisor of 1
-    if (tm * gsize > r) --tm;
-    tn = g * p.ngroup + (r - tm * gsize);
-}
 
 #define G8_BUF 65536
 #define G8_SLOT 16384
@@ -114,7 +98,7 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
     auto cursor_tile = [&](int i) {
         if (i >= my_count) i = my_count - 1;                  // past the end: harmless re-reads keep the vmcnt arithmetic fixed
         int tm, tn;
-        tile_coords(p, first + i * wg_per_xcd, tm, tn);
+        tile_order_coords(p.order, first + i * wg_per_xcd, tm, tn);
         sA = p.A + (long long)tm * 256 * lda2;
         sB = p.B + (long long)tn * 256 * ldb2;
     };
@@ -170,25 +154,14 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
         _Pragma("unroll") for (int rt = 0; rt < 4; ++rt)                                                                                  \
             _Pragma("unroll") for (int ct = 0; ct < 2; ++ct)                                                                              \
                 acc[4 * (MH) + rt][2 * (NH) + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BV[2 * c + ct], av[c][rt], c == 0 ? zero4 : acc[4 * (MH) + rt][2 * (NH) + ct], 0, 0, 0)
-#define G8_SYNC_COMPUTE(MFMAS) G8_SYNC_COMPUTE_W(asm volatile("s_waitcnt vmcnt(8)" ::: "memory"), MFMAS)
+    // (the fragment reads of a phase are plain loads: the compiler places their lgkmcnt waits itself)
+#define G8_SYNC_COMPUTE(MFMAS) PIPE_SYNC_COMPUTE(asm volatile("s_waitcnt vmcnt(8)" ::: "memory"), , MFMAS)
 // first K-tile after a tile seam: the epilogue's stores sit in the (in-order) vmcnt queue between the DMA issued before the seam and the
 // DMA issued now.  "All DMA except the newest four half-tiles has landed" is then vmcnt(8 + stores): the write-backs of the previous
 // tile drain behind the next tile's MFMAs instead of stalling its first phase.
 #define G8_SYNC_COMPUTE_SEAM(MFMAS)                                                                                                       \
-    G8_SYNC_COMPUTE_W(if (after_seam) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 + EPI_STORES) : "memory");                               \
-                      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"), MFMAS)
-#define G8_SYNC_COMPUTE_W(WAIT, MFMAS)                                                                                                    \
-    WAIT;                                                                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
-    __builtin_amdgcn_s_setprio(1);                                                                                                        \
-    MFMAS;                                                                                                                                \
-    __builtin_amdgcn_s_setprio(0);                                                                                                        \
-    __builtin_amdgcn_sched_barrier(0)
-#define G8_BARRIER()                                                                                                                      \
-    __builtin_amdgcn_s_barrier();                                                                                                         \
-    __builtin_amdgcn_sched_barrier(0)
+    PIPE_SYNC_COMPUTE(if (after_seam) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 + EPI_STORES) : "memory");                               \
+                      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"), , MFMAS)
 
     floatx4 acc[8][4];                                          // [16-row tile of the wave's 128 rows][16-column tile of its 64 columns]
     const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -204,8 +177,8 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
     // ---- prologue: the first six half-tiles of the stream, then everybody meets once; the second half then drops one barrier behind
     G8_STAGE(0, 0); G8_STAGE(1, 0); G8_STAGE(2, 0); G8_STAGE(3, 0); G8_STAGE(0, 1); G8_STAGE(1, 1);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // A0, B0 of K-tile 0 have landed (this wave's pieces)
-    G8_BARRIER();
-    if (wr == 1) { G8_BARRIER(); }
+    PIPE_BARRIER();
+    if (wr == 1) { PIPE_BARRIER(); }
 
     // stores one wave issues per tile (LSE mode: data-dependent count, no relaxation)
     constexpr int EPI_STORES = (EPI & G8_LSE) ? 0 : ((EPI & G8_PRE) ? 32 : 16);
@@ -217,54 +190,54 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(2, 1);                                                                                                               \
             G8_SYNC_COMPUTE_SEAM(MF(0, 0, b0v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_READ_B(0, 1, b1v);                                                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(3, 1);                                                                                                               \
             G8_SYNC_COMPUTE_SEAM(MF(0, 1, b1v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_READ_A(0, 1);                                                                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(0, 0);                                                                                                               \
             G8_SYNC_COMPUTE_SEAM(MF(1, 1, b1v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_STAGE(1, 0);                                                                                                               \
             G8_SYNC_COMPUTE_SEAM(MF(1, 0, b0v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_READ_B(1, 0, b0v); G8_READ_A(1, 0);                                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(2, 0);                                                                                                               \
             G8_SYNC_COMPUTE(G8_MFMA(0, 0, b0v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_READ_B(1, 1, b1v);                                                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(3, 0);                                                                                                               \
             G8_SYNC_COMPUTE(G8_MFMA(0, 1, b1v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_READ_A(1, 1);                                                                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             G8_STAGE(0, 1);                                                                                                               \
             G8_SYNC_COMPUTE(G8_MFMA(1, 1, b1v));                                                                                          \
-            G8_BARRIER();                                                                                                                 \
+            PIPE_BARRIER();                                                                                                                 \
             G8_STAGE(1, 1);                                                                                                               \
             G8_SYNC_COMPUTE(G8_MFMA(1, 0, b0v));                                                                                          \
         } while (0)
         {
             const bool after_seam = EPI_STORES > 0 && ti > 0;
             G8_KPAIR(1, G8_MFMA_Z);
-            if (2 < KT) { G8_BARRIER(); }
+            if (2 < KT) { PIPE_BARRIER(); }
         }
         for (int kt2 = 2; kt2 < KT; kt2 += 2) {
             constexpr bool after_seam = false;
             G8_KPAIR(0, G8_MFMA);
-            if (kt2 + 2 < KT) { G8_BARRIER(); }
+            if (kt2 + 2 < KT) { PIPE_BARRIER(); }
         }
         // ---- tile seam.  The leading half is past its last MFMAs one barrier interval before the trailing half: it takes the closing barrier of
         // the last phase first, the trailing half after its epilogue, so both epilogues run in the same interval (and overlap).
-        if (wr == 0) { G8_BARRIER(); }
+        if (wr == 0) { PIPE_BARRIER(); }
 
         int tm, tn;
-        tile_coords(p, first + ti * wg_per_xcd, tm, tn);
+        tile_order_coords(p.order, first + ti * wg_per_xcd, tm, tn);
         const int m_w = tm * 256 + wr * 128, n_w = tn * 256 + wc * 64;
         // lane-derived epilogue addresses are rebuilt per tile from a fresh lane id (v_mbcnt): hoisted to kernel entry they would be
         // live across the whole main loop and push its operands into scratch
@@ -329,14 +302,14 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                             if constexpr (PREG) {
                                 if (pass == 0) {
 #pragma unroll
-                                    for (int r = 0; r < 4; ++r) act[4 * h + nt][r] = gelu_erf_with_grad(fmaf(a4[r], p.alpha, bcol[nt][r]), v[r]);
+                                    for (int r = 0; r < 4; ++r) act[4 * h + nt][r] = gelu_erf_with_grad(epi_affine(a4[r], p.alpha, bcol[nt][r]), v[r]);
                                 } else {
 #pragma unroll
                                     for (int r = 0; r < 4; ++r) v[r] = act[4 * h + nt][r];
                                 }
                             } else {
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) v[r] = fmaf(a4[r], p.alpha, bcol[nt][r]);
+                                for (int r = 0; r < 4; ++r) v[r] = epi_affine(a4[r], p.alpha, bcol[nt][r]);
                             }
                             if (final_pass && !PREG) {
                                 if constexpr ((EPI & G8_GELU) != 0) {
@@ -373,12 +346,9 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                             const uint32_t rw[4] = {rr[mi % RAHEAD][ps].x, rr[mi % RAHEAD][ps].y, rr[mi % RAHEAD][ps].z, rr[mi % RAHEAD][ps].w};
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                float x0 = bf16_to_f32((uint16_t)(w[q] & 0xffff)), x1 = bf16_to_f32((uint16_t)(w[q] >> 16));
-                                const float r0 = bf16_to_f32((uint16_t)(rw[q] & 0xffff)), r1 = bf16_to_f32((uint16_t)(rw[q] >> 16));
-                                if constexpr ((EPI & G8_RADD) != 0) { x0 += r0; x1 += r1; }
-                                else if constexpr ((EPI & G8_RMUL) != 0) { x0 *= r0; x1 *= r1; }
-                                else { x0 *= gelu_erf_grad(r0); x1 *= gelu_erf_grad(r1); }
-                                w[q] = pack2_bf16(x0, x1);
+                                const floatx2_t x = {bf_lo(w[q]), bf_hi(w[q])};     // (the staging buffer holds the stored bf16 already)
+                                const floatx2_t y = epi_residual_pair(x, rw[q], (EPI & G8_RADD) ? 0 : (EPI & G8_RMUL) ? 2 : 1);
+                                w[q] = pack2_bf16(y[0], y[1]);
                             }
                         }
                         EXP_G8_STORE_IF(p, w)
@@ -394,7 +364,7 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
             // ---- LSE mode: logits = alpha * acc + bias stay in registers.  Per C row (four lanes e15 + 16 eq hold its 64 columns of this
             // wave): max, sum exp(x - max), and the gold logit if the row's label falls into these columns.  The four waves of a row block
             // (wc = 0..3) write separate partials: slot index tn * 4 + wc of a [M, tiles_n * 4] table.
-            const int nslots = p.tiles_n * 4;
+            const int nslots = p.order.tiles_n * 4;
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) {                      // 16-row accumulator tiles; four lanes (eq = 0..3) share a C row
                 const int m_l = m_w + mt * 16 + e15;
@@ -408,7 +378,7 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                     for (int r = 0; r < 4; ++r) {
                         const int n = n_w + nt * 16 + 4 * eq + r;
                         // the logits the unfused path would have stored are bf16: round the same way so both paths agree to the bit
-                        const float t = bf16_to_f32(f32_to_bf16(acc[mt][nt][r] * p.alpha + (HAS_BIAS ? p.bias[n] : 0.f)));
+                        const float t = round_to_stored_bf16(epi_affine(acc[mt][nt][r], p.alpha, HAS_BIAS ? p.bias[n] : 0.f));
                         x[nt][r] = t;
                         mx = fmaxf(mx, t);
                         if ((long long)n == lab) { gold = t; has = true; }
@@ -429,62 +399,32 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                 if (has) p.lse_gold[m_l] = gold;
             }
         }
-        if (wr == 1) { G8_BARRIER(); }
+        if (wr == 1) { PIPE_BARRIER(); }
     }
-    if (wr == 0) { G8_BARRIER(); }                              // the leading half pays back the barrier the trailing half took at the start
+    if (wr == 0) { PIPE_BARRIER(); }                              // the leading half pays back the barrier the trailing half took at the start
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // speculative half-tiles past the end of the stream
-}
-
-int g8_cu_count()
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount;
-    }
-    return cus;
-}
-
-int grid_for(const G8Params &p)
-{
-    int grid = g8_cu_count() & ~7;
-    if (grid < 8) grid = 8;
-    if (grid > ((p.total + 7) & ~7)) grid = (p.total + 7) & ~7;
-    return grid;
 }
 
 template <int EPI>
 int g8_launch(G8Params &p, hipStream_t stream)
 {
     constexpr int LDS = G8_STAGING + 8 * 4096;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)gemm8_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
-    p.tiles_m = p.M / 256; p.tiles_n = p.N / 256;
-    p.total = p.tiles_m * p.tiles_n;
-    p.per = (p.total + 7) >> 3;
-    // B panels of 256 x K bf16 that fit about half of a 4 MB L2 (the rest holds the A panels in flight and the output lines in transit)
-    const long long panel = 256ll * p.K * 2;
-    int ng = (int)(2560ll * 1024 / panel);
-    if (ng < 1) ng = 1;
-    long long single_kb = 4096;                               // a B matrix up to this size is walked as ONE group (plain n-fastest)
+    if (lds_opt_in<gemm8_kernel<EPI>>(LDS) != LDS_OPT_IN_OK) return -3;
+    const int tiles_m = p.M / 256, tiles_n = p.N / 256;
+    p.total = tiles_m * tiles_n;
+    p.per = xcd_per(p.total);
+    long long single_kb = 4096;
+    int force_ng = 0;
     EXP_G8_HOST_L2(single_kb)
-    if (ng > p.tiles_n || 2 * ng < p.tiles_n || (long long)p.N * p.K * 2 <= (single_kb << 10)) ng = p.tiles_n;
-    EXP_G8_HOST_GROUPS(p, ng)
-    const int groups = (p.tiles_n + ng - 1) / ng;
-    p.ngroup = (p.tiles_n + groups - 1) / groups;
-    auto magic = [](long long d) { return (uint32_t)(((1ull << 32) + (unsigned long long)d - 1) / (unsigned long long)d); };
-    const int last = p.tiles_n - (groups - 1) * p.ngroup;
-    if ((long long)p.total >= (1ll << 24)) return -4;
-    p.mg_full = magic((long long)p.ngroup * p.tiles_m); p.mg_group = p.ngroup > 1 ? magic(p.ngroup) : 0; p.mg_last = last > 1 ? magic(last) : 0;
+    EXP_G8_HOST_GROUPS(p, force_ng)
+    if ((long long)p.total >= (1ll << 24)) return -4;          // (the reciprocals of the tile order are stated below that)
+    p.order = tile_order_plan(tiles_m, tiles_n, 256, p.K, p.N, 2560, single_kb, force_ng);
     // one K-tile takes ~3,200 shader cycles at the sustained rate; 1/8 of that per XCD index, in 1,024-cycle naps: 3200 / 8 / 1024 * 64 = 25
-    p.stagger = p.total >= 4 * grid_for(p) ? 25 : 0;             // only when every workgroup has several tiles to amortise the late start
+    int grid = device_cu_count() & ~7;                         // one workgroup per CU, a multiple of 8, no wider than the XCD ranges
+    if (grid < 8) grid = 8;
+    if (grid > 8 * p.per) grid = 8 * p.per;
+    p.stagger = p.total >= 4 * grid ? 25 : 0;                  // only when every workgroup has several tiles to amortise the late start
     EXP_G8_HOST_LAUNCH(p)
-    const int grid = grid_for(p);
     hipLaunchKernelGGL((gemm8_kernel<EPI>), dim3(grid), dim3(512), LDS, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

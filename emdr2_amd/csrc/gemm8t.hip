@@ -10,8 +10,8 @@
 // one half-tile of LDS-DMA and a counted vmcnt, the two wave halves one barrier apart.
 // What differs:
 //  * the operands arrive with the REDUCTION index slow.  A half-tile is [64 r][128 columns]: full 256-byte rows straight from the activation
-//    matrices (one DMA instruction = 4 rows), and the fragments are gathered with ds_read_b64_tr_b16 (two per 8-element k-run, layout as in
-//    gemm_tn.hip / tools/tr_probe.hip).  16-byte granules are XOR-swizzled with (r & 3) << 2 on the source side: the four rows a 32-lane
+//    matrices (one DMA instruction = 4 rows), and the fragments are gathered with ds_read_b64_tr_b16 (two per 8-element k-run, layout pinned
+//    by tools/tr_probe.hip).  16-byte granules are XOR-swizzled with (r & 3) << 2 on the source side: the four rows a 32-lane
 //    service group touches land on 4 x 64 B = distinct banks.
 //  * a wave's 128 i-columns are two separate blocks of 64 (block h in half-tile A_h), its 64 j-columns two blocks of 32, so that every half-
 //    tile is one contiguous 128-column span of the operand.
@@ -24,13 +24,13 @@
 //    against ones: four VALU ops per fragment).
 #include "../../include/emdr2_ops.h"
 #include "gemm_common.h"
+#include "device_attr.h"
 #include "exp_hooks.h"
 #include "ops_timing.h"
 #include <stdlib.h>
 
 typedef short short4_t __attribute__((ext_vector_type(4)));
 typedef short short8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) short4_t lds_s4_t;
 
 namespace {
@@ -57,12 +57,9 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
     const int wr = wave >> 2, wc = wave & 3;                 // wave grid 2 (i) x 4 (j); wr is also the half that runs one barrier behind
     const int t = lane & 15, lq = lane >> 4;                  // v_mfma_f32_16x16x32_bf16: fragment column t, k = 8 lq .. 8 lq + 7 of a 32-row k-step
 
-    // ---- this workgroup's item: XCD x = id & 7 owns items [x * per_xcd, (x + 1) * per_xcd), tile index fastest inside a slice
-    const int per_xcd = (p.items + 7) >> 3;
-    const int item = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-    if (item >= p.items) return;
-    const int zs = item / p.tiles, tile = item - zs * p.tiles;
-    const int tj = tile / p.tiles_i, ti = tile - tj * p.tiles_i;
+    int item, zs, ti, tj;
+    if (!xcd_item(p.items, item)) return;
+    tn_item_coords(item, p.tiles, p.tiles_i, zs, ti, tj);
     const int i0 = ti * 256, j0 = tj * 256;
     // the slices are INTERLEAVED K-tile by K-tile: at any moment all workgroups read one window of `slices` consecutive K-tiles (a few MB that
     // slides down the operands) instead of `slices` streams a hundred MB apart
@@ -132,16 +129,15 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
     int rd_off = 0;                                           // ring offset of the current K-tile's A0; B0, B1, A1 follow (with wrap-around)
     auto ring = [](int off) { return off >= T8_RING ? off - T8_RING : off; };
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-#define T8_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define T8_READ_A(SLOT)                                                                                                                   \
     _Pragma("unroll") for (int rt = 0; rt < 4; ++rt) {                                                                                    \
         const uint32_t base_ = lds0 + (uint32_t)ring(rd_off + (SLOT) * T8_SLOT) + a_rd[rt];                                               \
-        T8_TR(al[0][rt], base_, 0); T8_TR(ah[0][rt], base_, 1024); T8_TR(al[1][rt], base_, 8192); T8_TR(ah[1][rt], base_, 9216);          \
+        TR_READ(al[0][rt], base_, 0); TR_READ(ah[0][rt], base_, 1024); TR_READ(al[1][rt], base_, 8192); TR_READ(ah[1][rt], base_, 9216);          \
     }
 #define T8_READ_B(SLOT, L, H)                                                                                                             \
     _Pragma("unroll") for (int ct = 0; ct < 2; ++ct) {                                                                                    \
         const uint32_t base_ = lds0 + (uint32_t)ring(rd_off + (SLOT) * T8_SLOT) + b_rd[ct];                                               \
-        T8_TR(L[ct], base_, 0); T8_TR(H[ct], base_, 1024); T8_TR(L[2 + ct], base_, 8192); T8_TR(H[2 + ct], base_, 9216);                  \
+        TR_READ(L[ct], base_, 0); TR_READ(H[ct], base_, 1024); TR_READ(L[2 + ct], base_, 8192); TR_READ(H[2 + ct], base_, 9216);                  \
     }
 #define T8_WAIT_A()                                                                                                                       \
     asm volatile("s_waitcnt lgkmcnt(0)"                                                                                                   \
@@ -150,27 +146,13 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
                  :: "memory")
 #define T8_WAIT_B(L, H)                                                                                                                   \
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(L[0]), "+v"(H[0]), "+v"(L[1]), "+v"(H[1]), "+v"(L[2]), "+v"(H[2]), "+v"(L[3]), "+v"(H[3])::"memory")
-#define T8_FR(L, H) __builtin_bit_cast(bf16x8, make_uint4((L).x, (L).y, (H).x, (H).y))
     // rows of the MFMA result = i (A fragment first), columns = j: a lane holds one j and 4 i, 16 lanes write 64 contiguous bytes of C
 #define T8_MFMA(MH, NH, BL, BH)                                                                                                           \
     _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                                                         \
         _Pragma("unroll") for (int rt = 0; rt < 4; ++rt)                                                                                  \
             _Pragma("unroll") for (int ct = 0; ct < 2; ++ct)                                                                              \
-                acc[4 * (MH) + rt][2 * (NH) + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(T8_FR(al[c][rt], ah[c][rt]), T8_FR(BL[2 * c + ct], BH[2 * c + ct]), acc[4 * (MH) + rt][2 * (NH) + ct], 0, 0, 0)
-#define T8_SYNC_COMPUTE(WAIT, MFMAS)                                                                                                      \
-    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");                                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
-    WAIT;                                                                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
-    __builtin_amdgcn_s_setprio(1);                                                                                                        \
-    MFMAS;                                                                                                                                \
-    __builtin_amdgcn_s_setprio(0);                                                                                                        \
-    __builtin_amdgcn_sched_barrier(0)
-#define T8_BARRIER()                                                                                                                      \
-    __builtin_amdgcn_s_barrier();                                                                                                         \
-    __builtin_amdgcn_sched_barrier(0)
+                acc[4 * (MH) + rt][2 * (NH) + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(TR_FRAG(al[c][rt], ah[c][rt]), TR_FRAG(BL[2 * c + ct], BH[2 * c + ct]), acc[4 * (MH) + rt][2 * (NH) + ct], 0, 0, 0)
+#define T8_SYNC_COMPUTE(WAIT, MFMAS) PIPE_SYNC_COMPUTE(asm volatile("s_waitcnt vmcnt(12)" ::: "memory"), WAIT, MFMAS)
 
     floatx4 acc[8][4];                                         // [16-column tile of the wave's 128 i][16-column tile of its 64 j]
 #pragma unroll
@@ -208,8 +190,8 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
     // ---- prologue: the first eight half-tiles of the stream, then everybody meets once; the second half then drops one barrier behind
     T8_STAGE(0); T8_STAGE(1); T8_STAGE(2); T8_STAGE(3); T8_STAGE(0); T8_STAGE(1); T8_STAGE(2); T8_STAGE(3);
     asm volatile("s_waitcnt vmcnt(12)" ::: "memory");         // A0, B0 of K-tile 0 have landed (this wave's pieces)
-    T8_BARRIER();
-    if (wr == 1) { T8_BARRIER(); }
+    PIPE_BARRIER();
+    if (wr == 1) { PIPE_BARRIER(); }
 
     for (int kt = 0; kt < KT; ++kt) {
         T8_READ_B(1, b0l, b0h); T8_READ_A(0);
@@ -217,25 +199,25 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
         T8_STAGE(0);
         T8_SYNC_COMPUTE(T8_WAIT_B(b0l, b0h); T8_WAIT_A(), T8_MFMA(0, 0, b0l, b0h));
         T8_COLSUM(0);
-        T8_BARRIER();
+        PIPE_BARRIER();
         T8_READ_B(2, b1l, b1h);
         __builtin_amdgcn_sched_barrier(0);
         T8_STAGE(1);
         T8_SYNC_COMPUTE(T8_WAIT_B(b1l, b1h), T8_MFMA(0, 1, b1l, b1h));
-        T8_BARRIER();
+        PIPE_BARRIER();
         T8_READ_A(3);
         __builtin_amdgcn_sched_barrier(0);
         T8_STAGE(2);
         T8_SYNC_COMPUTE(T8_WAIT_A(), T8_MFMA(1, 1, b1l, b1h));
         T8_COLSUM(1);
         cs_phase = cs_phase == 0 ? tiles_j - 1 : cs_phase - 1;
-        T8_BARRIER();
+        PIPE_BARRIER();
         T8_STAGE(3);
         T8_SYNC_COMPUTE(, T8_MFMA(1, 0, b0l, b0h));
         rd_off = ring(rd_off + 4 * T8_SLOT);
-        if (kt + 1 < KT) { T8_BARRIER(); }
+        if (kt + 1 < KT) { PIPE_BARRIER(); }
     }
-    if (wr == 0) { T8_BARRIER(); }                            // the leading half pays back the barrier the trailing half took at the start
+    if (wr == 0) { PIPE_BARRIER(); }                            // the leading half pays back the barrier the trailing half took at the start
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // speculative half-tiles past the end of the stream
 
     // ---- epilogue.  acc[4 mh + rt][2 nh + ct]: rows i = i0 + 128 mh + 64 wr + 16 rt + 4 lq + r, column j = j0 + 128 nh + 32 wc + 16 ct + t
@@ -288,13 +270,7 @@ int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, flo
     p.ablate = 0;
     EXP_T8_HOST(p)
     p.atomic = split_k > 1;                                   // the caller zeroed C exactly when it asked for more than one slice
-    constexpr int LDS = T8_RING;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)gemm8t_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
-    const unsigned grid = (unsigned)(((p.items + 7) / 8) * 8);
-    hipLaunchKernelGGL(gemm8t_kernel, dim3(grid), dim3(512), LDS, stream, p);
+    if (lds_opt_in<gemm8t_kernel>(T8_RING) != LDS_OPT_IN_OK) return -3;
+    hipLaunchKernelGGL(gemm8t_kernel, dim3(8 * xcd_per(p.items)), dim3(512), T8_RING, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

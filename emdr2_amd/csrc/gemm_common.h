@@ -1,5 +1,6 @@
-// emdr2_amd/csrc/gemm_common.h -- scalar helpers shared by the bf16 GEMM kernels (gemm.hip, gemm8.hip): bf16 packing, the erf-form GELU of the
-// reference (transformer.py:80,103-104: F.gelu, not the tanh fusion) and its derivative, streaming stores.
+// emdr2_amd/csrc/gemm_common.h -- what the bf16 GEMM kernels (gemm.hip, gemm8.hip, gemm_tn.hip, gemm8t.hip) share: bf16 packing, the erf-form
+// GELU of the reference (transformer.py:80,103-104: F.gelu, not the tanh fusion) and its derivative, streaming stores, the element recipe of
+// the NT epilogues, the XCD-contiguous item mapping, and the barrier / transposed-read macros of the 256 x 256 pipelines.
 #ifndef EMDR2_GEMM_COMMON_H
 #define EMDR2_GEMM_COMMON_H
 #include <hip/hip_runtime.h>
@@ -15,6 +16,8 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float floatx2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }            // the two bf16 of a packed pair
+__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 __device__ __forceinline__ uint16_t f32_to_bf16(float f)
 {
@@ -73,4 +76,60 @@ __device__ __forceinline__ float gelu_erf_grad(float x)
     const float hp = gelu_half_poly_exp(x, e);
     return fmaf(e, fmaf(x, 0.3989422804014327f, -copysignf(hp, x)), gelu_step(x));
 }
+
+// ---- the element recipe of the NT epilogues (order of roundings): what gemm.hip's vector and scalar epilogues and gemm8.hip
+// share beside gelu_erf / gelu_erf_with_grad above; each keeps its own staging, dropout form and branches on the output mode.
+__device__ __forceinline__ float epi_affine(float acc, float alpha, float bias) { return fmaf(acc, alpha, bias); }
+// the value meets the residual as the bf16 the reference's F.linear would have stored: one rounding before the combine, one after
+__device__ __forceinline__ float round_to_stored_bf16(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+// one packed bf16 pair of the residual.  rmode 0: + r;  1: * gelu'(r) -- r is the saved GELU pre-activation (backward of the FFN's first
+// linear, fused);  2: * r.  A run-time rmode costs a uniform branch per pair (and keeps the pair in packed math), a constant folds.
+__device__ __forceinline__ floatx2_t epi_residual_pair(floatx2_t x, uint32_t rw, int rmode)
+{
+    const floatx2_t r = {bf_lo(rw), bf_hi(rw)};
+    if (rmode == 0) return x + r;
+    if (rmode == 2) return x * r;
+    const floatx2_t g = {gelu_erf_grad(r[0]), gelu_erf_grad(r[1])};
+    return x * g;
+}
+
+// ---- XCD-contiguous item mapping.  Workgroup ids go round-robin to the 8 XCDs (one L2 each); XCD x = id & 7 owns the items
+// [x * per, (x + 1) * per) of a sequence, so that consecutive items -- which share operand panels -- run on one L2.  Grids are 8 * per wide.
+__host__ __device__ __forceinline__ int xcd_per(int total) { return (total + 7) >> 3; }
+// this workgroup's item of a one-item-per-workgroup launch; false: none (ragged tail of the last XCD ranges)
+__device__ __forceinline__ bool xcd_item(int total, int &item)
+{
+    item = ((int)blockIdx.x & 7) * xcd_per(total) + ((int)blockIdx.x >> 3);
+    return item < total;
+}
+// TN kernels: item -> (reduction slice, tile) with the tile index fastest, so the `tiles` workgroups that stream the SAME token rows of dy and x
+// run together on one L2 and both operands leave HBM once per slice; tiles are i-fastest
+__device__ __forceinline__ void tn_item_coords(int item, int tiles, int tiles_i, int &zs, int &ti, int &tj)
+{
+    zs = item / tiles;
+    const int tile = item - zs * tiles;
+    tj = tile / tiles_i; ti = tile - tj * tiles_i;
+}
+
+// ---- ds_read_b64_tr_b16 as inline asm (the builtin makes the wait-count pass put vmcnt(0) in front of every read: gemm8t.hip), and the bf16x8
+// MFMA operand of two such 8-byte halves
+#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+#define TR_FRAG(L, H) __builtin_bit_cast(bf16x8, make_uint4((L).x, (L).y, (H).x, (H).y))
+
+// ---- phase boundary of the 256 x 256 pipelines (gemm8.hip, gemm8t.hip): wait for this phase's DMA, meet, wait for its LDS reads, MFMAs at
+// raised priority; the scheduling barriers keep the compiler from moving anything across
+#define PIPE_BARRIER()                                                                                                                    \
+    __builtin_amdgcn_s_barrier();                                                                                                         \
+    __builtin_amdgcn_sched_barrier(0)
+#define PIPE_SYNC_COMPUTE(VM_WAIT, LDS_WAIT, MFMAS)                                                                                       \
+    VM_WAIT;                                                                                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
+    __builtin_amdgcn_s_barrier();                                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
+    LDS_WAIT;                                                                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                                                    \
+    __builtin_amdgcn_s_setprio(1);                                                                                                        \
+    MFMAS;                                                                                                                                \
+    __builtin_amdgcn_s_setprio(0);                                                                                                        \
+    __builtin_amdgcn_sched_barrier(0)
 #endif

@@ -13,16 +13,11 @@
 // Optional fused bias gradient: colsum[i] += sum_r A[r, i] (the fp32 column sums of dy), taken from the A fragments already in
 // registers by the workgroups of the first j-tile.  split_k > 1: reduction slices accumulate with fp32 atomics into a pre-zeroed C.
 #include "../../include/emdr2_ops.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
+#include "gemm_common.h"
+#include "device_attr.h"
 #include "ops_timing.h"
 #include "exp_hooks.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
                      float *colsum_a, hipStream_t stream);       // gemm8t.hip
@@ -41,11 +36,6 @@ struct TnParams {
 #define TN_OPER 16384                       // one operand stage: 32 reduction rows x 256 columns x 2 B
 #define TN_STAGE (2 * TN_OPER)
 
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
 __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -54,15 +44,10 @@ __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
     const int t = lane & 15, colgrp = (lane >> 4) & 1;
-    // 1-D grid, XCD-aware: workgroup ids go round-robin to the 8 XCDs (one L2 each); every XCD gets a contiguous range of
-    // (reduction slice, tile) pairs with the tile index fastest, so the tiles_i * tiles_j workgroups that stream the SAME token rows of
-    // dy and x run together on one L2 and both operands leave HBM once per slice.
-    const int tiles = p.tiles_i * p.tiles_j, total = tiles * p.splitk;
-    const int per_xcd = (total + 7) >> 3;
-    const int t_id = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-    if (t_id >= total) return;
-    const int zs = t_id / tiles, tile = t_id - zs * tiles;
-    const int tj = tile / p.tiles_i, ti = tile - tj * p.tiles_i;
+    const int tiles = p.tiles_i * p.tiles_j;
+    int item, zs, ti, tj;
+    if (!xcd_item(tiles * p.splitk, item)) return;
+    tn_item_coords(item, tiles, p.tiles_i, zs, ti, tj);
     const int i0 = ti * 256, j0 = tj * 256;
 
     // fragment addresses: lane -> row (t >> 2) of its group's [4][16] block, column segment (t & 3) * 4
@@ -153,9 +138,9 @@ __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
                          : "memory");
             bf16x8 a[2], b[4];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = __builtin_bit_cast(bf16x8, make_uint4(al[mi].x, al[mi].y, ah[mi].x, ah[mi].y));
+            for (int mi = 0; mi < 2; ++mi) a[mi] = TR_FRAG(al[mi], ah[mi]);
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) b[ni] = __builtin_bit_cast(bf16x8, make_uint4(bl[ni].x, bl[ni].y, bh[ni].x, bh[ni].y));
+            for (int ni = 0; ni < 4; ++ni) b[ni] = TR_FRAG(bl[ni], bh[ni]);
             if (want_colsum) {
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
@@ -217,13 +202,8 @@ extern "C" int emdr2_gemm_tn_bf16(const void *A, int64_t lda, const void *B, int
     p.A = (const char *)A; p.B = (const char *)B; p.C = C; p.colsum = colsum_a;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.I = I; p.J = J; p.R = R; p.splitk = split_k;
     constexpr int LDS = TN_STAGES * TN_STAGE;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
+    if (lds_opt_in<gemm_tn_kernel>(LDS) != LDS_OPT_IN_OK) return -3;
     p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256;
-    dim3 grid((unsigned)(((p.tiles_i * p.tiles_j * split_k + 7) / 8) * 8));
-    hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(512), LDS, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(gemm_tn_kernel, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * split_k)), dim3(512), LDS, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

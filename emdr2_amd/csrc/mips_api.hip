@@ -15,18 +15,6 @@ struct Timing {
     int64_t rows[TIMING_SLOTS] = {};
 } g_timing;
 
-int cu_count()
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Tuning / ablation switches are read from the environment ONLY in -DEMDR2_EXPERIMENTS builds (`make exp`, used by tools/); the production
@@ -40,7 +28,7 @@ bool search_knobs(SearchKnobs *kn, bool product = false)
     kn->growth_i8 = KNOB("EMDR2_MIPS_GROWTH_I8", 2);
     kn->margin_i8 = (float)KNOB("EMDR2_MIPS_MARGIN_PCT", 25) * 0.01f;
     kn->force_variant = KNOB("EMDR2_MIPS_VARIANT", -1);
-    kn->cus = KNOB("EMDR2_MIPS_GRID", cu_count());
+    kn->cus = KNOB("EMDR2_MIPS_GRID", device_cu_count());
     kn->scan_kernel = KNOB("EMDR2_MIPS_KERNEL", 1);          // 1 = lockstep v1, 2 = ping-pong
     kn->ablate = KNOB("EMDR2_MIPS_ABLATE", 0);
     kn->tune = KNOB("EMDR2_MIPS_TUNE", 17);
@@ -116,7 +104,7 @@ extern "C" {
 
 int emdr2_abi_version(void) { return EMDR2_ABI_VERSION; }
 
-int emdr2_device_cu_count(void) { return cu_count(); }
+int emdr2_device_cu_count(void) { return device_cu_count(); }
 
 int emdr2_mips_set_timing(int enabled)
 {
@@ -723,7 +711,7 @@ int emdr2_mips_debug_scores(const void *tiled, int64_t n_rows, int dim, const vo
     sp.trace = nullptr;
     sp.tile_begin = 0;
     sp.tile_end = (int)((n_rows + BM - 1) / BM);
-    const int cus = cu_count();
+    const int cus = device_cu_count();
     return mips_launch_scan(variant, 2, sp, sp.tile_end < cus ? sp.tile_end : cus, stream);
 }
 

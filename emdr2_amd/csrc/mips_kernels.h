@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "mips_device.h"
 #include "mips_plan.h"
+#include "device_attr.h"
 
 #define CAPQ 16384u /* candidate slots per query (8 B each) */
 #define SUBCAP 1024u /* ... plus 8 sub-lists of this many per query, one per XCD, filled by the persistent scan (mips_scan8.hip) */

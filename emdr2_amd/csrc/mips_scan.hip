@@ -391,11 +391,7 @@ static int launch_scan_t(const ScanParams &p, int grid, hipStream_t stream)
 {
     constexpr int STAGE = (WM * 64 + WN * 128) * 64;
     constexpr int LDS = NST * STAGE + QCAP * 16 + 16;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)mips_scan_kernel<WM, WN, MODE, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
+    if (lds_opt_in<mips_scan_kernel<WM, WN, MODE, ABL>>(LDS) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL((mips_scan_kernel<WM, WN, MODE, ABL>), dim3(grid), dim3(512), LDS, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

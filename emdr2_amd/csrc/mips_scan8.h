@@ -373,11 +373,7 @@ int s8_launch(typename OPS::Params &P, int bn, int64_t row_begin, int64_t row_en
     P.per = ((P.total + 7) >> 3);
     P.per = (P.per + 1) & ~1;                                 // both halves of a tile on the same XCD
     constexpr int LDS = 2 * S8_BUF + S8_QCAP * 16 + 128;
-    static bool attr_done = false;                            // (one per instance)
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)mips_scan8_kernel<OPS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
+    if (lds_opt_in<mips_scan8_kernel<OPS>>(LDS) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL(mips_scan8_kernel<OPS>, dim3(grid), dim3(512), LDS, stream, P);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -468,6 +468,26 @@ def test_tn_kernels_in_the_poison_layout(R, split):
                     assert not bool(cs.any())
 
 
+def test_second_device_gets_its_own_lds_opt_in():
+    """The dynamic-LDS opt-in of a kernel belongs to (function, device) (csrc/device_attr.h).  One process, the last device first and device 0
+    after it: a flag kept per process would launch the 160 KiB kernels on device 0 without the opt-in.  gemm8 (4096, 256, 128) with a bias and
+    gemm8t (R 128, I = J = 264, one slice), through emdr2_gemm_nt_bf16 / emdr2_gemm_tn_bf16."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    for dev in (torch.cuda.device_count() - 1, 0):
+        with torch.cuda.device(dev):
+            for fam in ("randn", "row_scaled"):
+                _run_recipe("g8_dev%d" % dev, fam, 4096, 256, 128, "bias")
+                A, B = G.tn_inputs(fam, 128, 264, 264, 3, DEV)
+                C = torch.full((264, 264), G.SENTINEL, dtype=torch.float32, device=DEV)
+                _tn(A.to(BF16), B.to(BF16), C, 1, None)
+                torch.cuda.synchronize()
+                r = G.tn_reference(A, B)
+                ratio, idx = G.worst(C, r.dW, G.tn_bounds(r, 1)["dW"])
+                _note("gemm8t_dev%d" % dev, fam, "dW", ratio)
+                assert ratio <= 1.0, (dev, fam, ratio, idx)
+
+
 @pytest.mark.parametrize("R", [8256, 8224])
 def test_weight_grad_tn_splits_the_reduction(R):
     """kernels.weight_grad_tn: tiles = 2 * 1, split = min(256, R // 4096) = 2.  R = 8256 = 129 * 64 -> gemm8t, R = 8224 (% 64 == 32) -> gemm_tn."""

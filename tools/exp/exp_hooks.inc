@@ -24,11 +24,11 @@ static inline bool exp_gemm_use_gemm8() { static const int v = getenv("EMDR2_GEM
 // ---- gemm8.hip: EMDR2_G8_ABLATE 1 = no epilogue, 2 = epilogue without global stores; _SINGLE_KB / _NGROUP / _NT / _STAGGER ---------------
 #define EXP_G8_AFTER_KLOOP(p, acc, wr) if ((p).ablate == 1) { \
     _Pragma("unroll") for (int mi = 0; mi < 8; ++mi) _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) asm volatile("" ::"v"(acc[mi][ni])); \
-    if (wr == 1) { G8_BARRIER(); } continue; }
+    if (wr == 1) { PIPE_BARRIER(); } continue; }
 #define EXP_G8_STORE_IF(p, w) if ((p).ablate != 2 || (w)[0] == 0x12345678u)
 #define EXP_G8_HOST_L2(single_kb) { static const int single_env = getenv("EMDR2_G8_SINGLE_KB") ? atoi(getenv("EMDR2_G8_SINGLE_KB")) : 0; if (single_env > 0) single_kb = single_env; }
 #define EXP_G8_HOST_GROUPS(p, ng) { static const int ng_env = getenv("EMDR2_G8_NGROUP") ? atoi(getenv("EMDR2_G8_NGROUP")) : 0; \
-    if (ng_env > 0) ng = ng_env < (p).tiles_n ? ng_env : (p).tiles_n; \
+    if (ng_env > 0) ng = ng_env; \
     static const int nt_env = getenv("EMDR2_G8_NT") ? atoi(getenv("EMDR2_G8_NT")) : 0; (p).nt_a = nt_env; }
 #define EXP_G8_HOST_LAUNCH(p) { static const int ablate_env = getenv("EMDR2_G8_ABLATE") ? atoi(getenv("EMDR2_G8_ABLATE")) : 0; \
     static const int stagger_env = getenv("EMDR2_G8_STAGGER") ? atoi(getenv("EMDR2_G8_STAGGER")) : -1; \

@@ -160,11 +160,7 @@ static int launch_scan_pp_t(const ScanParams &p, int grid, hipStream_t stream)
     constexpr int STAGE = (WM * 64 + WN * 128) * 64;
     constexpr int LDS = NS * STAGE + (NS == 3 ? QCAP * 16 + 16 : 0);
     static_assert(LDS <= 163840, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void *)mips_scan_pp_kernel<WM, WN, NS, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -3;
-        attr_done = true;
-    }
+    if (lds_opt_in<mips_scan_pp_kernel<WM, WN, NS, ABL>>(LDS) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL((mips_scan_pp_kernel<WM, WN, NS, ABL>), dim3(grid), dim3(512), LDS, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
