@@ -1,4 +1,4 @@
-"""ctypes binding of libemdr2_hip.so (C ABI: include/emdr2_mips.h, include/emdr2_assembly.h).
+"""ctypes binding of libemdr2_hip.so (C ABI: include/emdr2_mips.h, include/emdr2_assembly.h, include/emdr2_answers.h).
 
 The library is built in-tree by `__graft_entry__.build()` / `make -C emdr2_amd/csrc`.  If it is
 missing this module raises at first use -- the product path never falls back to a CPU or eager
@@ -79,6 +79,8 @@ SIGNATURES = {
 
 SIGNATURES["emdr2_assemble_evidence"] = (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32,
                                                   _vp, _vp, _vp, _vp, _vp, _vp])
+# include/emdr2_answers.h: arena, doc_ids, n_b, k, ans_tokens, ans_off, q_ans_off, cont_bits, hit_pos, hit_ans, best_slot, slot_hist, stream
+SIGNATURES["emdr2_answer_hits"] = (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 
 
 _f32 = ctypes.c_float

@@ -191,6 +191,15 @@ def get_parser():
     g.add_argument('--indexer-batch-size', type=int, default=128)
     g.add_argument('--indexer-log-interval', type=int, default=1000)
     g.add_argument('--report-topk-accuracies', nargs='+', type=int, default=[])
+    g.add_argument('--retrieval-answer-hits', action='store_true',
+                   help='(not in the reference, which measures this in a separate evaluator over the evidence text: '
+                        'tasks/openqa/dense_retriever/evaluation) report how often, and at which rank, the passages the reader is shown hold a '
+                        'reference answer, matched on the device against the token ids of the evidence arena (include/emdr2_answers.h: one '
+                        'launch pair per training step and per evaluation batch).  Training: every --log-interval line gains '
+                        '"answer hits@k" for the questions since the last line (data-parallel ranks summed) and "hit mass", the retriever\'s '
+                        'probability mass on answer-bearing passages.  Evaluation: "Answer Hits@k" beside the exact match score.  k: '
+                        '--report-topk-accuracies cut to --topk-retrievals (1 5 20 and --topk-retrievals when none are given).  Off: no '
+                        'launch, no output changes')
     return p
 
 

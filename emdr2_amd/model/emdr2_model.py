@@ -168,6 +168,8 @@ class PreComputedEvidenceDocsRetriever(object):
         distance, topkindex = self._search(query_tensor)
         out = self.arena.assemble(topkindex, self.args.topk_retrievals, query_uid, query_ids_t5, query_ids_t5_len,
                                   self.args.seq_length_ret, self.args.seq_length, cls_id, sep_id, pad_id)
+        # (--retrieval-answer-hits) the evidence the reader really sees, after the uid skip
+        self.last_kept_ids = out[4] if getattr(self, "track_kept_ids", False) else None
         self.last_kept_rows = self._last_kept_slots = None
         if getattr(self, "track_rows", False) and self.last_search_rows is not None:
             self._last_kept_slots = kept_slots(out[4], topkindex)
@@ -294,6 +296,9 @@ class EMDR2Model(torch.nn.Module):
         # `take_writeback` at the step boundary.  Off: nothing is kept and the retriever does not track rows.
         self.index_writeback = False
         self._writeback_rows, self._writeback_embeds = None, []
+        # --retrieval-answer-hits: an AnswerHitTracker (tasks/openqa/e2eqa/answer_hits.py); the forward step arms it, a step's retrieval is
+        # matched once, each question group adds its prior's mass on the hit slots.  None: no launch
+        self.answer_hits = None
 
     def retriever_embedder(self, tokens, mask, types, embedder_type, disable_dropout=False):
         tower = self.retriever_model.query_model if embedder_type == "query" else self.retriever_model.context_model
@@ -318,8 +323,13 @@ class EMDR2Model(torch.nn.Module):
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
             ctx_embeds = self.evidence_retriever.kept_embeddings() if self.context_embeddings_from_index else None
+            if self.answer_hits is not None:
+                self.answer_hits.match(self.evidence_retriever.last_kept_ids)
         self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
-        return self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids, ctx_embeds)
+        out = self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids, ctx_embeds)
+        if self.answer_hits is not None:
+            self.answer_hits.add_mass(out[1], 0, ctx_ids.shape[0])
+        return out
 
     def _keeps_writeback(self):
         return self.index_writeback and self.training
@@ -431,6 +441,8 @@ class EMDR2Model(torch.nn.Module):
             ctx_ids, ctx_types, qext, qone, _, _ = self.evidence_retriever.get_topk_assembled(
                 query_logits.detach(), query_uid, query_ids_t5, query_ids_t5_len, self.cls_id, self.sep_id, self.pad_id)
             ctx_embeds = self.evidence_retriever.kept_embeddings() if self.context_embeddings_from_index else None
+            if self.answer_hits is not None:                             # one match for all groups, like the search
+                self.answer_hits.match(self.evidence_retriever.last_kept_ids)
         self._writeback_rows = getattr(self.evidence_retriever, "last_kept_rows", None) if self._keeps_writeback() else None
         Kk = ctx_ids.shape[1]
         q_leaf = query_logits.detach().requires_grad_(query_logits.requires_grad)
@@ -442,6 +454,8 @@ class EMDR2Model(torch.nn.Module):
                 lm, tlp, one = self.forward_assembled(q_leaf[lo:hi], ctx_ids[lo:hi], ctx_types[lo:hi], qext[lo * Kk:hi * Kk], qone[lo * Kk:hi * Kk],
                                                       dec_ids[lo:hi], ctx_embeds[lo:hi] if ctx_embeds is not None else None)
                 loss, stats = emdr2_loss(lm, tlp, one, labels[lo:hi], loss_mask[lo:hi], eos_id, ret_kldiv=ret_kldiv, totals=totals)
+                if self.answer_hits is not None:
+                    self.answer_hits.add_mass(tlp, lo, hi)
                 del lm, tlp, one
                 if on_group is not None:
                     on_group(i)

@@ -25,8 +25,11 @@ def _cross_entropy_forward_step(batch, model, eos_id):
         batch_ = next(batch)
     except BaseException:
         batch_ = batch
-    query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len, dec_ids, labels, loss_mask, _ = process_batch(batch_)
+    query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len, dec_ids, labels, loss_mask, reference = process_batch(batch_)
     assert torch.all(query_uid < 0), "query uid can't be positive"
+    tracker = getattr(model, "answer_hits", None)
+    if tracker is not None and model.training:                # --retrieval-answer-hits: what this step's retrieval is matched against
+        tracker.begin(batch_['query_uid'].tolist(), reference)
     try:
         ret_kldiv, micro = bool(getattr(get_args(), 'ret_kldiv', False)), int(getattr(get_args(), 'question_micro_batches', 1) or 1)
     except RuntimeError:
@@ -103,7 +106,8 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
     args = get_args()
     if args.beam_size < 1:
         raise AssertionError("--beam-size < 1 is not supported for ORQA reader.")
-    score_list, quid_list = [], []
+    score_list, quid_list, best_list = [], [], []
+    tracker = getattr(model, "answer_hits", None)            # --retrieval-answer-hits
     model.eval()
     with torch.no_grad():
         for batch in dataloader:
@@ -115,23 +119,34 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
                 search = BeamSearch(max_decode_len=args.max_decode_len, bos_id=tokenizer.bos_token_id, eos_id=tokenizer.eos_token_id,
                                     beam_size=args.beam_size, topk_evidence=topk_retrievals)
             hypothesis = search.generate_output(model, query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len)
+            if tracker is not None:                           # the passages this batch's answers were read from
+                best_list.append(tracker.best_slots(batch['query_uid'].tolist(), reference, model.evidence_retriever.last_kept_ids)[1])
             for quid, ref, hyp in zip(query_uid.tolist(), reference, hypothesis):
                 score_list.append(float(metric_max_over_ground_truths(exact_match_score, tokenizer.decode(hyp), ref)))
                 quid_list.append(quid)
     model.train()
     scores = torch.tensor(score_list, dtype=torch.float32, device="cuda")
     quids = torch.tensor(quid_list, dtype=torch.int64, device="cuda")
+    if tracker is not None:                                   # best slots travel with the scores: same padding, gather and de-duplication
+        bests = torch.cat(best_list).to(torch.float32) if best_list else torch.zeros(0, device="cuda")
+        scores = torch.stack([scores, bests], dim=1)
     rank, world = _dp()
     if world > 1:                                                        # ranks may hold different counts (drop_last False): pad to the max
-        n = torch.tensor([scores.numel()], device="cuda"); nmax = n.clone()
+        n = torch.tensor([scores.shape[0]], device="cuda"); nmax = n.clone()
         torch.distributed.all_reduce(nmax, op=torch.distributed.ReduceOp.MAX)
-        pad = int(nmax.item()) - scores.numel()
-        scores = torch.cat([scores, torch.zeros(pad, device="cuda")]); quids = torch.cat([quids, torch.zeros(pad, dtype=torch.int64, device="cuda")])
+        pad = int(nmax.item()) - scores.shape[0]
+        scores = torch.cat([scores, torch.zeros((pad,) + tuple(scores.shape[1:]), device="cuda")])
+        quids = torch.cat([quids, torch.zeros(pad, dtype=torch.int64, device="cuda")])
         gs = [torch.empty_like(scores) for _ in range(world)]; gq = [torch.empty_like(quids) for _ in range(world)]
         torch.distributed.all_gather(gs, scores); torch.distributed.all_gather(gq, quids)
         scores, quids = torch.cat(gs), torch.cat(gq)
     score_dict = {q: s for q, s in zip(quids.tolist(), scores.tolist()) if q != 0}     # duplicates (sampler padding) overwrite
-    return {'Exact Match Score': sum(score_dict.values())}, len(score_dict)
+    if tracker is None:
+        return {'Exact Match Score': sum(score_dict.values())}, len(score_dict)
+    stats = {'Exact Match Score': sum(s[0] for s in score_dict.values())}
+    for k in tracker.ks:                                      # counts, like the EM score: metrics_func prints them as percentages of the total
+        stats['Answer Hits@{}'.format(k)] = sum(1 for s in score_dict.values() if s[1] < k)
+    return stats, len(score_dict)
 
 
 def validation_loss(model, dataloader, eos_id):
@@ -349,6 +364,7 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
         audit_index(audited, args.iteration)          # what was loaded or restored, before the first step searches it
     stamped = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if getattr(args, "index_generations", False) else None
     newest_wins = bool(getattr(args, "index_newest_wins", False))
+    hit_tracker = getattr(model, "answer_hits", None)        # --retrieval-answer-hits
     start_epoch = args.iteration // args.train_iters_per_epoch
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
@@ -364,6 +380,8 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 indexer.pump()
             losses = train_step(forward_step, batch, model, optimizer, lr_scheduler, eos_id, guard=guard)
             iteration += 1
+            if hit_tracker is not None:
+                hit_tracker.commit()
             retrieved_ages = None
             if stamped is not None and iteration % args.log_interval == 0 and stamped.last_search_rows is not None:
                 # the ages of the rows this step's search returned (the merged rows of all ranks' questions: the same list on every rank),
@@ -407,6 +425,8 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                     iteration, args.train_iters, dt, lr_scheduler.get_lr())
                 for k in sums:
                     msg += ' {}: {:.6E} |'.format(k, float(sums[k]) / args.log_interval)
+                if hit_tracker is not None:                   # (collective: every rank is here at the same iterations)
+                    msg += hit_tracker.line()
                 print_rank_0(msg)
                 sums = {}
             if args.save and args.save_interval and iteration % args.save_interval == 0:
