@@ -200,6 +200,14 @@ def get_parser():
                         'probability mass on answer-bearing passages.  Evaluation: "Answer Hits@k" beside the exact match score.  k: '
                         '--report-topk-accuracies cut to --topk-retrievals (1 5 20 and --topk-retrievals when none are given).  Off: no '
                         'launch, no output changes')
+    g.add_argument('--reader-attention-mass', action='store_true',
+                   help='(not in the reference) report which retrieved passages the FiD decoder READS: the cross-attention probability mass per '
+                        'passage slot, summed over decoder layers, heads and answer positions and normalised per question (csrc/attention_mass.hip: '
+                        'one small launch behind each decoder cross-attention forward).  Training: every --log-interval line gains "read entropy" '
+                        '(mean entropy of that distribution) and "read-prior agree" (questions whose most-read passage is the retriever\'s top '
+                        'one); with --retrieval-answer-hits also "read mass" (mass on answer-bearing passages, comparable to "hit mass") and '
+                        '"read top1 hit"; the evaluation then prints "Read Top-1 Hit".  Needs 64-channel heads; not with --fp32-validation.  '
+                        'Off: no launch, no output changes')
     return p
 
 
@@ -245,6 +253,10 @@ def parse_args(argv=None):
         args.index_generations = True
     if args.audit_index_interval < 0:
         raise ValueError("--audit-index-interval must be >= 0")
+    if args.reader_attention_mass and (args.kv_channels != 64 or args.fp32_validation):
+        # (the model build refuses the same: emdr2_model.check_reader_attention_mass)
+        raise ValueError("--reader-attention-mass reads the fused bf16 attention kernels' operands and statistics: it needs --kv-channels 64 "
+                         "and does not run with --fp32-validation")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

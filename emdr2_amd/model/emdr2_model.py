@@ -252,7 +252,7 @@ class EMDR2Model(torch.nn.Module):
     def __init__(self, evidence_retriever, cfg=None, t5_vocab_size=None, bert_vocab_size=None, topk=None, seq_length=None, seq_length_ret=None,
                  cls_id=None, sep_id=None, pad_id=0, update_retriever=True, retriever_score_scaling=True, checkpoint_activations=False,
                  disable_retriever_dropout=False, no_query_embedder_training=False, no_context_embedder_training=False,
-                 context_embeddings_from_index=False):
+                 context_embeddings_from_index=False, reader_attention_mass=False):
         """`EMDR2Model(evidence_retriever)` -- the reference's form (emdr2_model.py:31-61): architecture, sequence lengths, top-k and the
         training switches from `get_args()`, vocabulary sizes and special ids from the global tokenizers.  Passing `cfg` and the rest
         explicitly bypasses the globals (tests, bench)."""
@@ -272,6 +272,9 @@ class EMDR2Model(torch.nn.Module):
             checkpoint_activations, disable_retriever_dropout = a.checkpoint_activations, a.disable_retriever_dropout
             no_query_embedder_training, no_context_embedder_training = a.no_query_embedder_training, a.no_context_embedder_training
             context_embeddings_from_index = getattr(a, "context_embeddings_from_index", False)
+            reader_attention_mass = getattr(a, "reader_attention_mass", False)
+        if reader_attention_mass:
+            check_reader_attention_mass(cfg)
         self.topk = topk
         self.language_model = T5Model(cfg, t5_vocab_size, 2, checkpoint_activations)
         self._language_model_key = 'encoder/t5_model'
@@ -299,6 +302,53 @@ class EMDR2Model(torch.nn.Module):
         # --retrieval-answer-hits: an AnswerHitTracker (tasks/openqa/e2eqa/answer_hits.py); the forward step arms it, a step's retrieval is
         # matched once, each question group adds its prior's mass on the hit slots.  None: no launch
         self.answer_hits = None
+        # --reader-attention-mass: the FiD decoder's cross-attention probability mass per retrieved passage (kernels.ATTN_MASS,
+        # csrc/attention_mass.hip).  On: the FiD pass of every forward arms the collector around its decoder call and
+        # `last_attention_mass` is fp32 [B, K] afterwards -- summed over decoder layers, heads and the real decoder positions, normalised
+        # per question to sum 1 (all zeros for a question without a real position); under `forward_backward` the groups' results in
+        # question order; after greedy decoding (search_strategy.SampleOrGreedySearch, incremental form) the sum over the decoding
+        # steps with weight 1 for hypotheses that had not emitted [EOS] before the step.  Beam search does not collect it.  The
+        # one-context pass and the encoders never do.  `reader_mass` (a ReaderMassMeter, tasks/openqa/e2eqa/reader_mass.py) receives
+        # each group's result.  Off: no launch, no allocation, every tensor bit-identical.
+        self.reader_attention_mass = bool(reader_attention_mass)
+        self.last_attention_mass = None
+        self.reader_mass = None
+
+    # ---- --reader-attention-mass ------------------------------------------------------------------------------------------------------
+    def passage_segments(self, enc_ids, B, Kk, S):
+        """The segment table int32 [B, K + 1] of the decoder's keys: the K passages of each question.  Packed keys (a PackedSeqs of B * K
+        sequences, or its grouped form): the sequences' own extents relative to the question's first key; dense keys: multiples of S."""
+        if isinstance(enc_ids, K.PackedSeqs):
+            idx = torch.arange(B, device=enc_ids.cu.device)[:, None] * Kk + torch.arange(Kk + 1, device=enc_ids.cu.device)[None]
+            cu = enc_ids.cu[idx]
+            return (cu - cu[:, :1]).to(torch.int32).contiguous()
+        return (torch.arange(Kk + 1, dtype=torch.int32, device=enc_ids.device) * S)[None].expand(B, Kk + 1).contiguous()
+
+    def arm_attention_mass(self, enc_ids, seg, weights):
+        """Arm the collector for cross-attention calls whose key side is `enc_ids`; -> the buffer fp32 [B, heads, K] the layers add into."""
+        heads = self.language_model.language_model.decoder.layers[0].inter_attention.heads
+        out = torch.zeros((seg.shape[0], heads, seg.shape[1] - 1), dtype=torch.float32, device=seg.device)
+        K.ATTN_MASS.arm(enc_ids, seg, weights, out)
+        return out
+
+    @staticmethod
+    def finish_attention_mass(out):
+        """Disarm; the buffer summed over heads and normalised per question -> fp32 [B, K]."""
+        K.ATTN_MASS.disarm()
+        return normalise_mass(out.sum(1))
+
+    def _decode_fid(self, dec_ids, enc, enc_ids, seqs, B, Kk, S):
+        """The FiD decoder pass; with --reader-attention-mass armed around it.  `seqs`: the ungrouped PackedSeqs behind packed keys."""
+        if not self.reader_attention_mass:
+            return self.language_model.decode(dec_ids, enc, enc_ids)
+        seg = self.passage_segments(seqs if seqs is not None else enc_ids, B, Kk, S)
+        out = self.arm_attention_mass(enc_ids, seg, (dec_ids != 0).to(torch.float32))
+        try:
+            lm_logits = self.language_model.decode(dec_ids, enc, enc_ids)
+        finally:
+            mass = self.finish_attention_mass(out)
+        self.last_attention_mass = mass
+        return lm_logits
 
     def retriever_embedder(self, tokens, mask, types, embedder_type, disable_dropout=False):
         tower = self.retriever_model.query_model if embedder_type == "query" else self.retriever_model.context_model
@@ -329,6 +379,8 @@ class EMDR2Model(torch.nn.Module):
         out = self.forward_assembled(query_logits, ctx_ids, ctx_types, qext, qone, dec_ids, ctx_embeds)
         if self.answer_hits is not None:
             self.answer_hits.add_mass(out[1], 0, ctx_ids.shape[0])
+        if self.reader_mass is not None and self.reader_attention_mass and dec_ids is not None:
+            self.reader_mass.add(self.last_attention_mass, out[1], 0, ctx_ids.shape[0])
         return out
 
     def _keeps_writeback(self):
@@ -378,10 +430,10 @@ class EMDR2Model(torch.nn.Module):
             # the reader encoder over real tokens only; a question's K passages are consecutive sequences of the packed buffer, so the FiD
             # concatenation (:159-161) is the same rows seen as B groups of K sequences -- no pad rows between the passages
             enc, seqs = self.language_model.encode_packed(qext)
-            lm_logits = self.language_model.decode(dec_ids, enc, seqs.grouped(Kk)) if dec_ids is not None else None
+            lm_logits = self._decode_fid(dec_ids, enc, seqs.grouped(Kk), seqs, B, Kk, S) if dec_ids is not None else None
         else:
             enc = self.language_model.encode(qext).reshape(B, Kk * S, H)                      # K passages concatenated (FiD), :148-164
-            lm_logits = self.language_model.decode(dec_ids, enc, qext.reshape(B, Kk * S)) if dec_ids is not None else None   # :166-183
+            lm_logits = self._decode_fid(dec_ids, enc, qext.reshape(B, Kk * S), None, B, Kk, S) if dec_ids is not None else None   # :166-183
 
         one = None
         if dec_ids is None and self.training:
@@ -447,7 +499,7 @@ class EMDR2Model(torch.nn.Module):
         Kk = ctx_ids.shape[1]
         q_leaf = query_logits.detach().requires_grad_(query_logits.requires_grad)
         bounds = question_group_bounds(B, m)
-        loss_sum, stats_sum = None, {}
+        loss_sum, stats_sum, masses = None, {}, []
         try:
             for i, (lo, hi) in enumerate(bounds):
                 K.DROPOUT.micro = i
@@ -456,6 +508,10 @@ class EMDR2Model(torch.nn.Module):
                 loss, stats = emdr2_loss(lm, tlp, one, labels[lo:hi], loss_mask[lo:hi], eos_id, ret_kldiv=ret_kldiv, totals=totals)
                 if self.answer_hits is not None:
                     self.answer_hits.add_mass(tlp, lo, hi)
+                if self.reader_attention_mass:
+                    masses.append(self.last_attention_mass)
+                    if self.reader_mass is not None:
+                        self.reader_mass.add(self.last_attention_mass, tlp, lo, hi)
                 del lm, tlp, one
                 if on_group is not None:
                     on_group(i)
@@ -468,6 +524,8 @@ class EMDR2Model(torch.nn.Module):
             K.DROPOUT.micro = 0
         if q_leaf.grad is not None:
             query_logits.backward(q_leaf.grad)                           # the query tower's backward: once, over all B questions
+        if masses:
+            self.last_attention_mass = torch.cat(masses, dim=0)          # the groups' questions, in question order
         return loss_sum, stats_sum
 
     def state_dict_for_save_checkpoint(self):
@@ -513,6 +571,22 @@ class EMDR2Model(torch.nn.Module):
             return
         checkpointing.load_t5_checkpoint(self.language_model, pretrained_t5_load)
         checkpointing.load_dualencoder_checkpoint(self.retriever_model, pretrained_dpr_load)
+
+
+def check_reader_attention_mass(cfg):
+    """--reader-attention-mass observes the fused bf16 attention kernels: refused where they do not run."""
+    if cfg.kv_channels != 64:
+        raise ValueError("reader_attention_mass needs attention heads of 64 channels (kv_channels = %d): the mass kernel reads the fused "
+                         "attention kernels' operands and statistics, and other head sizes run the composed GEMM + softmax path" % cfg.kv_channels)
+    if getattr(cfg, "compute_dtype", "bf16") == "fp32":
+        raise ValueError("reader_attention_mass is a bf16 instrument: the fp32 validation path (--fp32-validation) keeps the probabilities "
+                         "themselves and has no (m, l) statistics to rebuild them from")
+
+
+def normalise_mass(mass):
+    """fp32 [B, K] non-negative -> each row divided by its sum; a row that sums to 0 (no weighted position) stays all zeros."""
+    tot = mass.sum(dim=1, keepdim=True)
+    return torch.where(tot > 0, mass / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.zeros_like(mass))
 
 
 def question_group_bounds(batch, micro_batches):

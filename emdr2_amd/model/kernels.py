@@ -1020,6 +1020,61 @@ def _composed_attention_bwd(L, q, k, v, m, l, D, dctx, dq, dk, dv, drop_p, seed)
             out.copy_(g[..., :L.hn])
 
 
+def attention_key_mass(q, k, ids_q, ids_k, m, l, seg, w, mass, accumulate=False, scale=None):
+    """mass[b, h, g] (+)= sum over the real queries i (weight w[b, i]) and the keys j of segment g of the attention probability
+    exp(s_ij - (m_i + ln l_i)) (include/emdr2_ops.h: emdr2_attention_key_mass).  q bf16 [b, sq <= 128, heads, 64] (a strided view) over dense
+    ids_q [b, sq]; k [b, sk, heads, 64] over dense ids_k [b, sk], or [rows, heads, 64] over a PackedSeqs; m, l fp32 [b, heads, sq] of the
+    forward over the same operands; seg int32 [b, n_seg + 1] key offsets inside each sequence; w fp32 [b, sq] or None (weight 1);
+    mass fp32 [b, heads, n_seg].  Returns mass."""
+    _check_bf16(q, k)
+    iq, _, q_sb, q_ss, q_sn, b, sq = _attn_side(q, ids_q)
+    ik, cu_k, k_sb, k_ss, k_sn, bk, sk = _attn_side(k, ids_k)
+    heads, hn = q.shape[-2:]
+    n_seg = seg.shape[1] - 1
+    if b != bk or tuple(k.shape[-2:]) != (heads, hn):
+        raise ValueError("query and key operands differ in batch, heads or head dim")
+    for t, dt, shape in ((m, torch.float32, (b, heads, sq)), (l, torch.float32, (b, heads, sq)), (seg, torch.int32, (b, n_seg + 1)),
+                         (mass, torch.float32, (b, heads, n_seg))) + (((w, torch.float32, (b, sq)),) if w is not None else ()):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("attention_key_mass: expected a contiguous CUDA %s tensor of shape %s, got %s %s" % (dt, shape, t.dtype, tuple(t.shape)))
+    _native.check(_lib().emdr2_attention_key_mass(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, iq.data_ptr(), ik.data_ptr(),
+                                                  _ptr(cu_k), m.data_ptr(), l.data_ptr(), seg.data_ptr(), _ptr(w), mass.data_ptr(), b, heads, sq,
+                                                  sk, n_seg, hn, 1.0 / math.sqrt(hn) if scale is None else scale, int(bool(accumulate)), _sp()),
+                  "attention_key_mass")
+    return mass
+
+
+class _AttentionMass(object):
+    """Reader attention mass (--reader-attention-mass): while armed, every attention forward whose KEY side is the armed one -- the FiD
+    decoder's cross-attention over a question's K passages -- hands its (q, k view, ids, m, l) to the mass kernel right behind the forward's
+    launch, and the layers add up in `out` fp32 [b, heads, n_seg].  The key side is named by identity (the dense ids tensor or the
+    PackedSeqs the decoder passes down), so the decoder's self-attention, the encoder and the one-context pass never match.  A forward
+    that consumes a stash (the re-run of a checkpointed layer inside the backward) launches nothing and records nothing, and the model
+    disarms the collector when the decoder's forward returns, before any backward.  Unarmed: one attribute test per attention call.
+    `keep` (tests only): the operands of each recorded call are retained in `calls`."""
+
+    def __init__(self):
+        self.ids_k = self.seg = self.w = self.out = None
+        self.keep, self.calls, self.count = False, [], 0
+
+    def arm(self, ids_k, seg, w, out):
+        self.ids_k, self.seg, self.w, self.out, self.count = ids_k, seg, w, out, 0
+
+    def disarm(self):
+        self.ids_k = self.seg = self.w = self.out = None
+
+    def record(self, L, q, k, m, l):
+        if not L.fused or L.pq:
+            raise ValueError("the reader attention mass needs the fused attention kernels (head dim 64, dense decoder queries)")
+        attention_key_mass(q, k, L.ids_q, L.ids_k, m, l, self.seg, self.w, self.out, accumulate=self.count > 0, scale=L.scale)
+        self.count += 1
+        if self.keep:
+            self.calls.append(dict(q=q.detach(), k=k.detach(), ids_q=L.ids_q, ids_k=L.ids_k, m=m, l=l, seg=self.seg, w=None if self.w is None else self.w.clone()))
+
+
+ATTN_MASS = _AttentionMass()
+
+
 class AttentionCoreFn(torch.autograd.Function):
     """dropout(softmax(mask(Q K^T / sqrt(hn)))) V for all heads (transformer.py:283-381).
     Inputs are the projection outputs themselves: self-attention passes `qsrc` = the packed [b, s, 3, np, hn] QKV tensor (kvsrc None),
@@ -1052,6 +1107,8 @@ class AttentionCoreFn(torch.autograd.Function):
                 ids_q.zero_tail(ctxo)
         else:
             _composed_attention_fwd(L, q, k, v, ctxo, m, l, drop_p, seed)
+        if ATTN_MASS.ids_k is not None and ids_k is ATTN_MASS.ids_k:                      # the armed cross-attention, right behind its launch
+            ATTN_MASS.record(L, q, k, m, l)
         ctx.save_for_backward(qsrc, kvsrc, m, l, ctxo)
         if stash_key and ATTN_STASH.mode == 'store':
             ATTN_STASH.store[stash_key] = (ctxo, m, l)

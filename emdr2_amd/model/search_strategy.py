@@ -12,10 +12,24 @@ the block form (decoder over the fixed [B, max_decode_len] block padded with id 
 import numpy as np
 import torch
 
+from emdr2_amd.model.kernels import ATTN_MASS
 from emdr2_amd.model.transformer import cross_kv_cache
 
 
+class _mass_disarmed_on_exit(object):
+    """Whatever ends the decoding loop, the attention-mass collector (kernels.ATTN_MASS) is not left armed."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        ATTN_MASS.disarm()
+
+
 class SampleOrGreedySearch(object):
+    """Greedy / sampled decoding.  With the model's `reader_attention_mass` on, the incremental form leaves the attention mass per
+    retrieved passage, accumulated over the decoding steps, in `model.last_attention_mass` (the block form and BeamSearch do not)."""
+
     def __init__(self, max_decode_len, bos_id, eos_id, sample=False, topk_evidence=-1, incremental=True, keep_logits=False):
         self.max_decode_length, self.bos_id, self.eos_id, self.sample, self.incremental = max_decode_len, bos_id, eos_id, sample, incremental
         self.keep_logits = keep_logits         # tests only: hold every step's [b, V] logits in `last_logits` (compares the two decoding forms)
@@ -30,7 +44,12 @@ class SampleOrGreedySearch(object):
         result = []
         hidden = ids_unflat = topk_log_probs = None
         self.last_logits = []
-        with torch.no_grad(), cross_kv_cache(model):
+        # --reader-attention-mass (incremental form): every step's cross-attention (one query per hypothesis over the dense keys of its K
+        # passages) adds into one buffer, with weight 1 for hypotheses that had not emitted [EOS] before the step
+        emdr2 = getattr(model, "module", model)
+        collect = self.incremental and getattr(emdr2, "reader_attention_mass", False)
+        mass = step_w = None
+        with torch.no_grad(), cross_kv_cache(model), _mass_disarmed_on_exit():
             state = None
             for i in range(L):
                 if i == 0 and self.incremental:
@@ -49,6 +68,14 @@ class SampleOrGreedySearch(object):
                         state = reader.language_model.init_decode_state(batch, L, y_block.device)
                         y_pad = torch.zeros((batch, state["len"]), dtype=torch.int64, device=y_block.device)
                     y_pad[:, :L] = y_block
+                    if collect:
+                        live = torch.from_numpy((eos_flags == 0).astype(np.float32)).to(y_block.device)[:, None]
+                        if mass is None:
+                            Kk = emdr2.topk
+                            step_w = live.contiguous()
+                            mass = emdr2.arm_attention_mass(ids_unflat, emdr2.passage_segments(ids_unflat, batch, Kk, ids_unflat.shape[1] // Kk), step_w)
+                        else:
+                            step_w.copy_(live)
                     step_logits = reader.decode_step(y_block[:, i:i + 1].contiguous(), i, y_pad, hidden, ids_unflat, state)[:, 0, :]
                 if self.keep_logits:
                     self.last_logits.append(step_logits.float())
@@ -63,6 +90,8 @@ class SampleOrGreedySearch(object):
                 eos_flags += (ys == self.eos_id)
                 if np.all(eos_flags):
                     break
+            if mass is not None:
+                emdr2.last_attention_mass = emdr2.finish_attention_mass(mass)
         result = np.stack(result).T
         outs = []
         for y in result:
@@ -82,7 +111,8 @@ class BeamSearch(object):
     (possibly empty).  The MI355X side of it: the reference re-runs the whole model call on [batch * beam] prefixes every step and
     re-gathers the [batch * beam, K * S, h] encoder states by parent index every step; here a step decodes ONE position through the
     per-layer self-attention K/V caches, which are what gets re-ordered by parent (a few KB per hypothesis), while the encoder states and
-    their cross-attention K/V projection are expanded once (all hypotheses of a question share them, so re-ordering them is a no-op)."""
+    their cross-attention K/V projection are expanded once (all hypotheses of a question share them, so re-ordering them is a no-op).  The reader attention mass
+    (--reader-attention-mass) is not collected here: which hypothesis a step's mass belongs to changes with every re-ordering."""
 
     def __init__(self, max_decode_len, bos_id, eos_id, beam_size=5, alpha=0.6, topk_evidence=-1):
         self.max_decode_length, self.bos_id, self.eos_id, self.k, self.alpha = max_decode_len, bos_id, eos_id, beam_size, alpha

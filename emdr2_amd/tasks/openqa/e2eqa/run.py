@@ -66,13 +66,17 @@ def model_provider(args=None, bert_tokenizer=None, t5_tokenizer=None, arena=None
                        disable_retriever_dropout=args.disable_retriever_dropout,
                        no_query_embedder_training=args.no_query_embedder_training,
                        no_context_embedder_training=args.no_context_embedder_training,
-                       context_embeddings_from_index=bool(getattr(args, "context_embeddings_from_index", False)))
+                       context_embeddings_from_index=bool(getattr(args, "context_embeddings_from_index", False)),
+                       reader_attention_mass=bool(getattr(args, "reader_attention_mass", False)))
     model.index_writeback = bool(getattr(args, "index_writeback", False))
     if getattr(args, "retrieval_answer_hits", False):
         from emdr2_amd.tasks.openqa.e2eqa.answer_hits import AnswerHitTracker, report_ranks
         retriever.track_kept_ids = True
         model.answer_hits = AnswerHitTracker(arena, bert_tokenizer, args.topk_retrievals,
                                              report_ranks(args.report_topk_accuracies, args.topk_retrievals))
+    if getattr(args, "reader_attention_mass", False):
+        from emdr2_amd.tasks.openqa.e2eqa.reader_mass import ReaderMassMeter
+        model.reader_mass = ReaderMassMeter(args.topk_retrievals, model.answer_hits)
     model.set_recompute_keep_last(getattr(args, "recompute_keep_last_layers", 0))
     sel = [int(v) for v in str(getattr(args, "selective_retention_layers", "0,0,0")).split(",")]
     if any(sel):

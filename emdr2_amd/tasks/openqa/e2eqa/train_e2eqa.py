@@ -30,6 +30,9 @@ def _cross_entropy_forward_step(batch, model, eos_id):
     tracker = getattr(model, "answer_hits", None)
     if tracker is not None and model.training:                # --retrieval-answer-hits: what this step's retrieval is matched against
         tracker.begin(batch_['query_uid'].tolist(), reference)
+    meter = getattr(model, "reader_mass", None)
+    if meter is not None and model.training:                  # --reader-attention-mass: the groups of this step add to it
+        meter.begin()
     try:
         ret_kldiv, micro = bool(getattr(get_args(), 'ret_kldiv', False)), int(getattr(get_args(), 'question_micro_batches', 1) or 1)
     except RuntimeError:
@@ -106,8 +109,9 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
     args = get_args()
     if args.beam_size < 1:
         raise AssertionError("--beam-size < 1 is not supported for ORQA reader.")
-    score_list, quid_list, best_list = [], [], []
+    score_list, quid_list, best_list, read_list = [], [], [], []
     tracker = getattr(model, "answer_hits", None)            # --retrieval-answer-hits
+    read = tracker is not None and getattr(model, "reader_attention_mass", False) and args.beam_size == 1    # --reader-attention-mass
     model.eval()
     with torch.no_grad():
         for batch in dataloader:
@@ -120,7 +124,11 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
                                     beam_size=args.beam_size, topk_evidence=topk_retrievals)
             hypothesis = search.generate_output(model, query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len)
             if tracker is not None:                           # the passages this batch's answers were read from
-                best_list.append(tracker.best_slots(batch['query_uid'].tolist(), reference, model.evidence_retriever.last_kept_ids)[1])
+                hit_pos, best = tracker.best_slots(batch['query_uid'].tolist(), reference, model.evidence_retriever.last_kept_ids)
+                best_list.append(best)
+                if read:                                      # does the slot the decoder read most, over its decoding steps, hold an answer
+                    top = model.last_attention_mass.argmax(dim=1)
+                    read_list.append(hit_pos.gather(1, top[:, None])[:, 0] >= 0)
             for quid, ref, hyp in zip(query_uid.tolist(), reference, hypothesis):
                 score_list.append(float(metric_max_over_ground_truths(exact_match_score, tokenizer.decode(hyp), ref)))
                 quid_list.append(quid)
@@ -129,7 +137,10 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
     quids = torch.tensor(quid_list, dtype=torch.int64, device="cuda")
     if tracker is not None:                                   # best slots travel with the scores: same padding, gather and de-duplication
         bests = torch.cat(best_list).to(torch.float32) if best_list else torch.zeros(0, device="cuda")
-        scores = torch.stack([scores, bests], dim=1)
+        cols = [scores, bests]
+        if read:
+            cols.append(torch.cat(read_list).to(torch.float32) if read_list else torch.zeros(0, device="cuda"))
+        scores = torch.stack(cols, dim=1)
     rank, world = _dp()
     if world > 1:                                                        # ranks may hold different counts (drop_last False): pad to the max
         n = torch.tensor([scores.shape[0]], device="cuda"); nmax = n.clone()
@@ -146,6 +157,8 @@ def reader_em_score(model, dataloader, topk_retrievals, tokenizer):
     stats = {'Exact Match Score': sum(s[0] for s in score_dict.values())}
     for k in tracker.ks:                                      # counts, like the EM score: metrics_func prints them as percentages of the total
         stats['Answer Hits@{}'.format(k)] = sum(1 for s in score_dict.values() if s[1] < k)
+    if read:
+        stats['Read Top-1 Hit'] = sum(1 for s in score_dict.values() if s[2] > 0)
     return stats, len(score_dict)
 
 
@@ -365,6 +378,7 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
     stamped = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if getattr(args, "index_generations", False) else None
     newest_wins = bool(getattr(args, "index_newest_wins", False))
     hit_tracker = getattr(model, "answer_hits", None)        # --retrieval-answer-hits
+    read_meter = getattr(model, "reader_mass", None)         # --reader-attention-mass
     start_epoch = args.iteration // args.train_iters_per_epoch
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
@@ -382,6 +396,8 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
             iteration += 1
             if hit_tracker is not None:
                 hit_tracker.commit()
+            if read_meter is not None:
+                read_meter.commit()
             retrieved_ages = None
             if stamped is not None and iteration % args.log_interval == 0 and stamped.last_search_rows is not None:
                 # the ages of the rows this step's search returned (the merged rows of all ranks' questions: the same list on every rank),
@@ -427,6 +443,8 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                     msg += ' {}: {:.6E} |'.format(k, float(sums[k]) / args.log_interval)
                 if hit_tracker is not None:                   # (collective: every rank is here at the same iterations)
                     msg += hit_tracker.line()
+                if read_meter is not None:
+                    msg += read_meter.line()
                 print_rank_0(msg)
                 sums = {}
             if args.save and args.save_interval and iteration % args.save_interval == 0:

@@ -163,6 +163,23 @@ int emdr2_attention_bwd_splitkv(const void *q, int64_t q_sb, int64_t q_ss, int64
                                 int max_sk, int head_dim, int causal, float scale, float drop_p, uint32_t seed, int ksplit, void *ws, size_t ws_bytes,
                                 void *stream);
 
+/* Attention probability mass per key segment (csrc/attention_mass.hip): which keys a forward launch read.  The operands and the masking rule
+ * are those of emdr2_attention_fwd_splitkv -- q dense bf16 [batch, sq <= 128, heads, 64] as a strided view, keys dense ([batch, sk],
+ * sk % 32 == 0) or packed through cu_k, pad id 0 masked -- plus that forward's row statistics m, l (fp32 [batch, heads, sq], of the
+ * un-dropped softmax), a segment table seg (int32 [batch, n_seg + 1]: key offsets relative to the first key of sequence b, non-decreasing,
+ * inside the sequence; empty segments give 0, keys outside every segment are not counted) and query weights w (fp32 [batch, sq]; NULL = 1):
+ *     mass[b, h, g] (+)= sum_{i : ids_q[b, i] != 0} w[b, i] sum_{j in seg g} exp(s_ij - (m_i + ln l_i))
+ *     s_ij = scale q_i . k_j, REPLACED by -10000 where the key is masked
+ * mass is fp32 [batch, heads, n_seg].  No history mask, no dropout (the pre-dropout probability); a query whose token id is 0 contributes
+ * nothing whatever w says.  accumulate != 0 adds to what mass holds.  Every element is written by one workgroup in a fixed order: results
+ * are bit-reproducible and a sequence's do not depend on what it is batched with.
+ * -1: null q, k, ids, m, l, seg or mass, batch / heads / sq / n_seg < 1, q or k not 16-byte aligned; -4: head_dim != 64, sq > 128,
+ * max_sk > 65,536, dense sk % 32 != 0, strides that are no multiple of 8 elements. */
+int emdr2_attention_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
+                             const int64_t *ids_q, const int64_t *ids_k, const int32_t *cu_k, const float *m, const float *l,
+                             const int32_t *seg, const float *w, float *mass, int batch, int heads, int sq, int max_sk, int n_seg, int head_dim,
+                             float scale, int accumulate, void *stream);
+
 /* dpre = dact * gelu'(pre), exact-erf GELU (transformer.py:80,103-104; the tanh fusion of fused_bias_gelu.py is off in all scripts) */
 int emdr2_gelu_bwd(const void *pre, const void *dact, void *dpre, int64_t n, void *stream);
 

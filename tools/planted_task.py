@@ -286,8 +286,44 @@ def train(tmp, world, steps=300, update_retriever=True, batch=16, lr=2e-4, extra
     em_top1 = em_reading_the_top_passage(model, os.path.join(tmp, "valid.tsv"))
     from emdr2_amd.model import kernels as K
     K.GRAD_SINK = None
-    return {"recall_before": before, "recall_after": after, "em_top1": em_top1, "em_fid": float(stats["Exact Match Score"]) / max(int(total), 1),
-            "questions": int(total), "steps": steps, "update_retriever": bool(update_retriever)}
+    res = {"recall_before": before, "recall_after": after, "em_top1": em_top1, "em_fid": float(stats["Exact Match Score"]) / max(int(total), 1),
+           "questions": int(total), "steps": steps, "update_retriever": bool(update_retriever)}
+    if getattr(model, "reader_attention_mass", False) and getattr(model, "answer_hits", None) is not None:
+        # (--reader-attention-mass --retrieval-answer-hits in `extra`) optional fields: does the FiD decoder READ the gold passage
+        res.update(read_mass_on_gold(model, os.path.join(tmp, "valid.tsv")))
+    return res
+
+
+def read_mass_on_gold(model, qa_file):
+    """Greedy decoding over the validation questions with all K passages: the decoder's attention mass on the slots that hold the answer --
+    in this world the gold passage, wherever the retriever ranked it -- averaged over the questions whose retrieval holds it, next to the
+    uniform share 1 / K a reader that cannot choose would give it; and how often the gold slot is the most-read one."""
+    import torch
+    from emdr2_amd.global_vars import get_args, get_t5_tokenizer, get_tokenizer
+    from emdr2_amd.model.search_strategy import SampleOrGreedySearch
+    from emdr2_amd.tasks.openqa.e2eqa.train_data_utils import OpenQADataset
+    from emdr2_amd.tasks.openqa.e2eqa.train_e2eqa import build_data_loader, process_batch
+    args, tok = get_args(), get_t5_tokenizer()
+    ds = OpenQADataset("OPENQA_DATASET", "valid", [qa_file], get_tokenizer(), args.seq_length_ret, args.decoder_seq_length, seed=args.seed)
+    loader = build_data_loader(ds, args.eval_batch_size, num_workers=0, drop_last=False, shuffle=False)
+    mass_sum = top_sum = n = 0.0
+    was_training = model.training
+    model.eval()
+    with torch.no_grad():
+        for batch in loader:
+            query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len, _, _, _, reference = process_batch(batch)
+            search = SampleOrGreedySearch(max_decode_len=args.max_decode_len, bos_id=tok.bos_token_id, eos_id=tok.eos_token_id, sample=False,
+                                          topk_evidence=args.topk_retrievals)
+            search.generate_output(model, query_uid, q_bert, q_types, q_mask, q_t5, q_t5_len)
+            hits = model.answer_hits.best_slots(batch['query_uid'].tolist(), reference, model.evidence_retriever.last_kept_ids)[0] >= 0
+            mass = model.last_attention_mass
+            has = hits.any(dim=1)
+            mass_sum += float(((mass * hits).sum(dim=1) * has).sum())
+            top_sum += float((hits.gather(1, mass.argmax(dim=1)[:, None])[:, 0] & has).sum())
+            n += float(has.sum())
+    model.train(was_training)
+    return {"read_mass_gold": mass_sum / max(n, 1.0), "read_top1_gold": top_sum / max(n, 1.0), "read_questions_with_gold": int(n),
+            "read_uniform_share": 1.0 / args.topk_retrievals}
 
 
 def em_reading_the_top_passage(model, qa_file):
@@ -327,6 +363,9 @@ if __name__ == "__main__":
     ap.add_argument("--reader-steps", type=int, default=400)
     ap.add_argument("--no-update-retriever", action="store_true")
     ap.add_argument("--both", action="store_true", help="the run AND its control from the same prepared world")
+    ap.add_argument("--reader-attention-mass", action="store_true",
+                    help="run with --reader-attention-mass --retrieval-answer-hits: the JSON line gains read_mass_gold (the FiD decoder's attention "
+                         "mass on the gold passage), read_top1_gold, read_questions_with_gold and read_uniform_share (1 / K)")
     ap.add_argument("--writeback-arms", metavar="JSONL", default=None,
                     help="instead: two runs WITHOUT the refresher from the same prepared world, the second with --index-writeback; one JSON "
                          "line per arm (recall@1/5/20 before and after, EM) is also appended to this file")
@@ -340,4 +379,5 @@ if __name__ == "__main__":
                 fh.write(json.dumps(res) + "\n")
         sys.exit(0)
     for upd in ((True, False) if o.both else (not o.no_update_retriever,)):
-        print(json.dumps(train(o.dir, w, o.steps, upd, o.batch, o.lr)), flush=True)
+        extra = ["--reader-attention-mass", "--retrieval-answer-hits"] if o.reader_attention_mass else []
+        print(json.dumps(train(o.dir, w, o.steps, upd, o.batch, o.lr, extra=extra)), flush=True)
