@@ -139,6 +139,10 @@ SIGNATURES["emdr2_attention_bwd_splitkv"] = (_i32, [_vp, _i64, _i64, _i64, _vp, 
 # q + strides, k + strides, ids_q, ids_k, cu_k, m, l, seg, w, mass, batch, heads, sq, max_sk, n_seg, head_dim, scale, accumulate, stream
 SIGNATURES["emdr2_attention_key_mass"] = (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp])
+# ... seg, w, kw, kw_ld, mass, ... (the weighted form); x + strides, norm, ld, batch, sk, heads, head_dim, stream
+SIGNATURES["emdr2_attention_key_mass_weighted"] = (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                            _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp])
+SIGNATURES["emdr2_head_row_norms"] = (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp])
 SIGNATURES["emdr2_gemm_nt_lse_bf16"] = (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp])
 SIGNATURES["emdr2_retriever_prior_fwd"] = (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])
 SIGNATURES["emdr2_retriever_prior_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp])

@@ -208,6 +208,19 @@ def get_parser():
                         'one); with --retrieval-answer-hits also "read mass" (mass on answer-bearing passages, comparable to "hit mass") and '
                         '"read top1 hit"; the evaluation then prints "Read Top-1 Hit".  Needs 64-channel heads; not with --fp32-validation.  '
                         'Off: no launch, no output changes')
+    g.add_argument('--retriever-distill-attention', action='store_true',
+                   help='(not in the reference) train the retriever towards what the reader READS (FiD-KD): the retriever loss is '
+                        'KL(read || prior) per question, where "read" is the FiD decoder\'s cross-attention probability mass per passage slot -- '
+                        'the quantity of --reader-attention-mass, measured in the FiD pass the step runs anyway and taken as a constant.  A '
+                        'choice of objective, not a tuning knob: it replaces the EMDR2 marginal, and the no-grad one-context pass over all '
+                        'B x K passages that only the marginal (and --ret-kldiv) needs is not run.  Needs --update-retriever and 64-channel '
+                        'heads; exclusive with --ret-kldiv; not with --fp32-validation.  Off: the step launches what it launched before')
+    g.add_argument('--attention-mass-value-norms', action='store_true',
+                   help='(not in the reference) weight every attention probability of the mass by the norm of its key\'s value vector, '
+                        '||v_j||_2 per head and layer (ATLAS-style attention distillation; csrc/attention_mass.hip: one norm launch per '
+                        'decoder layer and group, once per batch under greedy decoding).  A choice of what "read" means, wherever the mass is '
+                        'collected: the log fields of --reader-attention-mass and the target of --retriever-distill-attention change together.  '
+                        'Needs one of those two flags')
     return p
 
 
@@ -257,6 +270,17 @@ def parse_args(argv=None):
         # (the model build refuses the same: emdr2_model.check_reader_attention_mass)
         raise ValueError("--reader-attention-mass reads the fused bf16 attention kernels' operands and statistics: it needs --kv-channels 64 "
                          "and does not run with --fp32-validation")
+    if args.retriever_distill_attention:
+        if not args.update_retriever:
+            raise ValueError("--retriever-distill-attention is a retriever loss: it needs --update-retriever")
+        if args.ret_kldiv:
+            raise ValueError("--retriever-distill-attention and --ret-kldiv are exclusive (each names THE retriever loss)")
+        if args.kv_channels != 64 or args.fp32_validation:
+            raise ValueError("--retriever-distill-attention distils from the attention mass, which reads the fused bf16 attention kernels' "
+                             "operands and statistics: it needs --kv-channels 64 and does not run with --fp32-validation")
+    if args.attention_mass_value_norms and not (args.reader_attention_mass or args.retriever_distill_attention):
+        raise ValueError("--attention-mass-value-norms changes what the attention mass holds: it needs --reader-attention-mass or "
+                         "--retriever-distill-attention, which collect it")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

@@ -14,6 +14,18 @@
 // there is no LDS tile and no barrier in the loop; the four waves take every fourth 16-key group of the segment.
 // Reduction order (fixed): a lane adds its 4 keys per group, group after group; times the weight; query tiles in order; the 64 lanes by a
 // 6-level butterfly; the 4 waves in order through the LDS.
+//
+// Key weights (emdr2_attention_key_mass_weighted): the kernel is a template over "has key weights".  The weighted instance multiplies
+// each p_ij by kw[h, key row] before the same additions in the same order -- a lane's 4 keys per group belong to ONE head, so kw costs
+// four floats per lane and 16-key group, loaded with the next group's key rows (under the current group's MFMAs) from the row index
+// CLAMPED like the key-row load: nothing outside [lo_key, hi_key) of the segment is read, four scalar 4-byte loads, no alignment assumed.
+// A key past the segment end contributes by SELECT, so kw outside every segment may hold anything.  The unweighted instance compiles
+// none of it.
+//
+// emdr2_head_row_norms: norm[h, r] = sqrt(sum_d x[r, h, d]^2), the per-key weight of value-norm weighted attention (||v_j||_2).  One
+// (row, head) = 128 bytes = 8 lanes x 16 bytes; heads fastest, so a wave reads 8 consecutive heads of a row.  Order of additions (fixed):
+// a lane squares its 8 values (exact in fp32: bf16 x bf16) and adds them in order d = 0..7 -- 7 additions --, then a 3-level xor
+// butterfly over the 8 lanes (1, 2, 4) -- 3 more: depth 10 --, one square root (within one fp32 ulp), lane 0 of the 8 stores.  No atomics.
 #include "../../include/emdr2_ops.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,12 +45,14 @@ struct MassParams {
     const long long *ids_q, *ids_k;
     long long q_sb, q_ss, q_sn, k_sb, k_ss, k_sn;
     const int *cu_k, *seg;
-    const float *m, *l, *w;
+    const float *m, *l, *w, *kw;
+    long long kw_ld;
     float *mass;
     int batch, heads, sq, sk, n_seg, accumulate;
     float scale;
 };
 
+template <bool KW>
 __global__ void __launch_bounds__(MASS_WAVES * 64) attention_key_mass_kernel(MassParams p)
 {
     __shared__ float wave_sum[MASS_WAVES];
@@ -64,6 +78,7 @@ __global__ void __launch_bounds__(MASS_WAVES * 64) attention_key_mass_kernel(Mas
     const char *qbase = p.q + ((long long)b * p.q_sb + (long long)n * p.q_sn) * 2 + grp * 16;
     const long long stat0 = ((long long)b * p.heads + n) * p.sq;
     const float sc2 = p.scale * L2E;
+    const float *kwbase = KW ? p.kw + (long long)n * p.kw_ld + krow0 + lo_key : nullptr;   // + key index inside the segment
 
     float total = 0.f;
     if (wave < ngroups) {
@@ -86,20 +101,28 @@ __global__ void __launch_bounds__(MASS_WAVES * 64) attention_key_mass_kernel(Mas
                 sum[t] = 0.f;
             }
             const bool two = (qt0 + 1) * MASS_QT < p.sq;                                      // wave-uniform: the second tile exists
-            auto load_keys = [&](int kg, bf16x8 (&kf)[2], bool &real) {
+            auto load_keys = [&](int kg, bf16x8 (&kf)[2], bool &real, floatx4 &kwv) {
                 const int kr = kg * MASS_KG + l15;
                 const int key = lo_key + (kr < nkeys ? kr : nkeys - 1);                       // past the segment: re-read its last key, zeroed below
                 const char *krow = kbase + (long long)key * p.k_ss * 2;
                 kf[0] = *(const bf16x8 *)krow;
                 kf[1] = *(const bf16x8 *)(krow + 64);
                 real = p.ids_k[krow0 + key] != 0;
+                if constexpr (KW) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {                                             // the 4 keys this lane holds in the C layout
+                        const int kc = kg * MASS_KG + 4 * grp + r;
+                        kwv[r] = kwbase[kc < nkeys ? kc : nkeys - 1];                         // clamped like the key row: inside the segment
+                    }
+                }
             };
             bf16x8 kf[2], kf_next[2];
             bool real, real_next;
-            load_keys(wave, kf, real);
+            floatx4 kwv = {0.f, 0.f, 0.f, 0.f}, kwv_next = {0.f, 0.f, 0.f, 0.f};
+            load_keys(wave, kf, real, kwv);
             for (int kg = wave; kg < ngroups; kg += MASS_WAVES) {
                 const bool more = kg + MASS_WAVES < ngroups;
-                if (more) load_keys(kg + MASS_WAVES, kf_next, real_next);                     // the next group's rows are in flight under this one's MFMAs
+                if (more) load_keys(kg + MASS_WAVES, kf_next, real_next, kwv_next);           // the next group's rows are in flight under this one's MFMAs
                 const uint32_t km = (uint32_t)__builtin_amdgcn_ballot_w64(real) & 0xffffu;   // lanes 0..15 hold keys 0..15 of the group
                 const int left = nkeys - kg * MASS_KG;                                        // keys of the group inside the segment (>= 1)
 #pragma unroll
@@ -114,11 +137,12 @@ __global__ void __launch_bounds__(MASS_WAVES * 64) attention_key_mass_kernel(Mas
                         const int kl = 4 * grp + r;
                         const float s2 = ((km >> kl) & 1u) ? s[r] * sc2 : MASKED2;            // a masked score is REPLACED
                         const float pr = __builtin_amdgcn_exp2f(s2 - off2[t]);
-                        part += kl < left ? pr : 0.f;
+                        if constexpr (KW) part += kl < left ? pr * kwv[r] : 0.f;              // select: kw past the segment is never used
+                        else part += kl < left ? pr : 0.f;
                     }
                     sum[t] += part;
                 }
-                if (more) { kf[0] = kf_next[0]; kf[1] = kf_next[1]; real = real_next; }
+                if (more) { kf[0] = kf_next[0]; kf[1] = kf_next[1]; real = real_next; if constexpr (KW) kwv = kwv_next; }
             }
             // select, not multiply: the statistics of a padded or absent query may hold anything
             total += wq[0] != 0.f ? wq[0] * sum[0] : 0.f;
@@ -139,23 +163,83 @@ __global__ void __launch_bounds__(MASS_WAVES * 64) attention_key_mass_kernel(Mas
     }
 }
 
+#define NORM_THREADS 256
+
+__global__ void __launch_bounds__(NORM_THREADS) head_row_norms_kernel(const char *x, long long x_sb, long long x_ss, long long x_sn, float *norm,
+                                                                      long long ld, int sk, int heads, long long items)
+{
+    const long long t = (long long)blockIdx.x * NORM_THREADS + threadIdx.x;
+    const long long item = t >> 3;                                  // (row, head), heads fastest; its 8 lanes are one aligned group of the wave
+    if (item >= items) return;
+    const int sub = (int)(t & 7);
+    const int h = (int)(item % heads);
+    const long long r = item / heads;
+    const long long bi = r / sk, si = r - bi * sk;
+    const bf16x8 v = *(const bf16x8 *)(x + (bi * x_sb + si * x_ss + (long long)h * x_sn) * 2 + sub * 16);
+    float acc = (float)v[0] * (float)v[0];
+#pragma unroll
+    for (int d = 1; d < 8; ++d) { const float f = (float)v[d]; acc += f * f; }
+#pragma unroll
+    for (int d = 1; d <= 4; d <<= 1) acc += __shfl_xor(acc, d, 64);
+    if (sub == 0) norm[(long long)h * ld + r] = sqrtf(acc);
+}
+
 } // namespace
+
+static int launch_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
+                           const int64_t *ids_q, const int64_t *ids_k, const int32_t *cu_k, const float *m, const float *l, const int32_t *seg,
+                           const float *w, const float *kw, int64_t kw_ld, bool weighted, float *mass, int batch, int heads, int sq, int max_sk,
+                           int n_seg, int head_dim, float scale, int accumulate, void *stream)
+{
+    if (!q || !k || !ids_q || !ids_k || !m || !l || !seg || !mass || batch < 1 || heads < 1 || sq < 1 || n_seg < 1) return -1;
+    if (weighted && (!kw || ((uintptr_t)kw & 3))) return -1;
+    if (head_dim != 64 || sq > QBLOCK || max_sk < 1 || max_sk > 65536 || (!cu_k && (max_sk & 31))) return -4;
+    if ((q_sb | q_ss | q_sn | k_sb | k_ss | k_sn) & 7) return -4;
+    if (((uintptr_t)q | (uintptr_t)k) & 15) return -1;
+    if ((long long)batch * heads * n_seg > 0x7fffffffLL) return -4;
+    if (weighted && (kw_ld < 1 || (!cu_k && kw_ld < (long long)batch * max_sk))) return -4;   // dense: the table holds every key row
+    MassParams p;
+    p.q = (const char *)q; p.k = (const char *)k; p.ids_q = (const long long *)ids_q; p.ids_k = (const long long *)ids_k;
+    p.q_sb = q_sb; p.q_ss = q_ss; p.q_sn = q_sn; p.k_sb = k_sb; p.k_ss = k_ss; p.k_sn = k_sn;
+    p.cu_k = cu_k; p.seg = seg; p.m = m; p.l = l; p.w = w; p.kw = weighted ? kw : nullptr; p.kw_ld = weighted ? kw_ld : 0; p.mass = mass;
+    p.batch = batch; p.heads = heads; p.sq = sq; p.sk = max_sk; p.n_seg = n_seg; p.accumulate = accumulate; p.scale = scale;
+    const dim3 grid((unsigned)(batch * heads * n_seg)), block(MASS_WAVES * 64);
+    if (weighted) hipLaunchKernelGGL(attention_key_mass_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(attention_key_mass_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 extern "C" int emdr2_attention_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
                                         const int64_t *ids_q, const int64_t *ids_k, const int32_t *cu_k, const float *m, const float *l,
                                         const int32_t *seg, const float *w, float *mass, int batch, int heads, int sq, int max_sk, int n_seg,
                                         int head_dim, float scale, int accumulate, void *stream)
 {
-    if (!q || !k || !ids_q || !ids_k || !m || !l || !seg || !mass || batch < 1 || heads < 1 || sq < 1 || n_seg < 1) return -1;
-    if (head_dim != 64 || sq > QBLOCK || max_sk < 1 || max_sk > 65536 || (!cu_k && (max_sk & 31))) return -4;
-    if ((q_sb | q_ss | q_sn | k_sb | k_ss | k_sn) & 7) return -4;
-    if (((uintptr_t)q | (uintptr_t)k) & 15) return -1;
-    if ((long long)batch * heads * n_seg > 0x7fffffffLL) return -4;
-    MassParams p;
-    p.q = (const char *)q; p.k = (const char *)k; p.ids_q = (const long long *)ids_q; p.ids_k = (const long long *)ids_k;
-    p.q_sb = q_sb; p.q_ss = q_ss; p.q_sn = q_sn; p.k_sb = k_sb; p.k_ss = k_ss; p.k_sn = k_sn;
-    p.cu_k = cu_k; p.seg = seg; p.m = m; p.l = l; p.w = w; p.mass = mass;
-    p.batch = batch; p.heads = heads; p.sq = sq; p.sk = max_sk; p.n_seg = n_seg; p.accumulate = accumulate; p.scale = scale;
-    hipLaunchKernelGGL(attention_key_mass_kernel, dim3((unsigned)(batch * heads * n_seg)), dim3(MASS_WAVES * 64), 0, (hipStream_t)stream, p);
+    return launch_key_mass(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, ids_q, ids_k, cu_k, m, l, seg, w, nullptr, 0, false, mass, batch, heads, sq,
+                           max_sk, n_seg, head_dim, scale, accumulate, stream);
+}
+
+extern "C" int emdr2_attention_key_mass_weighted(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss,
+                                                 int64_t k_sn, const int64_t *ids_q, const int64_t *ids_k, const int32_t *cu_k, const float *m,
+                                                 const float *l, const int32_t *seg, const float *w, const float *kw, int64_t kw_ld, float *mass,
+                                                 int batch, int heads, int sq, int max_sk, int n_seg, int head_dim, float scale, int accumulate,
+                                                 void *stream)
+{
+    return launch_key_mass(q, q_sb, q_ss, q_sn, k, k_sb, k_ss, k_sn, ids_q, ids_k, cu_k, m, l, seg, w, kw, kw_ld, true, mass, batch, heads, sq,
+                           max_sk, n_seg, head_dim, scale, accumulate, stream);
+}
+
+extern "C" int emdr2_head_row_norms(const void *x, int64_t x_sb, int64_t x_ss, int64_t x_sn, float *norm, int64_t ld, int batch, int sk, int heads,
+                                    int head_dim, void *stream)
+{
+    if (!x || !norm || batch < 1 || sk < 1 || heads < 1) return -1;
+    if (((uintptr_t)x & 15) || ((uintptr_t)norm & 3)) return -1;
+    if (head_dim != 64) return -4;
+    if ((x_sb | x_ss | x_sn) & 7) return -4;
+    const long long rows = (long long)batch * sk, items = rows * heads;
+    if (ld < rows) return -4;
+    const long long blocks = (items * 8 + NORM_THREADS - 1) / NORM_THREADS;
+    if (blocks > 0x7fffffffLL) return -4;
+    hipLaunchKernelGGL(head_row_norms_kernel, dim3((unsigned)blocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const char *)x, (long long)x_sb,
+                       (long long)x_ss, (long long)x_sn, norm, (long long)ld, sk, heads, items);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

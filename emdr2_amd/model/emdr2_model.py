@@ -243,6 +243,19 @@ class OneContextLogits(object):
             return K.linear(self.hidden, self.weight, self.bias)
 
 
+class ReadTarget(object):
+    """--retriever-distill-attention: what stands in the training-mode triple where `OneContextLogits` stands otherwise -- the group's
+    reader attention mass per retrieved passage, fp32 [b, K], normalised per question (rows sum to 1, or are all zero for a question
+    without a weighted position), detached: a constant of the step.  `emdr2_loss` dispatches on it (`distill_kl`)."""
+
+    def __init__(self, mass):
+        self.mass = mass.detach()
+
+    @property
+    def shape(self):
+        return tuple(self.mass.shape)
+
+
 class EMDR2Model(torch.nn.Module):
     """reference: megatron/model/emdr2_model.py:31-247.  Same sub-module names (`language_model`, `retriever_model`), same
     checkpoint keys ('encoder/t5_model', 'retriever/biencoder_model'), same training-mode return triple
@@ -252,7 +265,8 @@ class EMDR2Model(torch.nn.Module):
     def __init__(self, evidence_retriever, cfg=None, t5_vocab_size=None, bert_vocab_size=None, topk=None, seq_length=None, seq_length_ret=None,
                  cls_id=None, sep_id=None, pad_id=0, update_retriever=True, retriever_score_scaling=True, checkpoint_activations=False,
                  disable_retriever_dropout=False, no_query_embedder_training=False, no_context_embedder_training=False,
-                 context_embeddings_from_index=False, reader_attention_mass=False):
+                 context_embeddings_from_index=False, reader_attention_mass=False, retriever_distill_attention=False,
+                 attention_mass_value_norms=False):
         """`EMDR2Model(evidence_retriever)` -- the reference's form (emdr2_model.py:31-61): architecture, sequence lengths, top-k and the
         training switches from `get_args()`, vocabulary sizes and special ids from the global tokenizers.  Passing `cfg` and the rest
         explicitly bypasses the globals (tests, bench)."""
@@ -273,8 +287,17 @@ class EMDR2Model(torch.nn.Module):
             no_query_embedder_training, no_context_embedder_training = a.no_query_embedder_training, a.no_context_embedder_training
             context_embeddings_from_index = getattr(a, "context_embeddings_from_index", False)
             reader_attention_mass = getattr(a, "reader_attention_mass", False)
-        if reader_attention_mass:
-            check_reader_attention_mass(cfg)
+            retriever_distill_attention = getattr(a, "retriever_distill_attention", False)
+            attention_mass_value_norms = getattr(a, "attention_mass_value_norms", False)
+        for name, on in (("reader_attention_mass", reader_attention_mass), ("retriever_distill_attention", retriever_distill_attention),
+                         ("attention_mass_value_norms", attention_mass_value_norms)):
+            if on:
+                check_reader_attention_mass(cfg, name)
+        if attention_mass_value_norms and not (reader_attention_mass or retriever_distill_attention):
+            raise ValueError("attention_mass_value_norms changes what the attention mass holds: it needs reader_attention_mass or "
+                             "retriever_distill_attention, which collect it")
+        if retriever_distill_attention and not update_retriever:
+            raise ValueError("retriever_distill_attention is a retriever loss: it needs update_retriever")
         self.topk = topk
         self.language_model = T5Model(cfg, t5_vocab_size, 2, checkpoint_activations)
         self._language_model_key = 'encoder/t5_model'
@@ -313,8 +336,20 @@ class EMDR2Model(torch.nn.Module):
         self.reader_attention_mass = bool(reader_attention_mass)
         self.last_attention_mass = None
         self.reader_mass = None
+        # --retriever-distill-attention: the retriever is trained towards that mass (FiD-KD): the training-mode forward collects it, does NOT
+        # run the one-context pass, and returns a `ReadTarget` as the triple's third element; `emdr2_loss` then takes `distill_kl` of the
+        # prior against it.  The meter and its log fields stay tied to `reader_attention_mass` alone.
+        # --attention-mass-value-norms: every probability of the mass is weighted by its key's value-vector norm ||v_j||_2 per head and
+        # layer (kernels.head_row_norms), wherever the mass is collected -- training, teacher-forced evaluation, greedy decoding -- so the
+        # log lines and the distillation target always describe the same quantity.
+        self.retriever_distill_attention = bool(retriever_distill_attention)
+        self.attention_mass_value_norms = bool(attention_mass_value_norms)
 
     # ---- --reader-attention-mass ------------------------------------------------------------------------------------------------------
+    @property
+    def collects_attention_mass(self):
+        return self.reader_attention_mass or self.retriever_distill_attention
+
     def passage_segments(self, enc_ids, B, Kk, S):
         """The segment table int32 [B, K + 1] of the decoder's keys: the K passages of each question.  Packed keys (a PackedSeqs of B * K
         sequences, or its grouped form): the sequences' own extents relative to the question's first key; dense keys: multiples of S."""
@@ -328,7 +363,7 @@ class EMDR2Model(torch.nn.Module):
         """Arm the collector for cross-attention calls whose key side is `enc_ids`; -> the buffer fp32 [B, heads, K] the layers add into."""
         heads = self.language_model.language_model.decoder.layers[0].inter_attention.heads
         out = torch.zeros((seg.shape[0], heads, seg.shape[1] - 1), dtype=torch.float32, device=seg.device)
-        K.ATTN_MASS.arm(enc_ids, seg, weights, out)
+        K.ATTN_MASS.arm(enc_ids, seg, weights, out, value_norms=self.attention_mass_value_norms)
         return out
 
     @staticmethod
@@ -338,8 +373,8 @@ class EMDR2Model(torch.nn.Module):
         return normalise_mass(out.sum(1))
 
     def _decode_fid(self, dec_ids, enc, enc_ids, seqs, B, Kk, S):
-        """The FiD decoder pass; with --reader-attention-mass armed around it.  `seqs`: the ungrouped PackedSeqs behind packed keys."""
-        if not self.reader_attention_mass:
+        """The FiD decoder pass; with the attention mass collected, armed around it.  `seqs`: the ungrouped PackedSeqs behind packed keys."""
+        if not self.collects_attention_mass:
             return self.language_model.decode(dec_ids, enc, enc_ids)
         seg = self.passage_segments(seqs if seqs is not None else enc_ids, B, Kk, S)
         out = self.arm_attention_mass(enc_ids, seg, (dec_ids != 0).to(torch.float32))
@@ -438,7 +473,9 @@ class EMDR2Model(torch.nn.Module):
         one = None
         if dec_ids is None and self.training:
             raise ValueError("dec_ids=None (encoder only) is an evaluation-mode call")
-        if self.training and self.update_retriever:
+        if self.training and self.update_retriever and self.retriever_distill_attention:
+            one = ReadTarget(self.last_attention_mass)                                        # no one-context pass: the FiD pass above measured the target
+        elif self.training and self.update_retriever:
             with torch.no_grad():                                                             # :185-210
                 dec_rep = torch.repeat_interleave(dec_ids, Kk, dim=0)
                 K.DROPOUT.pass_id = 1                                                         # a second, independent draw of every dropout site
@@ -508,9 +545,9 @@ class EMDR2Model(torch.nn.Module):
                 loss, stats = emdr2_loss(lm, tlp, one, labels[lo:hi], loss_mask[lo:hi], eos_id, ret_kldiv=ret_kldiv, totals=totals)
                 if self.answer_hits is not None:
                     self.answer_hits.add_mass(tlp, lo, hi)
-                if self.reader_attention_mass:
+                if self.collects_attention_mass:
                     masses.append(self.last_attention_mass)
-                    if self.reader_mass is not None:
+                    if self.reader_mass is not None and self.reader_attention_mass:
                         self.reader_mass.add(self.last_attention_mass, tlp, lo, hi)
                 del lm, tlp, one
                 if on_group is not None:
@@ -573,14 +610,15 @@ class EMDR2Model(torch.nn.Module):
         checkpointing.load_dualencoder_checkpoint(self.retriever_model, pretrained_dpr_load)
 
 
-def check_reader_attention_mass(cfg):
-    """--reader-attention-mass observes the fused bf16 attention kernels: refused where they do not run."""
+def check_reader_attention_mass(cfg, what="reader_attention_mass"):
+    """--reader-attention-mass (and what is built on the mass: --retriever-distill-attention, --attention-mass-value-norms) observes the
+    fused bf16 attention kernels: refused where they do not run."""
     if cfg.kv_channels != 64:
-        raise ValueError("reader_attention_mass needs attention heads of 64 channels (kv_channels = %d): the mass kernel reads the fused "
-                         "attention kernels' operands and statistics, and other head sizes run the composed GEMM + softmax path" % cfg.kv_channels)
+        raise ValueError("%s needs attention heads of 64 channels (kv_channels = %d): the mass kernel reads the fused "
+                         "attention kernels' operands and statistics, and other head sizes run the composed GEMM + softmax path" % (what, cfg.kv_channels))
     if getattr(cfg, "compute_dtype", "bf16") == "fp32":
-        raise ValueError("reader_attention_mass is a bf16 instrument: the fp32 validation path (--fp32-validation) keeps the probabilities "
-                         "themselves and has no (m, l) statistics to rebuild them from")
+        raise ValueError("%s is a bf16 instrument: the fp32 validation path (--fp32-validation) keeps the probabilities "
+                         "themselves and has no (m, l) statistics to rebuild them from" % what)
 
 
 def normalise_mass(mass):
@@ -611,6 +649,20 @@ def loss_totals(labels, loss_mask, eos_id):
     return mask.sum(), mask.masked_fill(lab >= eos_id, 0).sum(), labels.shape[0]
 
 
+def distill_kl(topk_log_probs, target, batch):
+    """--retriever-distill-attention: KL(target || prior) summed over the questions and divided by `batch`,
+        L_ret = (1 / B) sum_b sum_{k : t_bk > 0} t_bk (ln t_bk - logp_bk),
+    the `kl_div(..., reduction='sum') / batch` form of the --ret-kldiv line.  topk_log_probs [b, K] (the prior's log-probabilities),
+    target fp32 [b, K] >= 0 (a constant: no gradient flows into it), `batch` the batch-WIDE question count, so the groups of a step sum
+    to the undivided step.  A zero entry contributes exactly 0 (0 ln 0 = 0, by selection), and so does an all-zero row -- to the loss
+    and to the gradient, which is -t / B."""
+    t = target.detach().float()
+    logp = topk_log_probs.float()
+    pos = t > 0
+    terms = torch.where(pos, t * (torch.log(torch.where(pos, t, torch.ones_like(t))) - logp), torch.zeros_like(t))
+    return terms.sum() / batch
+
+
 def emdr2_loss(lm_logits, topk_log_probs, lm_logits_one_context, labels, loss_mask, eos_id, ret_kldiv=False, totals=None):
     """_cross_entropy_forward_step + get_loss_and_retriever_utility (tasks/openqa/e2eqa/train_e2eqa.py:72-181).
     The two vocabulary-sized log-softmax + gather passes run in the HIP kernel; what is left in torch acts on [B,L] / [B,K,L].
@@ -622,6 +674,10 @@ def emdr2_loss(lm_logits, topk_log_probs, lm_logits_one_context, labels, loss_ma
     lm_loss = -torch.sum(gold * mask * (labels != 0)) / mask_sum                              # CrossEntropyLoss(ignore_index=0) * loss_mask
     stats = {"lm_loss": lm_loss.detach()}
     retriever_loss = torch.zeros((), device=lm_logits.device)
+    if isinstance(lm_logits_one_context, ReadTarget):                                         # --retriever-distill-attention
+        retriever_loss = distill_kl(topk_log_probs, lm_logits_one_context.mass, batch)
+        stats["retriever_loss"] = retriever_loss.detach()
+        return lm_loss + retriever_loss, stats
     if lm_logits_one_context is not None:
         Kk = lm_logits_one_context.shape[1]
         lab = labels.masked_fill(~loss_mask.to(torch.bool), 0)

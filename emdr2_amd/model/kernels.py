@@ -1020,12 +1020,38 @@ def _composed_attention_bwd(L, q, k, v, m, l, D, dctx, dq, dk, dv, drop_p, seed)
             out.copy_(g[..., :L.hn])
 
 
-def attention_key_mass(q, k, ids_q, ids_k, m, l, seg, w, mass, accumulate=False, scale=None):
+def head_row_norms(v, out=None):
+    """norm[h, r] = ||v[r, h, :]||_2 in fp32 (include/emdr2_ops.h: emdr2_head_row_norms): v bf16 [rows, heads, 64] (a packed operand) or
+    [b, s, heads, 64] (row r = b * s + s_), any strided view with unit stride along the head dim -- `kv[..., 1, :, :]` of the packed KV
+    projection as it is.  -> fp32 [heads, rows], head-major: the `kw` table of `attention_key_mass`.  `out`: a contiguous fp32
+    [heads, ld >= rows] tensor to write into."""
+    _check_bf16(v)
+    if v.dim() == 3:
+        batch, sk, sb, ss, sn = 1, v.shape[0], 0, v.stride(0), v.stride(1)
+    elif v.dim() == 4:
+        batch, sk, sb, ss, sn = v.shape[0], v.shape[1], v.stride(0), v.stride(1), v.stride(2)
+    else:
+        raise ValueError("head_row_norms: expected [rows, heads, 64] or [b, s, heads, 64], got %s" % (tuple(v.shape),))
+    heads, hn = v.shape[-2:]
+    if v.stride(-1) != 1 or not v.is_cuda:
+        raise ValueError("head_row_norms: expected a CUDA view with unit stride along the head dim")
+    rows = batch * sk
+    if out is None:
+        out = torch.empty((heads, rows), dtype=torch.float32, device=v.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != heads or out.shape[1] < rows or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("head_row_norms: out must be a contiguous CUDA fp32 [heads, >= rows] tensor")
+    if rows:
+        _native.check(_lib().emdr2_head_row_norms(v.data_ptr(), sb, ss, sn, out.data_ptr(), out.shape[1], batch, sk, heads, hn, _sp()), "head_row_norms")
+    return out
+
+
+def attention_key_mass(q, k, ids_q, ids_k, m, l, seg, w, mass, accumulate=False, scale=None, kw=None):
     """mass[b, h, g] (+)= sum over the real queries i (weight w[b, i]) and the keys j of segment g of the attention probability
     exp(s_ij - (m_i + ln l_i)) (include/emdr2_ops.h: emdr2_attention_key_mass).  q bf16 [b, sq <= 128, heads, 64] (a strided view) over dense
     ids_q [b, sq]; k [b, sk, heads, 64] over dense ids_k [b, sk], or [rows, heads, 64] over a PackedSeqs; m, l fp32 [b, heads, sq] of the
     forward over the same operands; seg int32 [b, n_seg + 1] key offsets inside each sequence; w fp32 [b, sq] or None (weight 1);
-    mass fp32 [b, heads, n_seg].  Returns mass."""
+    mass fp32 [b, heads, n_seg].  `kw` fp32 [heads, ld] (ld >= the key rows: b * sk dense, the PackedSeqs' rows packed): every p_ij is
+    multiplied by kw[h, key row] (emdr2_attention_key_mass_weighted; finite for every key inside a segment).  Returns mass."""
     _check_bf16(q, k)
     iq, _, q_sb, q_ss, q_sn, b, sq = _attn_side(q, ids_q)
     ik, cu_k, k_sb, k_ss, k_sn, bk, sk = _attn_side(k, ids_k)
@@ -1037,6 +1063,17 @@ def attention_key_mass(q, k, ids_q, ids_k, m, l, seg, w, mass, accumulate=False,
                          (mass, torch.float32, (b, heads, n_seg))) + (((w, torch.float32, (b, sq)),) if w is not None else ()):
         if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
             raise ValueError("attention_key_mass: expected a contiguous CUDA %s tensor of shape %s, got %s %s" % (dt, shape, t.dtype, tuple(t.shape)))
+    if kw is not None:
+        key_rows = k.shape[0] if cu_k is not None else b * sk
+        if kw.dtype != torch.float32 or kw.dim() != 2 or kw.shape[0] != heads or kw.shape[1] < key_rows or not kw.is_contiguous() or not kw.is_cuda:
+            raise ValueError("attention_key_mass: kw must be a contiguous CUDA fp32 [heads = %d, >= %d key rows] tensor, got %s %s"
+                             % (heads, key_rows, kw.dtype, tuple(kw.shape)))
+        _native.check(_lib().emdr2_attention_key_mass_weighted(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, iq.data_ptr(),
+                                                               ik.data_ptr(), _ptr(cu_k), m.data_ptr(), l.data_ptr(), seg.data_ptr(), _ptr(w),
+                                                               kw.data_ptr(), kw.shape[1], mass.data_ptr(), b, heads, sq, sk, n_seg, hn,
+                                                               1.0 / math.sqrt(hn) if scale is None else scale, int(bool(accumulate)), _sp()),
+                      "attention_key_mass_weighted")
+        return mass
     _native.check(_lib().emdr2_attention_key_mass(q.data_ptr(), q_sb, q_ss, q_sn, k.data_ptr(), k_sb, k_ss, k_sn, iq.data_ptr(), ik.data_ptr(),
                                                   _ptr(cu_k), m.data_ptr(), l.data_ptr(), seg.data_ptr(), _ptr(w), mass.data_ptr(), b, heads, sq,
                                                   sk, n_seg, hn, 1.0 / math.sqrt(hn) if scale is None else scale, int(bool(accumulate)), _sp()),
@@ -1051,25 +1088,48 @@ class _AttentionMass(object):
     PackedSeqs the decoder passes down), so the decoder's self-attention, the encoder and the one-context pass never match.  A forward
     that consumes a stash (the re-run of a checkpointed layer inside the backward) launches nothing and records nothing, and the model
     disarms the collector when the decoder's forward returns, before any backward.  Unarmed: one attribute test per attention call.
-    `keep` (tests only): the operands of each recorded call are retained in `calls`."""
+    `value_norms` (--attention-mass-value-norms, set at `arm`): every probability is weighted by the norm of its key's value vector,
+    ||v_j||_2 per head (`head_row_norms` of the launch's v view, passed as `kw`).  The norms are cached for as long as the collector is
+    armed, keyed by the identity of the KV tensor (a reference to it is kept, so the identity cannot be reused): greedy decoding under
+    `cross_kv_cache` computes them once per layer and batch, not once per generated token; training once per layer and group.  `disarm`
+    drops the cache.  `norm_launches` counts the norm kernels launched since the last `arm`.
+    `keep` (tests only): the operands of each recorded call are retained in `calls` (v and kw too when the norms are on)."""
 
     def __init__(self):
         self.ids_k = self.seg = self.w = self.out = None
         self.keep, self.calls, self.count = False, [], 0
+        self.value_norms, self.norms, self.norm_launches = False, {}, 0
 
-    def arm(self, ids_k, seg, w, out):
+    def arm(self, ids_k, seg, w, out, value_norms=False):
         self.ids_k, self.seg, self.w, self.out, self.count = ids_k, seg, w, out, 0
+        self.value_norms, self.norms, self.norm_launches = bool(value_norms), {}, 0
 
     def disarm(self):
         self.ids_k = self.seg = self.w = self.out = None
+        self.value_norms, self.norms = False, {}
 
-    def record(self, L, q, k, m, l):
+    def _norms_of(self, kvsrc, v):
+        hit = self.norms.get(id(kvsrc))
+        if hit is None:
+            hit = self.norms[id(kvsrc)] = (kvsrc, head_row_norms(v))
+            self.norm_launches += 1
+        return hit[1]
+
+    def record(self, L, q, k, m, l, v=None, kvsrc=None):
         if not L.fused or L.pq:
             raise ValueError("the reader attention mass needs the fused attention kernels (head dim 64, dense decoder queries)")
-        attention_key_mass(q, k, L.ids_q, L.ids_k, m, l, self.seg, self.w, self.out, accumulate=self.count > 0, scale=L.scale)
+        kw = None
+        if self.value_norms:
+            if v is None:
+                raise ValueError("the value-norm weighted attention mass needs the launch's v view")
+            kw = self._norms_of(kvsrc if kvsrc is not None else v, v)
+        attention_key_mass(q, k, L.ids_q, L.ids_k, m, l, self.seg, self.w, self.out, accumulate=self.count > 0, scale=L.scale, kw=kw)
         self.count += 1
         if self.keep:
-            self.calls.append(dict(q=q.detach(), k=k.detach(), ids_q=L.ids_q, ids_k=L.ids_k, m=m, l=l, seg=self.seg, w=None if self.w is None else self.w.clone()))
+            call = dict(q=q.detach(), k=k.detach(), ids_q=L.ids_q, ids_k=L.ids_k, m=m, l=l, seg=self.seg, w=None if self.w is None else self.w.clone())
+            if kw is not None:
+                call.update(v=v.detach(), kw=kw)
+            self.calls.append(call)
 
 
 ATTN_MASS = _AttentionMass()
@@ -1108,7 +1168,7 @@ class AttentionCoreFn(torch.autograd.Function):
         else:
             _composed_attention_fwd(L, q, k, v, ctxo, m, l, drop_p, seed)
         if ATTN_MASS.ids_k is not None and ids_k is ATTN_MASS.ids_k:                      # the armed cross-attention, right behind its launch
-            ATTN_MASS.record(L, q, k, m, l)
+            ATTN_MASS.record(L, q, k, m, l, v, kvsrc)
         ctx.save_for_backward(qsrc, kvsrc, m, l, ctxo)
         if stash_key and ATTN_STASH.mode == 'store':
             ATTN_STASH.store[stash_key] = (ctxo, m, l)

@@ -47,7 +47,7 @@ class SampleOrGreedySearch(object):
         # --reader-attention-mass (incremental form): every step's cross-attention (one query per hypothesis over the dense keys of its K
         # passages) adds into one buffer, with weight 1 for hypotheses that had not emitted [EOS] before the step
         emdr2 = getattr(model, "module", model)
-        collect = self.incremental and getattr(emdr2, "reader_attention_mass", False)
+        collect = self.incremental and (getattr(emdr2, "reader_attention_mass", False) or getattr(emdr2, "retriever_distill_attention", False))
         mass = step_w = None
         with torch.no_grad(), cross_kv_cache(model), _mass_disarmed_on_exit():
             state = None

@@ -67,7 +67,12 @@ def model_provider(args=None, bert_tokenizer=None, t5_tokenizer=None, arena=None
                        no_query_embedder_training=args.no_query_embedder_training,
                        no_context_embedder_training=args.no_context_embedder_training,
                        context_embeddings_from_index=bool(getattr(args, "context_embeddings_from_index", False)),
-                       reader_attention_mass=bool(getattr(args, "reader_attention_mass", False)))
+                       reader_attention_mass=bool(getattr(args, "reader_attention_mass", False)),
+                       retriever_distill_attention=bool(getattr(args, "retriever_distill_attention", False)),
+                       attention_mass_value_norms=bool(getattr(args, "attention_mass_value_norms", False)))
+    if model.retriever_distill_attention:                       # (without the flag a run prints what it always printed)
+        print_rank_0('retriever loss: KL(reader attention mass{} || prior), no one-context pass (--retriever-distill-attention)'.format(
+            ', value-norm weighted' if model.attention_mass_value_norms else ''))
     model.index_writeback = bool(getattr(args, "index_writeback", False))
     if getattr(args, "retrieval_answer_hits", False):
         from emdr2_amd.tasks.openqa.e2eqa.answer_hits import AnswerHitTracker, report_ranks

@@ -180,6 +180,33 @@ int emdr2_attention_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t 
                              const int32_t *seg, const float *w, float *mass, int batch, int heads, int sq, int max_sk, int n_seg, int head_dim,
                              float scale, int accumulate, void *stream);
 
+/* The same with a weight per (head, key) -- value-norm weighted attention mass, kw = ||v_j||_2 from emdr2_head_row_norms:
+ *     mass[b, h, g] (+)= sum_{i : ids_q[b, i] != 0} w[b, i] sum_{j in seg g} p_ij kw[h * kw_ld + krow0(b) + j]
+ * krow0(b) + j is the row the kernel indexes ids_k with: b * sk + j for dense keys, cu_k[b] + j for packed ones; kw is fp32 [heads, kw_ld]
+ * (dense keys: kw_ld >= batch * max_sk).  Same grid, same order of additions as the unweighted entry (one more fp32 multiplication per
+ * term): kw == 1.0 gives its bits.  Only kw of keys INSIDE a segment is read (the load is clamped to the segment like the key-row load,
+ * 4-byte loads, no alignment beyond 4 bytes); kw elsewhere may hold anything, NaN included.
+ * Contract: kw is finite for every key inside a segment, pad keys (token id 0) included -- a masked key's p underflows to 0, and
+ * 0 * NaN would not be 0.
+ * Return codes of the unweighted entry, plus -1: kw null or not 4-byte aligned; -4: kw_ld < 1, or dense keys and kw_ld < batch * max_sk. */
+int emdr2_attention_key_mass_weighted(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss,
+                                      int64_t k_sn, const int64_t *ids_q, const int64_t *ids_k, const int32_t *cu_k, const float *m,
+                                      const float *l, const int32_t *seg, const float *w, const float *kw, int64_t kw_ld, float *mass, int batch,
+                                      int heads, int sq, int max_sk, int n_seg, int head_dim, float scale, int accumulate, void *stream);
+
+/* norm[h * ld + r] = sqrt(sum_{d < 64} x[r, h, d]^2) in fp32 (csrc/attention_mass.hip): x bf16 as a strided view, row r = b * sk + s at
+ * element offset b * x_sb + s * x_ss, head stride x_sn -- the (k_sb, k_ss, k_sn) conventions above, so kv[:, :, 1] of the packed KV
+ * projection is passed as it is; a packed operand is batch = 1, sk = rows.  norm is fp32 [heads, ld], ld >= batch * sk, head-major (the
+ * layout kw above wants).  Order of additions: 8 lanes x 16 bytes per (row, head); a lane adds its 8 exact squares in order (7 additions),
+ * a 3-level xor butterfly (3), one square root.  No atomics: a repeated call gives identical bits.
+ * Range: the relative accuracy (10 2^-24 on the sum, one ulp on the root) holds while the sum of squares is a normal fp32 number that
+ * does not overflow, i.e. for rows with 2^-59 <= max |x| and every |x| <= 2^60; smaller rows are right to an ABSOLUTE 2^-60 (squares
+ * below 2^-126 may be flushed), an all-zero row gives exactly 0.
+ * -1: null x or norm, batch / sk / heads < 1, x not 16-byte or norm not 4-byte aligned; -4: head_dim != 64, strides that are no multiple
+ * of 8 elements, ld < batch * sk. */
+int emdr2_head_row_norms(const void *x, int64_t x_sb, int64_t x_ss, int64_t x_sn, float *norm, int64_t ld, int batch, int sk, int heads,
+                         int head_dim, void *stream);
+
 /* dpre = dact * gelu'(pre), exact-erf GELU (transformer.py:80,103-104; the tanh fusion of fused_bias_gelu.py is off in all scripts) */
 int emdr2_gelu_bwd(const void *pre, const void *dact, void *dpre, int64_t n, void *stream);
 

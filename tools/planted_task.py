@@ -369,13 +369,34 @@ if __name__ == "__main__":
     ap.add_argument("--writeback-arms", metavar="JSONL", default=None,
                     help="instead: two runs WITHOUT the refresher from the same prepared world, the second with --index-writeback; one JSON "
                          "line per arm (recall@1/5/20 before and after, EM) is also appended to this file")
+    ap.add_argument("--retriever-distill-attention", metavar="JSONL", default=None,
+                    help="instead: from the same prepared world, a start arm (1 step, no retriever update: where recall, EM and the read mass "
+                         "stand before training), the EMDR2 arm and the --retriever-distill-attention arm, all with --reader-attention-mass "
+                         "--retrieval-answer-hits so that every line carries read_mass_gold; one JSON line per arm is also appended to this file")
+    ap.add_argument("--attention-mass-value-norms", action="store_true",
+                    help="with --retriever-distill-attention: a fourth arm that distils from the value-norm weighted mass")
     o = ap.parse_args()
+    if o.attention_mass_value_norms and not o.retriever_distill_attention:
+        ap.error("--attention-mass-value-norms goes with --retriever-distill-attention")
     w = prepare(o.dir, o.docs, o.topk, 0, o.retriever_steps, o.reader_steps)
     if o.writeback_arms:
         for arm, extra in (("no refresher", []), ("no refresher, --index-writeback", ["--index-writeback", "--disable-retriever-dropout"])):
             res = dict(train(o.dir, w, o.steps, True, o.batch, o.lr, extra=extra, refresher=False), arm=arm)
             print(json.dumps(res), flush=True)
             with open(o.writeback_arms, "a") as fh:
+                fh.write(json.dumps(res) + "\n")
+        sys.exit(0)
+    if o.retriever_distill_attention:
+        read = ["--reader-attention-mass", "--retrieval-answer-hits"]
+        arms = [("start: 1 step, no retriever update", 1, False, read), ("EMDR2 marginal", o.steps, True, read),
+                ("--retriever-distill-attention", o.steps, True, read + ["--retriever-distill-attention"])]
+        if o.attention_mass_value_norms:
+            arms.append(("--retriever-distill-attention --attention-mass-value-norms", o.steps, True,
+                         read + ["--retriever-distill-attention", "--attention-mass-value-norms"]))
+        for arm, steps, upd, extra in arms:
+            res = dict(train(o.dir, w, steps, upd, o.batch, o.lr, extra=extra), arm=arm)
+            print(json.dumps(res), flush=True)
+            with open(o.retriever_distill_attention, "a") as fh:
                 fh.write(json.dumps(res) + "\n")
         sys.exit(0)
     for upd in ((True, False) if o.both else (not o.no_update_retriever,)):
