@@ -151,6 +151,16 @@ SIGNATURES["emdr2_retriever_prior_h16_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _
 SIGNATURES["emdr2_marginal_fwd"] = (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp])
 SIGNATURES["emdr2_marginal_bwd"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp])
 SIGNATURES["emdr2_lse_combine"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp])
+# the ordered ("deterministic gradients") entries of include/emdr2_ops.h: each mirrors the entry named behind it, plus ws, ws_bytes
+_psz = ctypes.POINTER(_sz)
+SIGNATURES["emdr2_gemm_tn_ordered_ws_bytes"] = (_i32, [_i32, _i32, _i32, _i32, _psz])
+SIGNATURES["emdr2_gemm_tn_bf16_ordered"] = (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp])     # emdr2_gemm_tn_bf16
+SIGNATURES["emdr2_layernorm_bwd_ordered_ws_bytes"] = (_i32, [_i64, _i32, _psz])
+SIGNATURES["emdr2_layernorm_bwd_ordered"] = (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _u32, _vp, _sz,
+                                                      _vp])                                                               # emdr2_layernorm_bwd_mask
+SIGNATURES["emdr2_embedding_bwd_ordered_ws_bytes"] = (_i32, [_i64, _i32, _i32, _i32, _i32, _psz])
+SIGNATURES["emdr2_embedding_bwd_ordered"] = (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _u32, _vp, _sz,
+                                                      _vp])                                                               # emdr2_embedding_packed_bwd
 SIGNATURES["emdr2_ops_set_timing"] = (_i32, [_i32])
 SIGNATURES["emdr2_ops_timing_collect"] = (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), _i32])
 

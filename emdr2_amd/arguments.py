@@ -221,6 +221,12 @@ def get_parser():
                         'decoder layer and group, once per batch under greedy decoding).  A choice of what "read" means, wherever the mass is '
                         'collected: the log fields of --reader-attention-mass and the target of --retriever-distill-attention change together.  '
                         'Needs one of those two flags')
+    g.add_argument('--deterministic-gradients', action='store_true',
+                   help='(not in the reference) bit-reproducible parameter gradients: the weight-gradient GEMMs, the LayerNorm gain / bias '
+                        'gradients and the embedding backward sum in a fixed order through a workspace (the *_ordered entries of '
+                        'include/emdr2_ops.h) instead of fp32 atomics, so the same step from the same state gives the same bits.  Not '
+                        'promised: equality with a run without the flag, across world sizes or across shapes that choose another split.  '
+                        'Not with --fp32-validation.  Off: every launch is what it was')
     return p
 
 
@@ -281,6 +287,9 @@ def parse_args(argv=None):
     if args.attention_mass_value_norms and not (args.reader_attention_mass or args.retriever_distill_attention):
         raise ValueError("--attention-mass-value-norms changes what the attention mass holds: it needs --reader-attention-mass or "
                          "--retriever-distill-attention, which collect it")
+    if args.deterministic_gradients and args.fp32_validation:
+        raise ValueError("--deterministic-gradients orders the sums of the bf16 training path: it does not run with --fp32-validation "
+                         "(the fp32 validation kernels keep their atomics)")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

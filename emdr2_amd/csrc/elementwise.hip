@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rng.h"
+#include "ordered_sum.h"
 
 namespace {
 
@@ -185,7 +186,10 @@ __global__ void __launch_bounds__(256) layernorm_fwd768_kernel(const uint16_t *x
 // dx = rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*gamma ; optional residual-branch gradient added on the way out.
 // Block = 32 rows: phase 1 one wave per row computes the two row means into LDS; phase 2 every thread owns columns tid, tid+256, ...
 // for all 32 rows (dgamma / dbeta partials stay in registers; one global atomicAdd per column per block).
+// ORD (emdr2_layernorm_bwd_ordered): no atomics -- workgroup b stores its 2 x H column partials into slot b of dgamma (a workspace,
+// [gridDim.x][2][H], dbeta unused); ordered_slot_sum adds the slots.  dx is the same instruction sequence in both instances.
 #define LN_ROWS 32
+template <bool ORD>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const uint16_t *dy, const uint16_t *x, const float *gamma, const float *mean,
                                                             const float *rstd, const uint16_t *dres, uint16_t *dx, float *dgamma,
                                                             float *dbeta, long long rows, int H, int rows_per_block)
@@ -221,8 +225,13 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const uint16_t *dy, 
             dx[row * H + c] = f2bf(v);
             ag += d * xh; ab += d;
         }
-        atomicAdd(&dgamma[c], ag);
-        atomicAdd(&dbeta[c], ab);
+        if (ORD) {
+            dgamma[((long long)blockIdx.x * 2) * H + c] = ag;
+            dgamma[((long long)blockIdx.x * 2 + 1) * H + c] = ab;
+        } else {
+            atomicAdd(&dgamma[c], ag);
+            atomicAdd(&dbeta[c], ab);
+        }
     }
 }
 
@@ -231,7 +240,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const uint16_t *dy, 
 // DMASK: also write dx o keep(seed, row, col) / (1 - p) -- the bias-dropout-add below this LayerNorm wants exactly that tensor as the operand of
 // its two backward GEMMs (they read operands by LDS-DMA, so the mask cannot ride in their loads), and r03 made it with a kernel of its own
 // (read dx, write the masked copy: 21 ms of the step).  Same bits as that kernel: the mask is applied to the bf16-ROUNDED dx.
-template <bool DMASK>
+// ORD: as in layernorm_bwd_kernel -- slot blockIdx.x of dgamma ([gridDim.x][2][768]) takes the workgroup's column partials.
+template <bool DMASK, bool ORD = false>
 __global__ void __launch_bounds__(256) layernorm_bwd768_kernel(const uint16_t *dy, const uint16_t *x, const float *gamma, const float *mean,
                                                                const float *rstd, const uint16_t *dres, uint16_t *dx, float *dgamma, float *dbeta,
                                                                long long rows, uint16_t *dmask, float drop_p, uint32_t seed)
@@ -310,8 +320,14 @@ __global__ void __launch_bounds__(256) layernorm_bwd768_kernel(const uint16_t *d
         }
     __syncthreads();
     for (int c = threadIdx.x; c < 768; c += 256) {
-        atomicAdd(&dgamma[c], red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-        atomicAdd(&dbeta[c], red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+        const float a = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c], b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+        if (ORD) {
+            dgamma[(long long)blockIdx.x * 1536 + c] = a;
+            dgamma[(long long)blockIdx.x * 1536 + 768 + c] = b;
+        } else {
+            atomicAdd(&dgamma[c], a);
+            atomicAdd(&dbeta[c], b);
+        }
     }
 }
 
@@ -602,6 +618,9 @@ __global__ void __launch_bounds__(256) embedding_bwd_kernel(const long long *ids
 // serialises thousands of adds on a few addresses.  One thread owns (position, column) for ONE SLICE of the batch (gridDim.z slices: a
 // single walker per (position, column) made 3,200 dependent loads in a row -- 2.6 ms at the reader's shape), walks its sequences, and adds
 // its sums with one atomic per table entry: S x H x slices atomics instead of one per token.
+// ORD (emdr2_embedding_bwd_ordered): no atomics -- slice z = blockIdx.z stores its sums, zeros included, into workspaces passed as dP
+// ([slices][S][H]) and dT ([S][slices][n_types][H]); ordered_slot_sum adds them (position rows: slice order; type rows: slot pos * slices + z).
+template <bool ORD>
 __global__ void __launch_bounds__(256) embedding_bwd_pos_kernel(const long long *types, const uint16_t *dout, float *dP, float *dT, long long tokens,
                                                                 int S, int H, int n_types, float drop_p, uint32_t seed, const int *cu, int nseq)
 {
@@ -628,12 +647,134 @@ __global__ void __launch_bounds__(256) embedding_bwd_pos_kernel(const long long 
             for (int k = 0; k < 4; ++k) at[k] += (ty == k) ? g : 0.f;
         }
     }
+    if (ORD) {
+        dP[((long long)blockIdx.z * S + pos) * H + i] = ap;
+        if (types) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n_types) dT[(((long long)pos * gridDim.z + blockIdx.z) * n_types + k) * H + i] = at[k];
+        }
+        return;
+    }
     if (ap != 0.f) atomicAdd(&dP[(long long)pos * H + i], ap);
     if (types) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < n_types && at[k] != 0.f) atomicAdd(&dT[(long long)k * H + i], at[k]);
     }
+}
+
+// ---- ordered word-embedding rows (emdr2_embedding_bwd_ordered): store-and-sum through an inverted index, no atomics ---------------------
+// `order` = the stable sort of the token indices by id: position q of the sorted sequence holds token order[q], ids[order[q]] ascending, equal
+// ids in ascending token index.  The contribution rows are the rows of dout themselves (the dropout mask is re-applied on the way in).
+// ORDER.  The sorted sequence is cut at the multiples of EMB_CHUNK.  A run of equal ids inside one chunk is summed sequentially in sorted
+// order, from +0.0.  A run that lies inside one chunk is added onto dW[id] there; a run that crosses a chunk boundary leaves one piece per
+// chunk (slot 0 of the chunk: its first run, slot 1: its last run when that is another one) and the finish kernel adds the pieces in
+// ascending chunk order, ((piece_0 + piece_1) + piece_2) + ..., then adds the total onto dW[id] once.  A total of exactly zero is not added,
+// and a vocabulary row without tokens is never touched.
+#define EMB_CHUNK 128
+template <bool VEC>
+__global__ void __launch_bounds__(128) embedding_bwd_words_ordered_kernel(const long long *ids, const long long *order, const uint16_t *dout, float *dW,
+                                                                          float *part, long long tokens, int H, float drop_p, uint32_t seed)
+{
+    constexpr int NV = VEC ? 8 : 1;
+    __shared__ long long s_tok[EMB_CHUNK], s_id[EMB_CHUNK + 2];          // s_id[0] / s_id[n + 1]: the neighbours' ids, -1 = none (ids are >= 0)
+    const int tid = threadIdx.x;
+    const long long q0 = (long long)blockIdx.x * EMB_CHUNK;
+    const int n = (int)(tokens - q0 < EMB_CHUNK ? tokens - q0 : EMB_CHUNK);
+    if (tid < n) { const long long t = order[q0 + tid]; s_tok[tid] = t; s_id[1 + tid] = ids[t]; }
+    if (tid == 0) s_id[0] = q0 > 0 ? ids[order[q0 - 1]] : -1;
+    if (tid == 1) s_id[n + 1] = q0 + n < tokens ? ids[order[q0 + n]] : -1;
+    __syncthreads();
+    const int col = (blockIdx.y * 128 + tid) * NV;
+    if (col >= H) return;
+    const uint32_t thr = emdr2_drop_thr(drop_p);
+    const float ik = drop_p > 0.f ? emdr2_keep_scale(drop_p) : 1.f;
+    float acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.f;
+    auto flush = [&](long long id, bool piece, int slot) {
+        if (piece) {
+            float *o = part + ((long long)blockIdx.x * 2 + slot) * H + col;
+            if (VEC) { *(float4 *)o = make_float4(acc[0], acc[1], acc[2], acc[3]); *(float4 *)(o + 4) = make_float4(acc[4 % NV], acc[5 % NV], acc[6 % NV], acc[7 % NV]); }
+            else o[0] = acc[0];
+        } else {
+            float *o = dW + id * H + col;
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+                if (acc[v] != 0.f) o[v] += acc[v];
+        }
+    };
+    long long run = s_id[1];
+    bool first = true;
+    for (int q = 0; q < n; ++q) {
+        const long long id = s_id[1 + q];
+        if (id != run) {                                              // workgroup-uniform
+            flush(run, first && s_id[0] == run, 0);
+            first = false;
+            run = id;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) acc[v] = 0.f;
+        }
+        const long long t = s_tok[q];
+        const uint32_t rh = emdr2_row_hash(seed, (unsigned long long)t);
+        if (VEC) {
+            const uint4 w4 = *(const uint4 *)(dout + t * H + col);
+            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float lo = bf2f((uint16_t)(w[j] & 0xffff)), hi = bf2f((uint16_t)(w[j] >> 16));
+                if (drop_p > 0.f) {
+                    const uint32_t b = emdr2_pair_bits(rh, (uint32_t)(col + 2 * j));
+                    lo = (b & 0xffffu) >= thr ? lo * ik : 0.f;
+                    hi = (b >> 16) >= thr ? hi * ik : 0.f;
+                }
+                acc[(2 * j) % NV] += lo; acc[(2 * j + 1) % NV] += hi;
+            }
+        } else {
+            float g = bf2f(dout[t * H + col]);
+            if (drop_p > 0.f) g = emdr2_keep(rh, (uint32_t)col, thr) ? g * ik : 0.f;
+            acc[0] += g;
+        }
+    }
+    const bool before = first && s_id[0] == run, after = s_id[n + 1] == run;
+    flush(run, before || after, first ? 0 : 1);
+}
+
+// one workgroup per chunk; it acts when a run that crosses chunk boundaries STARTS in its chunk
+template <bool VEC>
+__global__ void __launch_bounds__(128) embedding_bwd_words_finish_kernel(const long long *ids, const long long *order, const float *part, float *dW,
+                                                                         long long tokens, int H)
+{
+    constexpr int NV = VEC ? 4 : 1;
+    const long long k = blockIdx.x, q0 = k * EMB_CHUNK, q1 = q0 + EMB_CHUNK;
+    if (q1 >= tokens) return;                                         // the last chunk: nothing continues
+    const long long id = ids[order[q1 - 1]];
+    if (ids[order[q1]] != id) return;                                 // the chunk's last run ends with it
+    const bool single = ids[order[q0]] == id;                         // the chunk is one run
+    if (single && q0 > 0 && ids[order[q0 - 1]] == id) return;         // a middle piece: the chunk where the run starts does the sum
+    long long lo = q1 + 1, hi = tokens;                               // end of the run: the first position past q1 with another id
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (ids[order[mid]] == id) lo = mid + 1; else hi = mid;
+    }
+    const long long ke = (lo - 1) / EMB_CHUNK;                        // the chunk of the run's last token; pieces k + 1 .. ke sit in slot 0
+    const int col = (blockIdx.y * 128 + threadIdx.x) * NV;
+    if (col >= H) return;
+    float t[NV];
+    const float *p0 = part + (k * 2 + (single ? 0 : 1)) * H + col;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) t[v] = p0[v];
+#pragma unroll 4
+    for (long long kk = k + 1; kk <= ke; ++kk) {
+        const float *pk = part + kk * 2 * H + col;
+        if (VEC) { const float4 a = *(const float4 *)pk; t[0] += a.x; t[1 % NV] += a.y; t[2 % NV] += a.z; t[3 % NV] += a.w; }
+        else t[0] += pk[0];
+    }
+    float *o = dW + id * H + col;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+        if (t[v] != 0.f) o[v] += t[v];
 }
 
 // ---- dropout mask of a site re-applied to a contiguous bf16 tensor (backward of the fused bias-dropout-add epilogue) --------------
@@ -845,7 +986,7 @@ extern "C" int emdr2_layernorm_bwd(const void *dy, const void *x, const float *g
         return LAUNCH_OK();
     }
     const int rpb = LN_ROWS;
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(layernorm_bwd_kernel<false>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)dy, (const uint16_t *)x, gamma, mean, rstd, (const uint16_t *)dres, (uint16_t *)dx, dgamma, dbeta,
                        (long long)rows, H, rpb);
     return LAUNCH_OK();
@@ -952,7 +1093,7 @@ extern "C" int emdr2_embedding_bwd(const int64_t *ids, const int64_t *types, con
     if (tokens % S || (types && (n_types < 1 || n_types > 4))) return -4;
     hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)tokens), dim3(256), 0, (hipStream_t)stream, (const long long *)ids, (const long long *)types,
                        (const uint16_t *)dout, dW, dP, dT, (long long)tokens, S, H, drop_p, seed);
-    hipLaunchKernelGGL(embedding_bwd_pos_kernel, dim3((unsigned)S, (unsigned)((H + 255) / 256), pos_slices(tokens / S)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(embedding_bwd_pos_kernel<false>, dim3((unsigned)S, (unsigned)((H + 255) / 256), pos_slices(tokens / S)), dim3(256), 0, (hipStream_t)stream,
                        (const long long *)types, (const uint16_t *)dout, dP, dT, (long long)tokens, S, H, n_types, drop_p, seed, (const int *)nullptr, 0);
     return LAUNCH_OK();
 }
@@ -965,8 +1106,112 @@ extern "C" int emdr2_embedding_packed_bwd(const int64_t *ids, const int64_t *typ
     // word rows: the same atomic scatter (a tail row carries a zero gradient and is skipped like any zero row)
     hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const long long *)ids, (const long long *)types,
                        (const uint16_t *)dout, dW, dP, dT, (long long)rows, S, H, drop_p, seed);
-    hipLaunchKernelGGL(embedding_bwd_pos_kernel, dim3((unsigned)S, (unsigned)((H + 255) / 256), pos_slices(nseq)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(embedding_bwd_pos_kernel<false>, dim3((unsigned)S, (unsigned)((H + 255) / 256), pos_slices(nseq)), dim3(256), 0, (hipStream_t)stream,
                        (const long long *)types, (const uint16_t *)dout, dP, dT, (long long)rows, S, H, n_types, drop_p, seed, (const int *)cu, nseq);
+    return LAUNCH_OK();
+}
+
+// ---- ordered ("deterministic gradients") forms: include/emdr2_ops.h ---------------------------------------------------------------------
+static inline size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
+static long long ln768_blocks(long long rows) { const long long b = (rows + 7) / 8; return b > 2048 ? 2048 : b; }
+
+extern "C" int emdr2_layernorm_bwd_ordered_ws_bytes(int64_t rows, int H, size_t *bytes)
+{
+    if (!bytes || rows < 1 || H < 1 || H > 8192) return -1;
+    *bytes = (size_t)((rows + LN_ROWS - 1) / LN_ROWS) * 2 * H * sizeof(float);     // the generic kernel's slots: never fewer than the 768 kernel's
+    if (H == 768 && (size_t)ln768_blocks(rows) * 1536 * sizeof(float) > *bytes) *bytes = (size_t)ln768_blocks(rows) * 1536 * sizeof(float);
+    return 0;
+}
+
+// ORDER.  H == 768, aligned: gridDim = min(ceil(rows / 8), 2048) workgroups, a function of `rows` alone; wave w of workgroup b takes the row
+// pairs 4 b + w, + 4 gridDim, ... in ascending order, each half-wave one row of the pair; a column's partial is (half 0 + half 1), then
+// ((wave 0 + wave 1) + wave 2) + wave 3, stored in slot b.  Otherwise: workgroup b owns rows [32 b, 32 b + 32), summed in ascending order,
+// slot b.  Both: dgamma[c] = dgamma[c] + total of the slots as ordered_slot_sum<., 32> adds them (ordered_sum.h), likewise dbeta.
+extern "C" int emdr2_layernorm_bwd_ordered(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd, const void *dres, void *dx,
+                                           float *dgamma, float *dbeta, int64_t rows, int H, void *dmask, float drop_p, uint32_t seed, void *ws,
+                                           size_t ws_bytes, void *stream)
+{
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !ws || ((uintptr_t)ws & 15) || rows < 1 || H < 1 || H > 8192) return -1;
+    if (dmask && (drop_p <= 0.f || drop_p >= 1.f)) return -1;
+    const bool al = !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dres | (uintptr_t)gamma | (uintptr_t)dmask) & 15);
+    const bool k768 = H == 768 && al;
+    if (dmask && !k768) return -4;
+    const long long slots = k768 ? ln768_blocks(rows) : (rows + LN_ROWS - 1) / LN_ROWS;
+    if (slots > 0x7fffffffll) return -4;
+    if (ws_bytes < (size_t)slots * 2 * H * sizeof(float)) return -2;
+    float *part = (float *)ws;
+    if (k768) {
+        if (dmask)
+            hipLaunchKernelGGL((layernorm_bwd768_kernel<true, true>), dim3((unsigned)slots), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dy,
+                               (const uint16_t *)x, gamma, mean, rstd, (const uint16_t *)dres, (uint16_t *)dx, part, (float *)nullptr, (long long)rows,
+                               (uint16_t *)dmask, drop_p, seed);
+        else
+            hipLaunchKernelGGL((layernorm_bwd768_kernel<false, true>), dim3((unsigned)slots), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dy,
+                               (const uint16_t *)x, gamma, mean, rstd, (const uint16_t *)dres, (uint16_t *)dx, part, (float *)nullptr, (long long)rows,
+                               (uint16_t *)nullptr, 0.f, 0u);
+    } else {
+        hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3((unsigned)slots), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dy,
+                           (const uint16_t *)x, gamma, mean, rstd, (const uint16_t *)dres, (uint16_t *)dx, part, (float *)nullptr, (long long)rows, H,
+                           LN_ROWS);
+    }
+    ordered_slot_sum(part, 2ll * H, (int)slots, dgamma, H, H, 1, true, false, (hipStream_t)stream);
+    ordered_slot_sum(part + H, 2ll * H, (int)slots, dbeta, H, H, 1, true, false, (hipStream_t)stream);
+    return LAUNCH_OK();
+}
+
+static size_t emb_ordered_floats(long long tokens, long long nseq, int S, int H, int n_types, size_t *pos_off, size_t *typ_off)
+{
+    const size_t chunks = (size_t)((tokens + EMB_CHUNK - 1) / EMB_CHUNK), slices = pos_slices(nseq);
+    const size_t words = round4(chunks * 2 * H), pos = round4(slices * S * H), typ = round4((size_t)S * slices * n_types * H);
+    if (pos_off) *pos_off = words;
+    if (typ_off) *typ_off = words + pos;
+    return words + pos + typ;
+}
+
+extern "C" int emdr2_embedding_bwd_ordered_ws_bytes(int64_t tokens, int nseq, int S, int H, int n_types, size_t *bytes)
+{
+    if (!bytes || tokens < 1 || nseq < 1 || S < 1 || H < 1 || n_types < 0 || n_types > 4) return -1;
+    *bytes = emb_ordered_floats(tokens, nseq, S, H, n_types, nullptr, nullptr) * sizeof(float);
+    return 0;
+}
+
+// The order of the word rows stands at embedding_bwd_words_ordered_kernel.  Position rows: slice z of pos_slices(number of sequences) walks the
+// sequences z, z + slices, ... in ascending order; dP[pos] += ((slice 0 + slice 1) + ...).  Type rows: the same per-(position, slice) sums,
+// slot = pos * slices + z, added as ordered_slot_sum<., 32> adds slots.  Totals of exactly zero are not added (positions nobody reaches).
+extern "C" int emdr2_embedding_bwd_ordered(const int64_t *ids, const int64_t *types, const int32_t *cu, int nseq, const int64_t *order, const void *dout,
+                                           float *dW, float *dP, float *dT, int64_t tokens, int S, int H, int n_types, float drop_p, uint32_t seed, void *ws,
+                                           size_t ws_bytes, void *stream)
+{
+    if (!ids || !order || !dout || !dW || !dP || !ws || ((uintptr_t)ws & 15) || tokens < 1 || S < 1 || H < 1 || (types && !dT) || (cu && nseq < 1) ||
+        drop_p < 0.f || drop_p >= 1.f)
+        return -1;
+    if ((!cu && tokens % S) || (types && (n_types < 1 || n_types > 4))) return -4;
+    const long long nb = cu ? nseq : tokens / S;
+    const int nt = types ? n_types : 0;
+    size_t pos_off, typ_off;
+    if (ws_bytes < emb_ordered_floats(tokens, nb, S, H, nt, &pos_off, &typ_off) * sizeof(float)) return -2;
+    float *part_w = (float *)ws, *part_p = part_w + pos_off, *part_t = part_w + typ_off;
+    const long long chunks = (tokens + EMB_CHUNK - 1) / EMB_CHUNK;
+    if (chunks > 0x7fffffffll) return -4;
+    const bool vec = !(H & 7) && !(((uintptr_t)dout | (uintptr_t)dW) & 15);
+    const int per = vec ? 128 * 8 : 128;
+    const dim3 grid((unsigned)chunks, (unsigned)((H + per - 1) / per));
+    if (vec) {
+        hipLaunchKernelGGL(embedding_bwd_words_ordered_kernel<true>, grid, dim3(128), 0, (hipStream_t)stream, (const long long *)ids, (const long long *)order,
+                           (const uint16_t *)dout, dW, part_w, (long long)tokens, H, drop_p, seed);
+        hipLaunchKernelGGL(embedding_bwd_words_finish_kernel<true>, dim3((unsigned)chunks, (unsigned)((H + 511) / 512)), dim3(128), 0, (hipStream_t)stream,
+                           (const long long *)ids, (const long long *)order, (const float *)part_w, dW, (long long)tokens, H);
+    } else {
+        hipLaunchKernelGGL(embedding_bwd_words_ordered_kernel<false>, grid, dim3(128), 0, (hipStream_t)stream, (const long long *)ids, (const long long *)order,
+                           (const uint16_t *)dout, dW, part_w, (long long)tokens, H, drop_p, seed);
+        hipLaunchKernelGGL(embedding_bwd_words_finish_kernel<false>, dim3((unsigned)chunks, (unsigned)((H + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
+                           (const long long *)ids, (const long long *)order, (const float *)part_w, dW, (long long)tokens, H);
+    }
+    const unsigned slices = pos_slices(nb);
+    hipLaunchKernelGGL(embedding_bwd_pos_kernel<true>, dim3((unsigned)S, (unsigned)((H + 255) / 256), slices), dim3(256), 0, (hipStream_t)stream,
+                       (const long long *)types, (const uint16_t *)dout, part_p, part_t, (long long)tokens, S, H, n_types, drop_p, seed, (const int *)cu, nseq);
+    ordered_slot_sum(part_p, (long long)S * H, (int)slices, dP, H, H, S, false, true, (hipStream_t)stream);
+    if (types) ordered_slot_sum(part_t, (long long)n_types * H, (int)(S * slices), dT, H, H, n_types, true, true, (hipStream_t)stream);
     return LAUNCH_OK();
 }
 

@@ -43,12 +43,17 @@ struct T8Params {
     int tiles_i, tiles, items;      // items = tiles * slices
     int slices, total_kt;           // reduction slices; K-tiles (64 reduction rows) in all.  Slice z takes K-tiles z, z + slices, ...
     int atomic;                     // more than one slice: accumulate with fp32 atomics into a pre-zeroed C
+    long long slab;                 // ORD instance only: slice z stores to C + z * slab (0: one slice, `atomic` then means C += in place)
     int ablate;                     // -DEMDR2_EXPERIMENTS builds only (EMDR2_T8_ABLATE): 1 = the DMA stream re-reads K-tile 0, 2 = no DMA
 };
 
 #define T8_SLOT 16384                 // one half-tile: 64 reduction rows x 128 columns x 2 B
 #define T8_RING (10 * T8_SLOT)        // all 160 KiB of a CU's LDS
 
+// ORD (emdr2_gemm_tn_bf16_ordered, gemm_tn.hip): no float atomics.  Slice z plain-stores its tile into slab z and its column sums into row
+// z * tiles_j + tj of p.colsum ([slices * tiles_j][I]; every workgroup stores its row, zeros where none of its K-tiles were its turn);
+// tn_ordered_finish_kernel adds the slabs and rows in index order.  The default instance is the kernel as it was.
+template <bool ORD>
 __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -228,7 +233,8 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
             tot += __shfl_xor(tot, 16);
             tot += __shfl_xor(tot, 32);
             const int i = i0 + 128 * mh + 64 * wr + 16 * wc + t;
-            if (lq == 0 && i < p.I) unsafeAtomicAdd(&p.colsum[i], tot);
+            if (ORD) { if (lq == 0 && i < p.I) p.colsum[((long long)zs * tiles_j + tj) * p.I + i] = tot; }
+            else if (lq == 0 && i < p.I) unsafeAtomicAdd(&p.colsum[i], tot);
         }
     }
 #pragma unroll
@@ -243,7 +249,11 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
                 const int i = ib + r;
                 if (i >= p.I) continue;
                 float *dst = p.C + (long long)i * p.ldc + j;
-                if (p.atomic) unsafeAtomicAdd(dst, acc[mi][ni][r]);
+                if (ORD) {
+                    dst += (long long)zs * p.slab;
+                    if (p.atomic) *dst = *dst + acc[mi][ni][r];   // one slice: this workgroup alone owns the element
+                    else *dst = acc[mi][ni][r];
+                } else if (p.atomic) unsafeAtomicAdd(dst, acc[mi][ni][r]);
                 else *dst = acc[mi][ni][r];
             }
         }
@@ -254,8 +264,9 @@ __global__ void __launch_bounds__(512) gemm8t_kernel(T8Params p)
 
 // Called by emdr2_gemm_tn_bf16 (gemm_tn.hip); -4 = shape not covered, the caller falls through to the general kernel.  `split_k` is the number
 // of reduction slices (capped at the number of K-tiles).
-int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
-                     float *colsum_a, hipStream_t stream)
+template <bool ORD>
+static int gemm8t_launch(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
+                         float *colsum_a, long long slab, hipStream_t stream)
 {
     if ((R & 63) || R < 64 || I < 8 || J < 8 || (I & 7) || (J & 7)) return -4;
     if (40ll * lda * 2 + 2ll * I >= (1ll << 32) || 40ll * ldb * 2 + 2ll * J >= (1ll << 32)) return -4;       // 32-bit lane offsets inside a K-tile
@@ -269,8 +280,31 @@ int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, flo
     p.items = p.tiles * p.slices;
     p.ablate = 0;
     EXP_T8_HOST(p)
-    p.atomic = split_k > 1;                                   // the caller zeroed C exactly when it asked for more than one slice
-    if (lds_opt_in<gemm8t_kernel>(T8_RING) != LDS_OPT_IN_OK) return -3;
-    hipLaunchKernelGGL(gemm8t_kernel, dim3(8 * xcd_per(p.items)), dim3(512), T8_RING, stream, p);
+    p.atomic = ORD ? slab == 0 : split_k > 1;                 // (default) the caller zeroed C exactly when it asked for more than one slice
+    p.slab = slab;
+    if (lds_opt_in<gemm8t_kernel<ORD>>(T8_RING) != LDS_OPT_IN_OK) return -3;
+    hipLaunchKernelGGL(gemm8t_kernel<ORD>, dim3(8 * xcd_per(p.items)), dim3(512), T8_RING, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
+                     float *colsum_a, hipStream_t stream)
+{
+    return gemm8t_launch<false>(A, lda, B, ldb, C, ldc, I, J, R, split_k, colsum_a, 0, stream);
+}
+
+// Ordered form (emdr2_gemm_tn_bf16_ordered): `slices` is what emdr2_gemm8t_slices gives; slab != 0: slice z stores into C + z * slab (ldc is
+// the slab's), slab == 0 (one slice): C += the product in place.  colsum_rows: [slices * ceil(J / 256)][I], every row stored.
+int emdr2_gemm8t_ordered_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int slices,
+                             float *colsum_rows, long long slab, hipStream_t stream)
+{
+    return gemm8t_launch<true>(A, lda, B, ldb, C, ldc, I, J, R, slices, colsum_rows, slab, stream);
+}
+
+// whether the shape goes to this kernel, and with how many slices (0: not covered) -- the cap of gemm8t_launch
+int emdr2_gemm8t_slices(int64_t lda, int64_t ldb, int I, int J, int R, int split_k)
+{
+    if ((R & 63) || R < 64 || I < 8 || J < 8 || (I & 7) || (J & 7)) return 0;
+    if (40ll * lda * 2 + 2ll * I >= (1ll << 32) || 40ll * ldb * 2 + 2ll * J >= (1ll << 32)) return 0;
+    return split_k < (R >> 6) ? split_k : (R >> 6);
 }

@@ -30,12 +30,17 @@ struct TnParams {
     long long lda, ldb, ldc;
     int I, J, R, splitk;
     int tiles_i, tiles_j;
+    long long slab;                         // ORD instance only: slice z stores to C + z * slab (0: one slice, C += in place)
 };
 
 #define TN_STAGES 3
 #define TN_OPER 16384                       // one operand stage: 32 reduction rows x 256 columns x 2 B
 #define TN_STAGE (2 * TN_OPER)
 
+// ORD (emdr2_gemm_tn_bf16_ordered): no float atomics -- slice z plain-stores its tile into slab z and its column sums into row z of
+// p.colsum ([splitk][I]); tn_ordered_finish_kernel adds them in slice order.  The host caps splitk so that every slice has chunks (a slice
+// without chunks returns below without storing).  The default instance is the kernel as it was.
+template <bool ORD>
 __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -161,7 +166,8 @@ __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
         for (int mi = 0; mi < 2; ++mi) {
             const float tot = csum[mi] + __shfl_xor(csum[mi], 32);
             const int i = i0 + wm * 64 + mi * 32 + l31;
-            if (hi == 0 && i < p.I) atomicAdd(&p.colsum[i], tot);
+            if (ORD) { if (hi == 0 && i < p.I) p.colsum[(long long)zs * p.I + i] = tot; }
+            else if (hi == 0 && i < p.I) atomicAdd(&p.colsum[i], tot);
         }
     }
     // C layout of the 32x32 MFMA: column j = lane&31, row i = (r&3) + 8*(r>>2) + 4*(lane>>5)
@@ -178,7 +184,10 @@ __global__ void __launch_bounds__(512) gemm_tn_kernel(TnParams p)
                 const int i = irow0 + mi * 32 + (r & 3) + 8 * (r >> 2);
                 if (i >= p.I) continue;
                 float *dst = p.C + (long long)i * p.ldc + j;
-                if (p.splitk > 1) atomicAdd(dst, acc[mi][ni][r]);
+                if (ORD) {
+                    if (p.slab) dst[(long long)zs * p.slab] = acc[mi][ni][r];
+                    else *dst = *dst + acc[mi][ni][r];            // one slice: this workgroup alone owns the element
+                } else if (p.splitk > 1) atomicAdd(dst, acc[mi][ni][r]);
                 else *dst = acc[mi][ni][r];
             }
     }
@@ -202,8 +211,96 @@ extern "C" int emdr2_gemm_tn_bf16(const void *A, int64_t lda, const void *B, int
     p.A = (const char *)A; p.B = (const char *)B; p.C = C; p.colsum = colsum_a;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.I = I; p.J = J; p.R = R; p.splitk = split_k;
     constexpr int LDS = TN_STAGES * TN_STAGE;
-    if (lds_opt_in<gemm_tn_kernel>(LDS) != LDS_OPT_IN_OK) return -3;
-    p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * split_k)), dim3(512), LDS, (hipStream_t)stream, p);
+    if (lds_opt_in<gemm_tn_kernel<false>>(LDS) != LDS_OPT_IN_OK) return -3;
+    p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256; p.slab = 0;
+    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * split_k)), dim3(512), LDS, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ---- ordered form: the same product with no float atomics (include/emdr2_ops.h: emdr2_gemm_tn_bf16_ordered) ---------------------------
+// ORDER.  The slices are those of emdr2_gemm_tn_bf16 for the same arguments (64-row kernel: K-tile kt belongs to slice kt % slices, slices =
+// min(split_k, R / 64); general kernel: slice z owns chunks [z * per, (z + 1) * per) of 32 rows, split_k lowered until no slice is empty);
+// inside a slice the MFMA accumulation order of the kernel.  Slice z stores its tile into slab z of the workspace ([I][J] fp32) and
+// C[i, j] = C[i, j] + (((s_0 + s_1) + s_2) + ...) in slice order, one add onto C.  colsum: the 64-row kernel stores one row per (slice z,
+// j-tile tj) -- the K-tiles of a slice take turns over the j-tiles -- and colsum[i] += ((row_0 + row_1) + ...) in the order z * tiles_j + tj;
+// the general kernel one row per slice.  One slice: no slab, the kernel adds onto C itself; the colsum rows still go through the workspace.
+int emdr2_gemm8t_ordered_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int slices,
+                             float *colsum_rows, long long slab, hipStream_t stream);       // gemm8t.hip
+int emdr2_gemm8t_slices(int64_t lda, int64_t ldb, int I, int J, int R, int split_k);
+
+#include "ordered_sum.h"
+
+namespace {
+
+struct TnOrderedPlan { int slices, cs_rows; bool k64; };
+
+// a pure function of the shape arguments (the leading dimensions decide only between the two kernels, as in emdr2_gemm_tn_bf16)
+TnOrderedPlan tn_ordered_plan(int64_t lda, int64_t ldb, int I, int J, int R, int split_k)
+{
+    TnOrderedPlan pl;
+    bool general_only = false;
+    EXP_TN_GENERAL_ONLY(general_only)
+    const int s8 = general_only ? 0 : emdr2_gemm8t_slices(lda, ldb, I, J, R, split_k);
+    pl.k64 = s8 > 0;
+    if (pl.k64) { pl.slices = s8; pl.cs_rows = s8 * ((J + 255) / 256); return pl; }
+    const int nch = R >> 5;
+    int s = split_k < nch ? split_k : nch;
+    for (;;) {                                                          // until the last slice starts inside the reduction
+        const int per = (nch + s - 1) / s, e = (nch + per - 1) / per;
+        if (e == s) break;
+        s = e;
+    }
+    pl.slices = s; pl.cs_rows = s;
+    return pl;
+}
+
+size_t tn_ordered_bytes(const TnOrderedPlan &pl, int I, int J, int slices_for_slabs)
+{
+    return ((size_t)slices_for_slabs * I * J + (size_t)pl.cs_rows * I) * sizeof(float);
+}
+
+} // namespace
+
+// the workspace for ANY leading dimensions: the larger of the two kernels' needs
+extern "C" int emdr2_gemm_tn_ordered_ws_bytes(int I, int J, int R, int split_k, size_t *bytes)
+{
+    if (!bytes || I < 8 || J < 8 || R < 32 || (R & 31) || split_k < 1 || (I & 7) || (J & 7)) return -1;
+    const TnOrderedPlan a = tn_ordered_plan(8, 8, I, J, R, split_k), b = tn_ordered_plan(1ll << 40, 1ll << 40, I, J, R, split_k);
+    const size_t na = tn_ordered_bytes(a, I, J, a.slices > 1 ? a.slices : 0), nb = tn_ordered_bytes(b, I, J, b.slices > 1 ? b.slices : 0);
+    *bytes = na > nb ? na : nb;
+    return 0;
+}
+
+extern "C" int emdr2_gemm_tn_bf16_ordered(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
+                                          float *colsum_a, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!A || !B || !C || I < 8 || J < 8 || R < 32 || (R & 31) || split_k < 1 || ldc < J) return -1;
+    if ((I & 7) || (J & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)ws & 15)) return -1;
+    const TnOrderedPlan pl = tn_ordered_plan(lda, ldb, I, J, R, split_k);
+    const bool slabs = pl.slices > 1;
+    if (slabs || colsum_a) {
+        if (!ws) return -1;
+        if (ws_bytes < tn_ordered_bytes(pl, I, J, slabs ? pl.slices : 0)) return -2;
+    }
+    OpsTimer timer(OPS_GEMM_TN, 2.0 * I * (double)J * R, (hipStream_t)stream);
+    const long long slab = slabs ? (long long)I * J : 0;
+    float *slab0 = (float *)ws, *cs_rows = colsum_a ? (float *)ws + (size_t)(slabs ? pl.slices : 0) * I * J : nullptr;
+    float *out = slabs ? slab0 : C;
+    const int64_t ldo = slabs ? J : ldc;
+    if (pl.k64) {
+        const int rc = emdr2_gemm8t_ordered_try(A, lda, B, ldb, out, ldo, I, J, R, pl.slices, cs_rows, slab, (hipStream_t)stream);
+        if (rc != 0) return rc == -4 ? -3 : rc;                         // the plan said this kernel covers the shape
+    } else {
+        TnParams p;
+        p.A = (const char *)A; p.B = (const char *)B; p.C = out; p.colsum = cs_rows;
+        p.lda = lda; p.ldb = ldb; p.ldc = ldo; p.I = I; p.J = J; p.R = R; p.splitk = pl.slices; p.slab = slab;
+        constexpr int LDS = TN_STAGES * TN_STAGE;
+        if (lds_opt_in<gemm_tn_kernel<true>>(LDS) != LDS_OPT_IN_OK) return -3;
+        p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256;
+        hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * pl.slices)), dim3(512), LDS, (hipStream_t)stream, p);
+        if (hipGetLastError() != hipSuccess) return -3;
+    }
+    if (slabs) ordered_slot_sum(slab0, slab, pl.slices, C, ldc, J, I, false, false, (hipStream_t)stream);
+    if (colsum_a) ordered_slot_sum(cs_rows, I, pl.cs_rows, colsum_a, I, I, 1, false, false, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

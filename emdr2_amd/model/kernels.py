@@ -107,15 +107,62 @@ def weight_grad_nt(dyT, xT):
     return gemm_nt(dyT, M, xT, M, c, Kd, N, Kd, M, split_k=split)
 
 
+class _OrderedGrads(object):
+    """Switch for bit-reproducible parameter gradients (--deterministic-gradients; include/emdr2_ops.h, "Ordered sums").  ON = the weight-gradient
+    GEMM, the LayerNorm gain / bias sums and the embedding backward go through the *_ordered entries: partial sums are stored into a workspace
+    and added in a fixed order, one fp32 add onto the gradient buffer, no float atomics.  OFF (default) = every launch is what it was; no
+    workspace, no sort.  One workspace per stream, grown to the largest request (launches on one stream are ordered, so they share it)."""
+
+    def __init__(self):
+        self.enabled = False
+        self._ws = {}
+        self.calls = 0                                   # ordered launches so far (tests: the path was taken)
+        self.max_split = 0                               # largest split the weight-gradient GEMM took while enabled
+
+    def workspace(self, nbytes, device):
+        import ctypes
+        key = (device, torch.cuda.current_stream(device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = None
+            self._ws.pop(key, None)                      # (free before growing)
+            ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        self.calls += 1
+        return ws.data_ptr(), ctypes.c_size_t(ws.numel())
+
+    def release(self):
+        self._ws.clear()
+
+
+ORDERED = _OrderedGrads()
+
+
+def _ws_bytes(fn, *args):
+    import ctypes
+    n = ctypes.c_size_t()
+    _native.check(fn(*(args + (ctypes.byref(n),))), "ordered workspace size")
+    return n.value
+
+
 def weight_grad_tn(dy, x, colsum=None, into=None):
     """dW [N, K] fp32 = dy [M, N]^T @ x [M, K] straight from the row-major activations (gemm_tn.hip); `colsum` (fp32 [N]) accumulates the
     bias gradient.  Few output tiles, reduction over all tokens -> the reduction is split across the chip.  `into` (fp32 [N, K], holding
     zeros or earlier contributions): accumulate there with the slices' atomics instead of returning a fresh tensor -- taken only when the
-    reduction is split (a single slice stores plainly); the caller learns which from the returned tensor."""
+    reduction is split (a single slice stores plainly); the caller learns which from the returned tensor.  With ORDERED.enabled the slices go
+    through per-slice slabs and are added in slice order (emdr2_gemm_tn_bf16_ordered): no atomics, `into` taken whatever the split."""
     M, N = dy.shape
     Kd = x.shape[1]
     tiles = ((N + 255) // 256) * ((Kd + 255) // 256)
     split = max(1, min(512 // max(tiles, 1), M // 4096))
+    if ORDERED.enabled:
+        # the same split, from the shape alone; the ordered entry ADDS its total (one add per element), so `into` is taken whatever the split
+        ORDERED.max_split = max(ORDERED.max_split, split)
+        c = into if into is not None else torch.zeros((N, Kd), dtype=torch.float32, device=dy.device)
+        ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_gemm_tn_ordered_ws_bytes, N, Kd, M, split), dy.device)
+        _native.check(_lib().emdr2_gemm_tn_bf16_ordered(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), c.data_ptr(), Kd, N, Kd, M, split,
+                                                        _ptr(colsum), ws, nws, _sp()), "gemm_tn_bf16_ordered")
+        return c
     if into is not None and split > 1:
         c = into
     else:
@@ -671,6 +718,22 @@ def _ln_backward(dy2, x2, gamma, beta, mean, rstd, dres):
     (dg, dg_direct), (db, db_direct) = _grad_buffer(gamma), _grad_buffer(beta)            # the kernel adds its column sums atomically
     req = PREMASK.request_for(x2)          # x2 is the output of a bias-dropout-add whose backward runs next and wants dx o mask
     rc = -4
+    if ORDERED.enabled:                    # the same dx / dmask bits; the column sums go through the workspace in a fixed order
+        ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_layernorm_bwd_ordered_ws_bytes, rows, H), x2.device)
+        args = (dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
+                rows, H)
+        if req is not None:
+            dmask = torch.empty_like(x2)
+            rc = _lib().emdr2_layernorm_bwd_ordered(*(args + (dmask.data_ptr(), req[0], req[1], ws, nws, _sp())))
+            if rc == 0:
+                PREMASK.offer(dx, req[0], req[1], dmask)
+            elif rc != -4:
+                _native.check(rc, "layernorm_bwd_ordered")
+        if rc == -4:
+            _native.check(_lib().emdr2_layernorm_bwd_ordered(*(args + (None, 0.0, 0, ws, nws, _sp()))), "layernorm_bwd_ordered")
+        _deliver_grad(gamma, dg, dg_direct)
+        _deliver_grad(beta, db, db_direct)
+        return dx
     if req is not None:
         dmask = torch.empty_like(x2)
         rc = _lib().emdr2_layernorm_bwd_mask(dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(),
@@ -1237,7 +1300,19 @@ class EmbeddingFn(torch.autograd.Function):
         dout = dout.contiguous()
         (dW, dW_direct), (dP, dP_direct) = _grad_buffer(W), _grad_buffer(P)            # the kernels scatter-add their rows atomically
         dT, dT_direct = _grad_buffer(T) if types is not None else (None, False)
-        if seqs is not None:
+        if ORDERED.enabled:
+            # the inverted index of the word rows: a stable sort puts each vocabulary row's tokens together, in ascending token index
+            if seqs is not None:
+                flat, cu, nseq, rows, S = ids, seqs.cu.data_ptr(), seqs.n, seqs.rows, seqs.S
+            else:
+                flat, cu, nseq, rows, S = ids, None, ids.shape[0], ids.numel(), ids.shape[1]
+            order = torch.sort(flat.reshape(-1)[:rows], stable=True)[1]
+            nt = T.shape[0] if dT is not None else 0
+            ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_embedding_bwd_ordered_ws_bytes, rows, nseq, S, H, nt), dout.device)
+            _native.check(_lib().emdr2_embedding_bwd_ordered(flat.data_ptr(), _ptr(types), cu, nseq, order.data_ptr(), dout.data_ptr(), dW.data_ptr(),
+                                                             dP.data_ptr(), _ptr(dT), rows, S, H, nt, float(ctx.drop_p), int(ctx.seed), ws, nws, _sp()),
+                          "embedding_bwd_ordered")
+        elif seqs is not None:
             _native.check(_lib().emdr2_embedding_packed_bwd(ids.data_ptr(), _ptr(types), seqs.cu.data_ptr(), seqs.n, dout.data_ptr(), dW.data_ptr(),
                                                             dP.data_ptr(), _ptr(dT), seqs.rows, seqs.S, H, T.shape[0] if dT is not None else 0,
                                                             float(ctx.drop_p), int(ctx.seed), _sp()), "embedding_packed_bwd")

@@ -74,6 +74,10 @@ def model_provider(args=None, bert_tokenizer=None, t5_tokenizer=None, arena=None
         print_rank_0('retriever loss: KL(reader attention mass{} || prior), no one-context pass (--retriever-distill-attention)'.format(
             ', value-norm weighted' if model.attention_mass_value_norms else ''))
     model.index_writeback = bool(getattr(args, "index_writeback", False))
+    from emdr2_amd.model import kernels
+    kernels.ORDERED.enabled = bool(getattr(args, "deterministic_gradients", False))       # process-wide, like PACKING: set either way
+    if kernels.ORDERED.enabled:
+        print_rank_0('parameter gradients are summed in a fixed order, no float atomics (--deterministic-gradients)')
     if getattr(args, "retrieval_answer_hits", False):
         from emdr2_amd.tasks.openqa.e2eqa.answer_hits import AnswerHitTracker, report_ranks
         retriever.track_kept_ids = True

@@ -43,6 +43,35 @@ int emdr2_gemm_nt_bf16(const void *A, int64_t lda, const void *B, int64_t ldb, v
 int emdr2_gemm_tn_bf16(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
                        float *colsum_a, void *stream);
 
+/* ---- Ordered sums ("deterministic gradients"): the gradient entries that add across workgroups, with no float atomics -----------------------
+ * Contract of every *_ordered entry: the total of a destination element is computed in an order that is a function of the entry's arguments
+ * and compile-time constants only (never of the CU count, of which workgroup finished first, or of what else runs), and is then added to
+ * the destination with ONE fp32 add per element per call: dst = dst + total.  The destination therefore holds zeros or earlier contributions
+ * (no pre-zeroing contract), and two calls with the same arguments on the same data give the same bits.  Partial sums go through `ws`
+ * (device memory, 16-byte aligned, at least *_ws_bytes; contents irrelevant before and after) and are finished by a second launch on the
+ * same stream.  The order of each sum is written at its kernel (csrc/gemm_tn.hip, csrc/elementwise.hip, csrc/ordered_sum.h).  Not promised:
+ * equality with the atomic entries, across different split_k, or across different row counts.  -2: ws_bytes too small.
+ *
+ * emdr2_gemm_tn_bf16_ordered mirrors emdr2_gemm_tn_bf16 (same operands, same dispatch between the two kernels, same slices): C += A^T B and
+ * colsum_a += column sums of A.  ws_bytes covers either kernel; ldc >= J. */
+int emdr2_gemm_tn_ordered_ws_bytes(int I, int J, int R, int split_k, size_t *bytes);
+int emdr2_gemm_tn_bf16_ordered(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,
+                               float *colsum_a, void *ws, size_t ws_bytes, void *stream);
+/* mirrors emdr2_layernorm_bwd (dmask == NULL) and emdr2_layernorm_bwd_mask (dmask != NULL: H == 768 and aligned only, -4 otherwise); dx and dmask
+ * have the bits of those entries, dgamma / dbeta += the ordered column sums. */
+int emdr2_layernorm_bwd_ordered_ws_bytes(int64_t rows, int H, size_t *bytes);
+int emdr2_layernorm_bwd_ordered(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd, const void *dres, void *dx,
+                                float *dgamma, float *dbeta, int64_t rows, int H, void *dmask, float drop_p, uint32_t seed, void *ws, size_t ws_bytes,
+                                void *stream);
+/* mirrors emdr2_embedding_bwd (cu == NULL: tokens % S == 0) and emdr2_embedding_packed_bwd (cu != NULL, nseq sequences, tokens = packed rows).
+ * order (int64 [tokens]): the STABLE ascending sort of the token indices by ids -- ids[order[q]] ascending, equal ids in ascending token index.
+ * Vocabulary rows without tokens and positions no sequence reaches are not written.  nseq of the ws_bytes call: the number of sequences
+ * (tokens / S when dense). */
+int emdr2_embedding_bwd_ordered_ws_bytes(int64_t tokens, int nseq, int S, int H, int n_types, size_t *bytes);
+int emdr2_embedding_bwd_ordered(const int64_t *ids, const int64_t *types, const int32_t *cu, int nseq, const int64_t *order, const void *dout, float *dW,
+                                float *dP, float *dT, int64_t tokens, int S, int H, int n_types, float drop_p, uint32_t seed, void *ws, size_t ws_bytes,
+                                void *stream);
+
 /* out[r, c] = keep(seed, r, c) ? x[r, c] / (1 - p) : 0 over a contiguous bf16 [n / cols, cols] tensor (the mask of a dropout site,
  * regenerated; cols % 8 == 0). */
 int emdr2_dropout(const void *x, void *out, int64_t n, int cols, float drop_p, uint32_t seed, void *stream);
