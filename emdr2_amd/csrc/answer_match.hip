@@ -6,7 +6,7 @@
 // costs one bitset lookup unless its token starts an answer; only then are the answers of that token's chain compared.
 // best_kernel: one wave per question finds the first slot with a hit and adds one to its histogram bin.
 #include "../../include/emdr2_answers.h"
-#include <hip/hip_runtime.h>
+#include "prims.h"
 
 namespace {
 
@@ -175,8 +175,8 @@ extern "C" int emdr2_answer_hits(const emdr2_evidence_arena *arena, const int32_
     p.n_b = n_b; p.k = k; p.groups = (k + AH_SLOTS_PER_WG - 1) / AH_SLOTS_PER_WG;
     if ((long long)n_b * p.groups > 0x7FFFFFFFll) return -1;
     hipLaunchKernelGGL(hits_kernel, dim3((unsigned)(n_b * p.groups)), dim3(AH_THREADS), 0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (const int rc = LAUNCH_OK()) return rc;
     hipLaunchKernelGGL(best_kernel, dim3((unsigned)((n_b + AH_WAVES - 1) / AH_WAVES)), dim3(AH_THREADS), 0, (hipStream_t)stream,
                        (const int32_t *)hit_pos, n_b, k, best_slot, slot_hist);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }

@@ -2,7 +2,7 @@
 // One workgroup per (query, kept evidence): thread 0 resolves the title-group neighbours and lays the three
 // output rows out as short segment lists (constant / query / passage / title slices); all threads then copy.
 #include "../../include/emdr2_assembly.h"
-#include <hip/hip_runtime.h>
+#include "prims.h"
 
 namespace {
 
@@ -175,5 +175,5 @@ extern "C" int emdr2_assemble_evidence(const emdr2_evidence_arena *arena, const 
     p.n_b = n_b; p.k_retrieved = k_retrieved; p.topk = topk; p.q_stride = q_stride;
     p.seq_len_ret = seq_len_ret; p.seq_len = seq_len; p.cls_id = cls_id; p.sep_id = sep_id; p.pad_id = pad_id;
     hipLaunchKernelGGL(assemble_kernel, dim3(n_b * topk), dim3(128), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }

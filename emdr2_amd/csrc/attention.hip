@@ -336,7 +336,7 @@ static int attention_fwd_launch(const FwdArgs &a)
     if (ksplit > 1)
         hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)((p.stat_n + 3) / 4)), dim3(256), 0, stream, p,
                            a.drop_p > 0.f ? emdr2_keep_scale(a.drop_p) : 1.f);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 extern "C" int emdr2_attention_fwd(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,

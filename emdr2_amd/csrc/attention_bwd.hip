@@ -501,7 +501,7 @@ static int attention_bwd_launch(const BwdArgs &a)
     attn_instance(a.drop_p > 0.f, a.causal, [&](auto drop, auto causal) {
         hipLaunchKernelGGL((attention_bwd_dkv_kernel<decltype(drop)::value, decltype(causal)::value>), kv_grid, dim3(KNW * 64), 0, stream, p);
     });
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 extern "C" int emdr2_attention_bwd(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,

@@ -4,29 +4,13 @@
 // granule) and for ds_read_b64_tr_b16 transpose reads (4 rows x 4 granules per 32-lane service group; layout pinned by tools/tr_probe.hip).
 #ifndef EMDR2_ATTENTION_COMMON_H
 #define EMDR2_ATTENTION_COMMON_H
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <type_traits>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
+#include "prims.h"
 
 #define L2E 1.4426950408889634f
 #define MASKED2 (-10000.f * 1.4426950408889634f)
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
 __device__ __forceinline__ int tile_swz(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b)
-{
-    const floatx2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));     // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 // Fragment of the row-major global matrix row: 8 bf16 at d = 16 t + 8 hi for t = 0..3 (the B operand of the "swapped" MFMAs)
 __device__ __forceinline__ void load_row_frags(const char *row, int hi, bf16x8 (&f)[4])

@@ -206,7 +206,7 @@ static int launch_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_
     const dim3 grid((unsigned)(batch * heads * n_seg)), block(MASS_WAVES * 64);
     if (weighted) hipLaunchKernelGGL(attention_key_mass_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attention_key_mass_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 extern "C" int emdr2_attention_key_mass(const void *q, int64_t q_sb, int64_t q_ss, int64_t q_sn, const void *k, int64_t k_sb, int64_t k_ss, int64_t k_sn,
@@ -241,5 +241,5 @@ extern "C" int emdr2_head_row_norms(const void *x, int64_t x_sb, int64_t x_ss, i
     if (blocks > 0x7fffffffLL) return -4;
     hipLaunchKernelGGL(head_row_norms_kernel, dim3((unsigned)blocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const char *)x, (long long)x_sb,
                        (long long)x_ss, (long long)x_sn, norm, (long long)ld, sk, heads, items);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }

@@ -7,27 +7,11 @@
 // are one wave per row.  fp32 in, fp32 accumulate, fp32 out -- the reference's arithmetic when --fp16 is not given
 // (megatron/training.py:55-56).
 #include "../../include/emdr2_ops_f32.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "prims.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
-
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -3)
-
-__device__ __forceinline__ float wave_sum(float x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ float wave_max(float x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
 
 // ================================================================ GEMM =================================================================
 struct GemmP {
@@ -251,7 +235,7 @@ __global__ void __launch_bounds__(256) lse_fwd_f32_kernel(const float *logits, c
     if (threadIdx.x == 0) {
         const float l = m + logf((red[0] + red[1]) + (red[2] + red[3]));
         lse[row] = l;
-        const long long lab = labels[row];                               // outside [0, V): gold logit 0, as in elementwise.hip
+        const long long lab = labels[row];                               // outside [0, V): gold logit 0, as in loss_tail.hip
         gold[row] = (lab >= 0 && lab < V ? lr[lab] : 0.f) - l;
     }
 }

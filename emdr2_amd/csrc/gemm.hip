@@ -207,14 +207,14 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                         for (int j = 0; j < 8; ++j) v[j] = gelu_erf_with_grad(v[j], d[j]);
                         uint32_t w[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) w[j] = pack2_bf16(d[2 * j], d[2 * j + 1]);
-                        store_stream((uint16_t *)p.C2 + o, make_uint4(w[0], w[1], w[2], w[3]));
+                        for (int j = 0; j < 4; ++j) w[j] = pack_bf16(d[2 * j], d[2 * j + 1]);
+                        st_stream((uint16_t *)p.C2 + o, make_uint4(w[0], w[1], w[2], w[3]));
                     } else {
                         if (p.C2) {
                             uint32_t w[4];
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) w[j] = pack2_bf16(v[2 * j], v[2 * j + 1]);
-                            store_stream((uint16_t *)p.C2 + o, make_uint4(w[0], w[1], w[2], w[3]));
+                            for (int j = 0; j < 4; ++j) w[j] = pack_bf16(v[2 * j], v[2 * j + 1]);
+                            st_stream((uint16_t *)p.C2 + o, make_uint4(w[0], w[1], w[2], w[3]));
                         }
                         if (p.gelu) {
 #pragma unroll
@@ -243,9 +243,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                     }
                     uint32_t w[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) w[j] = pack2_bf16(v[2 * j], v[2 * j + 1]);
+                    for (int j = 0; j < 4; ++j) w[j] = pack_bf16(v[2 * j], v[2 * j + 1]);
                     EXP_GEMM_STORE_IF(p, w)
-                    store_stream((uint16_t *)p.C + o, make_uint4(w[0], w[1], w[2], w[3]));
+                    st_stream((uint16_t *)p.C + o, make_uint4(w[0], w[1], w[2], w[3]));
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads of this half are done before the next half overwrites
@@ -269,20 +269,20 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_nt_kernel(GemmParams p)
                 if (m >= p.M) continue;
                 const long long o = coff + (long long)m * p.ldc + n;
                 float v = epi_affine(acc[mi][ni][r], p.alpha, bias);
-                if (p.gelu == 2) { float d; v = gelu_erf_with_grad(v, d); ((uint16_t *)p.C2)[o] = f32_to_bf16(d); }
+                if (p.gelu == 2) { float d; v = gelu_erf_with_grad(v, d); ((uint16_t *)p.C2)[o] = f2bf(d); }
                 else {
-                    if (p.C2) ((uint16_t *)p.C2)[o] = f32_to_bf16(v);
+                    if (p.C2) ((uint16_t *)p.C2)[o] = f2bf(v);
                     if (p.gelu) v = gelu_erf(v);
                 }
                 if (p.drop_p > 0.f) v = emdr2_keep(emdr2_row_hash(p.seed, (unsigned long long)m), (uint32_t)n, emdr2_drop_thr(p.drop_p)) ? v * emdr2_keep_scale(p.drop_p) : 0.f;
                 if (p.R) {
-                    const float rv = bf16_to_f32(((const uint16_t *)p.R)[o]);
+                    const float rv = bf2f(((const uint16_t *)p.R)[o]);
                     if (!p.out_f32) v = round_to_stored_bf16(v);          // (an fp32 output was never stored as bf16)
                     v = p.rmode == 0 ? v + rv : (p.rmode == 2 ? v * rv : v * gelu_erf_grad(rv));   // epi_residual_pair's combine on this lane's one element
                 }
                 if (p.splitk > 1) atomicAdd(&((float *)p.C)[o], v);
                 else if (p.out_f32) ((float *)p.C)[o] = v;
-                else ((uint16_t *)p.C)[o] = f32_to_bf16(v);
+                else ((uint16_t *)p.C)[o] = f2bf(v);
             }
         }
     }
@@ -305,7 +305,7 @@ static int launch_gemm_v(const GemmParams &p, int batch, hipStream_t stream)
     dim3 grid(tiles_m, tiles_n, batch * p.splitk);
     if (q.order == 1) grid = dim3(8 * xcd_per(tiles_m * tiles_n), 1, batch * p.splitk);
     hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, VEC, MI>), grid, dim3(WM * WN * 64), LDS, stream, q);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 template <int WM, int WN, int MI = 2>

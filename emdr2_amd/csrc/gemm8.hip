@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                             }
                             // accumulator order -> LDS: 4 consecutive columns = one 8-byte slot
                             const int c8 = nt * 4 + eq;
-                            *(uint2 *)(stg + srow * 128 + ((c8 ^ (srow & 15)) << 3)) = make_uint2(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]));
+                            *(uint2 *)(stg + srow * 128 + ((c8 ^ (srow & 15)) << 3)) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
                         }
                     }
                     asm volatile("" ::: "memory");                       // compiler fence only: the LDS executes one wave's writes and reads in order
@@ -348,11 +348,11 @@ __global__ void __launch_bounds__(512) gemm8_kernel(G8Params p)
                             for (int q = 0; q < 4; ++q) {
                                 const floatx2_t x = {bf_lo(w[q]), bf_hi(w[q])};     // (the staging buffer holds the stored bf16 already)
                                 const floatx2_t y = epi_residual_pair(x, rw[q], (EPI & G8_RADD) ? 0 : (EPI & G8_RMUL) ? 2 : 1);
-                                w[q] = pack2_bf16(y[0], y[1]);
+                                w[q] = pack_bf16(y[0], y[1]);
                             }
                         }
                         EXP_G8_STORE_IF(p, w)
-                        store_stream((uint16_t *)(outp + (mi * 4 + ps) * pitch8), make_uint4(w[0], w[1], w[2], w[3]));
+                        st_stream((uint16_t *)(outp + (mi * 4 + ps) * pitch8), make_uint4(w[0], w[1], w[2], w[3]));
                     }
                     asm volatile("" ::: "memory");                       // (the next pass's writes queue behind these reads in the same in-order LDS pipe)
                 }
@@ -426,7 +426,7 @@ int g8_launch(G8Params &p, hipStream_t stream)
     p.stagger = p.total >= 4 * grid ? 25 : 0;                  // only when every workgroup has several tiles to amortise the late start
     EXP_G8_HOST_LAUNCH(p)
     hipLaunchKernelGGL((gemm8_kernel<EPI>), dim3(grid), dim3(512), LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 } // namespace

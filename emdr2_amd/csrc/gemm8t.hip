@@ -284,7 +284,7 @@ static int gemm8t_launch(const void *A, int64_t lda, const void *B, int64_t ldb,
     p.slab = slab;
     if (lds_opt_in<gemm8t_kernel<ORD>>(T8_RING) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL(gemm8t_kernel<ORD>, dim3(8 * xcd_per(p.items)), dim3(512), T8_RING, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 int emdr2_gemm8t_try(const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int I, int J, int R, int split_k,

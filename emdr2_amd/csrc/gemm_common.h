@@ -1,44 +1,13 @@
-// emdr2_amd/csrc/gemm_common.h -- what the bf16 GEMM kernels (gemm.hip, gemm8.hip, gemm_tn.hip, gemm8t.hip) share: bf16 packing, the erf-form
-// GELU of the reference (transformer.py:80,103-104: F.gelu, not the tanh fusion) and its derivative, streaming stores, the element recipe of
+// emdr2_amd/csrc/gemm_common.h -- what the bf16 GEMM kernels (gemm.hip, gemm8.hip, gemm_tn.hip, gemm8t.hip) share beside prims.h: the erf-form
+// GELU of the reference (transformer.py:80,103-104: F.gelu, not the tanh fusion) and its derivative, the element recipe of
 // the NT epilogues, the XCD-contiguous item mapping, and the barrier / transposed-read macros of the 256 x 256 pipelines.
 #ifndef EMDR2_GEMM_COMMON_H
 #define EMDR2_GEMM_COMMON_H
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "prims.h"
 #include "rng.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float floatx2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }            // the two bf16 of a packed pair
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t f32_to_bf16(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40); // quiet NaN
-    u += 0x7fffu + ((u >> 16) & 1u);                                             // round to nearest even
-    return (uint16_t)(u >> 16);
-}
-// two fp32 -> packed bf16 pair with the hardware converter (v_cvt_pk_bf16_f32, round to nearest even, NaN preserved)
-__device__ __forceinline__ uint32_t pack2_bf16(float a, float b)
-{
-    const floatx2_t v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-// outputs are written once and not re-read by the producing kernel: streaming stores keep them from evicting the operand panels the
-// other tiles of the XCD are about to reuse
-__device__ __forceinline__ void store_stream(uint16_t *dst, uint4 v)
-{
-    const u32x4_t x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, (u32x4_t *)dst);
-}
 // erf-form GELU 0.5 x (1 + erf(x / sqrt 2)).  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below the bf16 output grid) on one
 // v_rcp and one v_exp; the library erff costs ~3x.  With erf(|z|) = 1 - P(t) exp(-z^2), t = 1 / (1 + p |z|), both signs of x collapse into
 //   gelu(x) = max(x, 0) - |x| * (P(t) / 2) * exp(-x^2 / 2)
@@ -81,7 +50,7 @@ __device__ __forceinline__ float gelu_erf_grad(float x)
 // share beside gelu_erf / gelu_erf_with_grad above; each keeps its own staging, dropout form and branches on the output mode.
 __device__ __forceinline__ float epi_affine(float acc, float alpha, float bias) { return fmaf(acc, alpha, bias); }
 // the value meets the residual as the bf16 the reference's F.linear would have stored: one rounding before the combine, one after
-__device__ __forceinline__ float round_to_stored_bf16(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+__device__ __forceinline__ float round_to_stored_bf16(float v) { return bf2f(f2bf(v)); }
 // one packed bf16 pair of the residual.  rmode 0: + r;  1: * gelu'(r) -- r is the saved GELU pre-activation (backward of the FFN's first
 // linear, fused);  2: * r.  A run-time rmode costs a uniform branch per pair (and keeps the pair in packed math), a constant folds.
 __device__ __forceinline__ floatx2_t epi_residual_pair(floatx2_t x, uint32_t rw, int rmode)
@@ -113,7 +82,6 @@ __device__ __forceinline__ void tn_item_coords(int item, int tiles, int tiles_i,
 
 // ---- ds_read_b64_tr_b16 as inline asm (the builtin makes the wait-count pass put vmcnt(0) in front of every read: gemm8t.hip), and the bf16x8
 // MFMA operand of two such 8-byte halves
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define TR_FRAG(L, H) __builtin_bit_cast(bf16x8, make_uint4((L).x, (L).y, (H).x, (H).y))
 
 // ---- phase boundary of the 256 x 256 pipelines (gemm8.hip, gemm8t.hip): wait for this phase's DMA, meet, wait for its LDS reads, MFMAs at

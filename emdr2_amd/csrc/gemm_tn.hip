@@ -214,7 +214,7 @@ extern "C" int emdr2_gemm_tn_bf16(const void *A, int64_t lda, const void *B, int
     if (lds_opt_in<gemm_tn_kernel<false>>(LDS) != LDS_OPT_IN_OK) return -3;
     p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256; p.slab = 0;
     hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * split_k)), dim3(512), LDS, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 // ---- ordered form: the same product with no float atomics (include/emdr2_ops.h: emdr2_gemm_tn_bf16_ordered) ---------------------------
@@ -298,9 +298,9 @@ extern "C" int emdr2_gemm_tn_bf16_ordered(const void *A, int64_t lda, const void
         if (lds_opt_in<gemm_tn_kernel<true>>(LDS) != LDS_OPT_IN_OK) return -3;
         p.tiles_i = (I + 255) / 256; p.tiles_j = (J + 255) / 256;
         hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(8 * xcd_per(p.tiles_i * p.tiles_j * pl.slices)), dim3(512), LDS, (hipStream_t)stream, p);
-        if (hipGetLastError() != hipSuccess) return -3;
+        if (const int rc = LAUNCH_OK()) return rc;
     }
     if (slabs) ordered_slot_sum(slab0, slab, pl.slices, C, ldc, J, I, false, false, (hipStream_t)stream);
     if (colsum_a) ordered_slot_sum(cs_rows, I, pl.cs_rows, colsum_a, I, I, 1, false, false, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }

@@ -216,5 +216,5 @@ int mips_launch_audit(const AuditParams &p, hipStream_t stream)
         hipLaunchKernelGGL(audit_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
         hipLaunchKernelGGL(audit_finish_kernel, dim3(1), dim3(64), 0, stream, p.emax_sq, p.report);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }

@@ -5,8 +5,6 @@
 #include "mips_derived.h"
 #include "mips_digest.h"
 
-#define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
-
 // ------------------------------------------------------------------------------------------------
 // index re-layout (reference: add_embed_data uploads a dense row-major fp16 matrix,
 // megatron/data/emdr2_index.py:248-256; here the upload is re-tiled into scan order)
@@ -89,7 +87,7 @@ int mips_launch_block_norms(const void *tiled, int dim, int64_t first_block, int
     if (n_blocks == 0) return 0;
     hipLaunchKernelGGL(block_norms_kernel<BlockRange>, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 8, BlockRange{first_block},
                        block_norm_sq);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // the same over the touched-block list of a scattered update: `grid` workgroups, those not below *n_touched exit
@@ -99,13 +97,13 @@ int mips_launch_block_norms_list(const void *tiled, int dim, const unsigned *tou
     if (grid == 0) return 0;
     hipLaunchKernelGGL(block_norms_kernel<BlockList>, dim3(grid), dim3(256), 0, stream, (const char *)tiled, dim / 8, BlockList{touched, n_touched},
                        block_norm_sq);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_table_max(const float *block_norm_sq, int64_t n_blocks, float *emax_sq, hipStream_t stream)
 {
     hipLaunchKernelGGL(table_max_kernel, dim3(1), dim3(1024), 0, stream, block_norm_sq, n_blocks, emax_sq);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // pack_rows_kernel alone: rows into the image, emax_sq untouched (the in-place update recomputes it from the block table)
@@ -120,7 +118,7 @@ int mips_launch_write_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_
     else
         hipLaunchKernelGGL(pack_rows_kernel<false>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, nseg, row_offset, (char *)tiled,
                            NoStamp{});
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // Scattered in-place updates (emdr2_mips_update_rows_scattered): pack_rows_kernel with the destination row read from row_ids.  Entries whose
@@ -167,7 +165,7 @@ int mips_launch_write_rows_at(const void *rows_rm, const int64_t *row_ids, int64
     else
         hipLaunchKernelGGL(pack_rows_at_kernel<false>, grid, dim3(256), 0, stream, (const uint4 *)rows_rm, row_ids, n_upd, nseg, n_rows_total,
                            (char *)tiled, claimed, n_touched, touched, cap, NoStamp{});
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t row_offset, void *tiled,
@@ -179,7 +177,7 @@ int mips_launch_pack_rows(const void *rows_rm, int64_t n_chunk, int dim, int64_t
     int nb = (int)((n_chunk + 3) / 4);
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(row_norm_max_kernel, dim3(nb), dim3(256), 0, stream, (const uint4 *)rows_rm, n_chunk, dim / 8, emax_sq);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // The one gather out of the image (emdr2_mips_unpack_rows: row_base 0; emdr2_mips_gather_rows: global rows): output row r is image row
@@ -206,7 +204,7 @@ int mips_launch_unpack_rows(const void *tiled, int64_t n_rows, int dim, int64_t 
     if (total == 0) return 0;
     hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const char *)tiled, nseg,
                        n_rows, row_base, row_ids, n_out, (uint4 *)rows_rm);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -288,7 +286,7 @@ int mips_launch_generation_stats(const uint32_t *generation, int64_t n_rows, int
         hipLaunchKernelGGL(generation_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, generation, n_rows, row_base, global_rows, n_items,
                            now, (unsigned long long *)report);
     }
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -320,7 +318,7 @@ int mips_launch_export_rows(const void *tiled, int dim, int64_t row_offset, int6
     const int64_t items = groups * npairs * 64;
     hipLaunchKernelGGL(export_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const char *)tiled, nch, npairs,
                        row_offset, row_offset + n_chunk, items, (uint4 *)rows_rm);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // g(r), h(r) and the stripe walk are stated once, in mips_digest.h; here the walk's sink folds the rows of [row_lo, row_hi) into the
@@ -360,7 +358,7 @@ int mips_launch_digest_rows(const void *tiled, int dim, int64_t row_offset, int6
     const int64_t first = row_offset / STRIPE_ROWS, last = (row_offset + n_chunk - 1) / STRIPE_ROWS;
     hipLaunchKernelGGL(digest_rows_kernel, dim3((unsigned)(last - first + 1)), dim3(256), 0, stream, (const char *)tiled, dim / 32, first, row_offset,
                        row_offset + n_chunk, row_base, (unsigned long long *)digest);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // The digest of the generation stamps of rows [row_lo, row_hi) (emdr2_mips_digest_stamps): h(r) of include/emdr2_mips.h, summed and xor-ed.
@@ -411,7 +409,7 @@ int mips_launch_digest_stamps(const uint32_t *generation, int64_t row_offset, in
     blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
     hipLaunchKernelGGL(digest_stamps_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, generation, row_offset, row_hi, body_lo, n_vec, row_base,
                        (unsigned long long *)digest);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -510,7 +508,7 @@ __global__ void pack_queries_frag_kernel(const uint4 *__restrict__ queries, int 
 int mips_launch_pack_queries_frag(const void *queries, int n_q, int dim, void *q_frag, hipStream_t stream)
 {
     hipLaunchKernelGGL(pack_queries_frag_kernel, dim3(512), dim3(64), 0, stream, (const uint4 *)queries, n_q, dim / 8, (char *)q_frag);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_prepare(const PrepareParams &p, hipStream_t stream)
@@ -518,7 +516,7 @@ int mips_launch_prepare(const PrepareParams &p, hipStream_t stream)
     if (p.tau && ((p.n_zero & 3) || ((uintptr_t)p.zero & 15) || (p.n_zero && !p.zero))) return -1;
     if (p.q8_tiled && (p.dim % 16)) return -1;
     hipLaunchKernelGGL(prepare_kernel, dim3(p.bn), dim3(64), p.q8_tiled ? (size_t)p.dim * 2 : 0, stream, p);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -681,7 +679,7 @@ int mips_launch_select(uint2 *cand, unsigned *count, uint2 *cand8, unsigned *cou
                        hipStream_t stream)
 {
     hipLaunchKernelGGL(select_kernel, dim3(n_q), dim3(256), 0, stream, cand, count, cand8, count8, tau, flags, capq, kp);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -884,7 +882,7 @@ int mips_launch_finalize(const FinalizeParams &p, bool select_first, hipStream_t
     if (p.pend) hipLaunchKernelGGL(finalize_kernel<2>, dim3(p.n_q), dim3(FINISH_THREADS), 0, stream, p);
     else if (select_first) hipLaunchKernelGGL(finalize_kernel<1>, dim3(p.n_q), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(finalize_kernel<0>, dim3(p.n_q), dim3(256), 0, stream, p);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -957,7 +955,7 @@ static int launch_merge(Source in, int n_shards, int n_q, int k, void *out_dist,
     if (n_shards * k > MERGE_MAX) return -4;
     hipLaunchKernelGGL((merge_kernel<Fmt, Source>), dim3(n_q), dim3(256), 0, stream, in, n_shards, n_q, k, (typename Fmt::stored_t *)out_dist, out_idx,
                        out_row);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_merge(const void *dist_in, const int32_t *idx_in, const int64_t *row_in, int n_shards, int n_q, int k, int f32, void *out_dist,
@@ -991,7 +989,7 @@ int mips_launch_pack_records(const void *dist, const int32_t *idx, const int64_t
 {
     if (n_sel < 1) return 0;
     hipLaunchKernelGGL(pack_records_kernel, dim3(n_sel), dim3(128), 0, stream, dist, idx, row, sel, k, f32, rec);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1055,7 +1053,7 @@ static int launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, con
     if (nb > 8192) nb = 8192;
     hipLaunchKernelGGL(exact_scores_kernel<Fmt>, dim3((unsigned)nb), dim3(256), (size_t)n_sel * dim * sizeof(int), stream, e_tiled, n_rows, dim,
                        queries, sel, n_sel, (typename Fmt::key_t *)keys);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_exact_scores(const char *e_tiled, int64_t n_rows, int dim, const uint16_t *queries, const int32_t *sel, int n_sel, int f32, void *keys,
@@ -1156,7 +1154,7 @@ static int launch_exact_select(const void *keys, int64_t n_rows, int64_t row_bas
 {
     hipLaunchKernelGGL(exact_select_kernel<Fmt>, dim3(n_sel), dim3(XS_THREADS), 0, stream, (const typename Fmt::key_t *)keys, n_rows, row_base, sel, k,
                        ids, (typename Fmt::stored_t *)out_dist, out_idx, out_row, flags);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 int mips_launch_exact_select(const void *keys, int64_t n_rows, int64_t row_base, const int32_t *sel, int n_sel, int k, const int32_t *ids, int f32,

@@ -20,8 +20,6 @@
 #include "mips_kernels.h"
 #include "mips_digest.h"
 
-#define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
-
 enum { SLAB_WORDS = 5 };    // per slab: rows changed, sum g, xor g, sum h, xor h
 
 struct DeltaWorkspace {
@@ -82,7 +80,7 @@ int mips_launch_row_keys(const void *tiled, int dim, int64_t row_offset, int64_t
     const int64_t first = row_offset / STRIPE_ROWS, last = (row_offset + n_chunk - 1) / STRIPE_ROWS;
     hipLaunchKernelGGL(row_keys_kernel, dim3((unsigned)(last - first + 1)), dim3(256), 0, stream, (const char *)tiled, dim / 32, first, row_offset,
                        row_offset + n_chunk, row_base, generation, keys);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }
 
 // The comparing sink.  Only the 64 lanes that finish rows call it, twice each (rows ri and 64 + ri of the stripe): the changed bits are
@@ -232,5 +230,5 @@ int mips_launch_changed_rows(const void *tiled, int64_t n_rows, int dim, int64_t
     }
     hipLaunchKernelGGL(changed_write_kernel, dim3((unsigned)(n_slabs ? n_slabs : 1)), dim3(256), 0, stream, n_stripes, slab, n_slabs, row_base, cap, ws,
                        out_rows, (unsigned long long *)out_info);
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }

@@ -1,12 +1,8 @@
 // emdr2_amd/csrc/mips_device.h -- device helpers shared by the MIPS kernels (gfx950 only).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "prims.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 #define STRIPE_ROWS 128
 #define CHUNK_K 32

@@ -393,7 +393,7 @@ static int launch_scan_t(const ScanParams &p, int grid, hipStream_t stream)
     constexpr int LDS = NST * STAGE + QCAP * 16 + 16;
     if (lds_opt_in<mips_scan_kernel<WM, WN, MODE, ABL>>(LDS) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL((mips_scan_kernel<WM, WN, MODE, ABL>), dim3(grid), dim3(512), LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 #ifdef EMDR2_EXPERIMENTS

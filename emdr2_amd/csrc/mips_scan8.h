@@ -375,7 +375,7 @@ int s8_launch(typename OPS::Params &P, int bn, int64_t row_begin, int64_t row_en
     constexpr int LDS = 2 * S8_BUF + S8_QCAP * 16 + 128;
     if (lds_opt_in<mips_scan8_kernel<OPS>>(LDS) != LDS_OPT_IN_OK) return -3;
     hipLaunchKernelGGL(mips_scan8_kernel<OPS>, dim3(grid), dim3(512), LDS, stream, P);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 } // namespace

@@ -193,7 +193,7 @@ int mips_launch_seal_shadow(const void *tiled, int dim, int64_t first_block, int
     if (n_blocks == 0) return 0;
     hipLaunchKernelGGL(seal_shadow_kernel<BlockRange>, dim3((unsigned)n_blocks), dim3(256), 0, stream, (const char *)tiled, dim / 32, BlockRange{first_block},
                        (char *)e8, (float4 *)blk, nonfinite);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *touched, const unsigned *n_touched, unsigned grid, void *e8, float *blk,
@@ -202,7 +202,7 @@ int mips_launch_seal_shadow_list(const void *tiled, int dim, const unsigned *tou
     if (grid == 0) return 0;
     hipLaunchKernelGGL(seal_shadow_kernel<BlockList>, dim3(grid), dim3(256), 0, stream, (const char *)tiled, dim / 32, BlockList{touched, n_touched},
                        (char *)e8, (float4 *)blk, nonfinite);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, const float *blk, const float *qc, void *pend, unsigned *pcount,
@@ -210,7 +210,7 @@ int mips_launch_triage(const ScanParams &p, const void *queries, unsigned pre, c
 {
     hipLaunchKernelGGL(triage_kernel, dim3(9, p.n_q), dim3(256), 0, stream, p.e_tiled, (const uint4 *)queries, p.nch * 4, p.cand, p.count, p.cand8,
                        p.count8, p.capq, pre, (const float4 *)blk, (const float4 *)qc, p.tau, (uint2 *)pend, pcount, margin);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return LAUNCH_OK();
 }
 
 // Filter scan (mode 0) of rows [row_begin, row_end) on the shadow image, for a query image of `bn` = 256 or 512 rows; `p` is the fp16 scan's

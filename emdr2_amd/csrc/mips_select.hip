@@ -26,8 +26,6 @@
 // does the same).
 #include "mips_kernels.h"
 
-#define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
-
 enum {
     SEL_THREADS = 256,
     SEL_CHUNK = 4 * SEL_THREADS,           // rows a workgroup takes at a time: four per thread
@@ -279,5 +277,5 @@ int mips_launch_oldest_rows(const uint32_t *generation, int64_t n_rows, int64_t 
         }
         hipLaunchKernelGGL(oldest_write_kernel, grid, block, 0, stream, generation, n_rows, slab, row_base, want, (const unsigned *)ws, out_rows, info);
     }
-    return CHECK_LAUNCH();
+    return LAUNCH_OK();
 }

@@ -11,13 +11,10 @@
 // GEMMs, LayerNorm and the epilogues see a [T, H] matrix with T = cu[n] rounded up to a multiple of 256 (tail rows are zeros); the
 // attention kernels take cu (csrc/attention.hip); the kernels here build the layout and move rows between the two forms.
 #include "../../include/emdr2_ops.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "prims.h"
 #include "device_attr.h"
 
 namespace {
-
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -3)
 
 // Two launches.  seq_len_kernel: a wave per sequence (ballot over 64-token chunks), 16 sequences per workgroup, len[i] -> cu[i] (the
 // 13 MB of ids of a 3,200 x 512 block go through the whole chip, not through one CU).  seq_lengths_kernel: ONE workgroup turns the lengths

@@ -1,6 +1,7 @@
 """Thin torch-tensor wrappers over the C ABI of include/emdr2_ops.h (libemdr2_hip.so) and the autograd glue that
 chains them.  No torch compute lives here: every FLOP and every byte moved on the model path goes through a hand-written HIP
 kernel; torch provides storage, views, the autograd tape and streams.  There is no CPU fallback (a missing library raises)."""
+import ctypes
 import math
 
 import torch
@@ -95,12 +96,18 @@ def matmul_nt(a, b, out_dtype=BF16, **kw):
     return gemm_nt(a, K, b, K, c, N, M, N, K, **kw)
 
 
+def _reduction_split(N, Kd, M):
+    """Slices of the token reduction of a weight gradient dW [N, Kd] over M tokens: few 256 x 256 output tiles -> fill the chip (~512 workgroups)
+    with slices of at least 4096 tokens.  A function of the shape alone (the ordered sums rest on that)."""
+    tiles = ((N + 255) // 256) * ((Kd + 255) // 256)
+    return max(1, min(512 // max(tiles, 1), M // 4096))
+
+
 def weight_grad_nt(dyT, xT):
     """dW [N, K] fp32 = dyT [N, M] @ xT [K, M]^T : few output tiles, reduction over all tokens -> split the reduction across the chip."""
     N, M = dyT.shape
     Kd = xT.shape[0]
-    tiles = ((N + 255) // 256) * ((Kd + 255) // 256)
-    split = max(1, min(512 // max(tiles, 1), M // 4096))
+    split = _reduction_split(N, Kd, M)
     if split == 1:
         return matmul_nt(dyT, xT, out_dtype=torch.float32)
     c = torch.zeros((N, Kd), dtype=torch.float32, device=dyT.device)
@@ -120,7 +127,6 @@ class _OrderedGrads(object):
         self.max_split = 0                               # largest split the weight-gradient GEMM took while enabled
 
     def workspace(self, nbytes, device):
-        import ctypes
         key = (device, torch.cuda.current_stream(device).cuda_stream)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
@@ -139,7 +145,6 @@ ORDERED = _OrderedGrads()
 
 
 def _ws_bytes(fn, *args):
-    import ctypes
     n = ctypes.c_size_t()
     _native.check(fn(*(args + (ctypes.byref(n),))), "ordered workspace size")
     return n.value
@@ -153,10 +158,9 @@ def weight_grad_tn(dy, x, colsum=None, into=None):
     through per-slice slabs and are added in slice order (emdr2_gemm_tn_bf16_ordered): no atomics, `into` taken whatever the split."""
     M, N = dy.shape
     Kd = x.shape[1]
-    tiles = ((N + 255) // 256) * ((Kd + 255) // 256)
-    split = max(1, min(512 // max(tiles, 1), M // 4096))
+    split = _reduction_split(N, Kd, M)
     if ORDERED.enabled:
-        # the same split, from the shape alone; the ordered entry ADDS its total (one add per element), so `into` is taken whatever the split
+        # the ordered entry ADDS its total (one add per element), so `into` is taken whatever the split
         ORDERED.max_split = max(ORDERED.max_split, split)
         c = into if into is not None else torch.zeros((N, Kd), dtype=torch.float32, device=dy.device)
         ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_gemm_tn_ordered_ws_bytes, N, Kd, M, split), dy.device)
@@ -313,7 +317,7 @@ FANIN = _FanInTable()
 
 class _PreMask(object):
     """The backward of a bias-dropout-add (y = x + dropout(z)) needs dy o mask as the operand of two GEMMs.  `dy` is produced by the backward of
-    the LayerNorm that consumed y, so that launch can write the masked copy on its way (csrc/elementwise.hip: layernorm_bwd768_kernel<true>)
+    the LayerNorm that consumed y, so that launch can write the masked copy on its way (csrc/layernorm.hip: layernorm_bwd768_kernel<true>)
     instead of a dropout launch re-reading dy.  Forward: the bias-dropout-add registers (p, seed) under its output's address (`want`);
     backward: the LayerNorm backward whose INPUT has that address leaves (dx ITSELF, p, seed) -> masked tensor in the one `slot`; the
     bias-dropout-add's backward takes it if its dy IS that dx (same storage, same shape, not written since) with the same (p, seed), and
@@ -679,12 +683,7 @@ class LayerNormFn(torch.autograd.Function):
         _check_bf16(x)
         H = x.shape[-1]
         x2 = x.reshape(-1, H)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        _native.check(_lib().emdr2_layernorm_fwd(x2.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                 rows, H, eps, _sp()), "layernorm_fwd")
+        y, mean, rstd = _ln_forward(x2, gamma, beta, eps)
         ctx.save_for_backward(x2, mean, rstd)
         ctx.gamma, ctx.beta = gamma, beta
         if passthrough:
@@ -717,34 +716,27 @@ def _ln_backward(dy2, x2, gamma, beta, mean, rstd, dres):
     dx = torch.empty_like(x2)
     (dg, dg_direct), (db, db_direct) = _grad_buffer(gamma), _grad_buffer(beta)            # the kernel adds its column sums atomically
     req = PREMASK.request_for(x2)          # x2 is the output of a bias-dropout-add whose backward runs next and wants dx o mask
-    rc = -4
-    if ORDERED.enabled:                    # the same dx / dmask bits; the column sums go through the workspace in a fixed order
-        ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_layernorm_bwd_ordered_ws_bytes, rows, H), x2.device)
-        args = (dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                rows, H)
-        if req is not None:
-            dmask = torch.empty_like(x2)
-            rc = _lib().emdr2_layernorm_bwd_ordered(*(args + (dmask.data_ptr(), req[0], req[1], ws, nws, _sp())))
-            if rc == 0:
-                PREMASK.offer(dx, req[0], req[1], dmask)
-            elif rc != -4:
-                _native.check(rc, "layernorm_bwd_ordered")
-        if rc == -4:
-            _native.check(_lib().emdr2_layernorm_bwd_ordered(*(args + (None, 0.0, 0, ws, nws, _sp()))), "layernorm_bwd_ordered")
-        _deliver_grad(gamma, dg, dg_direct)
-        _deliver_grad(beta, db, db_direct)
-        return dx
+    args = (dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, H)
+    # ordered: the same dx / dmask bits; the column sums go through the workspace in a fixed order
+    ws = ORDERED.workspace(_ws_bytes(_lib().emdr2_layernorm_bwd_ordered_ws_bytes, rows, H), x2.device) if ORDERED.enabled else None
+
+    def run(dmask, drop_p, seed):          # dmask None: dx alone
+        if ws is not None:
+            return _lib().emdr2_layernorm_bwd_ordered(*(args + (dmask, drop_p, seed) + ws + (_sp(),))), "layernorm_bwd_ordered"
+        if dmask is None:
+            return _lib().emdr2_layernorm_bwd(*(args + (_sp(),))), "layernorm_bwd"
+        return _lib().emdr2_layernorm_bwd_mask(*(args + (dmask, drop_p, seed, _sp()))), "layernorm_bwd_mask"
+
+    rc = -4                                # -4: this shape has no kernel that writes the masked copy (or none was asked for)
     if req is not None:
         dmask = torch.empty_like(x2)
-        rc = _lib().emdr2_layernorm_bwd_mask(dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(),
-                                             dg.data_ptr(), db.data_ptr(), rows, H, dmask.data_ptr(), req[0], req[1], _sp())
+        rc, name = run(dmask.data_ptr(), req[0], req[1])
         if rc == 0:
             PREMASK.offer(dx, req[0], req[1], dmask)
         elif rc != -4:
-            _native.check(rc, "layernorm_bwd_mask")
+            _native.check(rc, name)
     if rc == -4:
-        _native.check(_lib().emdr2_layernorm_bwd(dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres),
-                                                 dx.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, H, _sp()), "layernorm_bwd")
+        _native.check(*run(None, 0.0, 0))
     _deliver_grad(gamma, dg, dg_direct)
     _deliver_grad(beta, db, db_direct)
     return dx
@@ -952,7 +944,6 @@ def _splitkv_plan(batch, heads, sq, sk):
     key = (batch, heads, sq, sk)
     plan = _SPLITKV_PLANS.get(key)
     if plan is None:
-        import ctypes
         ks, fb, bb = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
         _native.check(_lib().emdr2_attention_splitkv_plan(batch, heads, sq, sk, ctypes.byref(ks), ctypes.byref(fb), ctypes.byref(bb)), "attention_splitkv_plan")
         plan = _SPLITKV_PLANS[key] = (ks.value, fb.value, bb.value)
@@ -1273,23 +1264,24 @@ class EmbeddingFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, types, W, P, T, drop_p=0.0, seed=0, seqs=None):
         H = W.shape[1]
-        lib = _lib()
         if seqs is not None:                                     # packed rows: ids / types come from the layout, positions from its row map
-            ids, types, S = seqs.ids, seqs.types, seqs.S
+            ids, types = seqs.ids, seqs.types
             if types is not None and T is None:
                 raise ValueError("the packed layout carries token types but no type table was passed")
-            out = torch.empty((seqs.rows, H), dtype=BF16, device=ids.device)
-            _native.check(lib.emdr2_embedding_packed_fwd(ids.data_ptr(), _ptr(types), seqs.rowmap.data_ptr(), w_bf16(W).data_ptr(), w_bf16(P).data_ptr(),
-                                                         w_bf16(T).data_ptr() if types is not None else None, out.data_ptr(), seqs.rows, S, H,
-                                                         float(drop_p), int(seed), _sp()), "embedding_packed_fwd")
+            # the layout of the rows, for both directions: (row offsets of the sequences, sequences, rows, positions per sequence)
+            layout, shape = (seqs.cu.data_ptr(), seqs.n, seqs.rows, seqs.S), (seqs.rows, H)
         else:
-            b, s = ids.shape
-            out = torch.empty((b, s, H), dtype=BF16, device=ids.device)
-            ids = ids.contiguous()
-            types = types.contiguous() if types is not None else None
-            _native.check(lib.emdr2_embedding_fwd(ids.data_ptr(), _ptr(types), w_bf16(W).data_ptr(), w_bf16(P).data_ptr(),
-                                                  w_bf16(T).data_ptr() if types is not None else None, out.data_ptr(), b * s, s, H, float(drop_p),
-                                                  int(seed), _sp()), "embedding_fwd")
+            ids, types = ids.contiguous(), types.contiguous() if types is not None else None
+            layout, shape = (None, ids.shape[0], ids.numel(), ids.shape[1]), tuple(ids.shape) + (H,)
+        cu, nseq, rows, S = layout
+        out = torch.empty(shape, dtype=BF16, device=ids.device)
+        tables = (w_bf16(W).data_ptr(), w_bf16(P).data_ptr(), w_bf16(T).data_ptr() if types is not None else None)
+        tail = (out.data_ptr(), rows, S, H, float(drop_p), int(seed), _sp())
+        if seqs is not None:
+            _native.check(_lib().emdr2_embedding_packed_fwd(*((ids.data_ptr(), _ptr(types), seqs.rowmap.data_ptr()) + tables + tail)), "embedding_packed_fwd")
+        else:
+            _native.check(_lib().emdr2_embedding_fwd(*((ids.data_ptr(), _ptr(types)) + tables + tail)), "embedding_fwd")
+        ctx.layout = layout
         ctx.ids, ctx.types, ctx.W, ctx.P, ctx.T, ctx.drop_p, ctx.seed, ctx.seqs = ids, types, W, P, T, drop_p, seed, seqs
         return out
 
@@ -1300,26 +1292,20 @@ class EmbeddingFn(torch.autograd.Function):
         dout = dout.contiguous()
         (dW, dW_direct), (dP, dP_direct) = _grad_buffer(W), _grad_buffer(P)            # the kernels scatter-add their rows atomically
         dT, dT_direct = _grad_buffer(T) if types is not None else (None, False)
+        cu, nseq, rows, S = ctx.layout
+        nt = T.shape[0] if dT is not None else 0
+        grads = (dout.data_ptr(), dW.data_ptr(), dP.data_ptr(), _ptr(dT))
+        tail = (rows, S, H, nt, float(ctx.drop_p), int(ctx.seed))
         if ORDERED.enabled:
             # the inverted index of the word rows: a stable sort puts each vocabulary row's tokens together, in ascending token index
-            if seqs is not None:
-                flat, cu, nseq, rows, S = ids, seqs.cu.data_ptr(), seqs.n, seqs.rows, seqs.S
-            else:
-                flat, cu, nseq, rows, S = ids, None, ids.shape[0], ids.numel(), ids.shape[1]
-            order = torch.sort(flat.reshape(-1)[:rows], stable=True)[1]
-            nt = T.shape[0] if dT is not None else 0
-            ws, nws = ORDERED.workspace(_ws_bytes(_lib().emdr2_embedding_bwd_ordered_ws_bytes, rows, nseq, S, H, nt), dout.device)
-            _native.check(_lib().emdr2_embedding_bwd_ordered(flat.data_ptr(), _ptr(types), cu, nseq, order.data_ptr(), dout.data_ptr(), dW.data_ptr(),
-                                                             dP.data_ptr(), _ptr(dT), rows, S, H, nt, float(ctx.drop_p), int(ctx.seed), ws, nws, _sp()),
+            order = torch.sort(ids.reshape(-1)[:rows], stable=True)[1]
+            ws = ORDERED.workspace(_ws_bytes(_lib().emdr2_embedding_bwd_ordered_ws_bytes, rows, nseq, S, H, nt), dout.device)
+            _native.check(_lib().emdr2_embedding_bwd_ordered(*((ids.data_ptr(), _ptr(types), cu, nseq, order.data_ptr()) + grads + tail + ws + (_sp(),))),
                           "embedding_bwd_ordered")
         elif seqs is not None:
-            _native.check(_lib().emdr2_embedding_packed_bwd(ids.data_ptr(), _ptr(types), seqs.cu.data_ptr(), seqs.n, dout.data_ptr(), dW.data_ptr(),
-                                                            dP.data_ptr(), _ptr(dT), seqs.rows, seqs.S, H, T.shape[0] if dT is not None else 0,
-                                                            float(ctx.drop_p), int(ctx.seed), _sp()), "embedding_packed_bwd")
+            _native.check(_lib().emdr2_embedding_packed_bwd(*((ids.data_ptr(), _ptr(types), cu, nseq) + grads + tail + (_sp(),))), "embedding_packed_bwd")
         else:
-            b, s = ids.shape
-            _native.check(_lib().emdr2_embedding_bwd(ids.data_ptr(), _ptr(types), dout.data_ptr(), dW.data_ptr(), dP.data_ptr(), _ptr(dT), b * s, s, H,
-                                                     T.shape[0] if dT is not None else 0, float(ctx.drop_p), int(ctx.seed), _sp()), "embedding_bwd")
+            _native.check(_lib().emdr2_embedding_bwd(*((ids.data_ptr(), _ptr(types)) + grads + tail + (_sp(),))), "embedding_bwd")
         _deliver_grad(W, dW, dW_direct)
         _deliver_grad(P, dP, dP_direct)
         if dT is not None:
@@ -1401,7 +1387,7 @@ def lm_head_gold_logprob(hidden, weight, bias, labels):
 
 
 class RetrieverPriorFn(torch.autograd.Function):
-    """topk_log_probs [B, K] = log_softmax_k(<q_b, c_bk> * scale) (emdr2_model.py:134-145) on the HIP kernel pair of elementwise.hip."""
+    """topk_log_probs [B, K] = log_softmax_k(<q_b, c_bk> * scale) (emdr2_model.py:134-145) on the HIP kernel pair of loss_tail.hip."""
 
     @staticmethod
     def forward(ctx, q, c, scale):

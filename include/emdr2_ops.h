@@ -49,7 +49,7 @@ int emdr2_gemm_tn_bf16(const void *A, int64_t lda, const void *B, int64_t ldb, f
  * the destination with ONE fp32 add per element per call: dst = dst + total.  The destination therefore holds zeros or earlier contributions
  * (no pre-zeroing contract), and two calls with the same arguments on the same data give the same bits.  Partial sums go through `ws`
  * (device memory, 16-byte aligned, at least *_ws_bytes; contents irrelevant before and after) and are finished by a second launch on the
- * same stream.  The order of each sum is written at its kernel (csrc/gemm_tn.hip, csrc/elementwise.hip, csrc/ordered_sum.h).  Not promised:
+ * same stream.  The order of each sum is written at its kernel (csrc/gemm_tn.hip, csrc/layernorm.hip, csrc/embedding.hip, csrc/ordered_sum.h).  Not promised:
  * equality with the atomic entries, across different split_k, or across different row counts.  -2: ws_bytes too small.
  *
  * emdr2_gemm_tn_bf16_ordered mirrors emdr2_gemm_tn_bf16 (same operands, same dispatch between the two kernels, same slices): C += A^T B and
@@ -101,7 +101,7 @@ int emdr2_layernorm_bwd_mask(const void *dy, const void *x, const float *gamma, 
  * un-dropped softmax); keep bit = keep(seed, row, k) of csrc/rng.h, row = (b * heads + n) * sq + q.
  * _bwd: dprobs -> dscores in place, d = rowsum(P*dP_eff).  With m, l given, `probs` holds the raw scaled scores and P is rebuilt from
  * the statistics (the forward need not keep the [sq, sk] probabilities); dropout requires that form.
- * _t: transposed twin for the attention backward: S^T -> dropped P^T, dP^T -> dS^T (see elementwise.hip). */
+ * _t: transposed twin for the attention backward: S^T -> dropped P^T, dP^T -> dS^T (see softmax.hip). */
 int emdr2_softmax_mask_fwd(void *scores, const int64_t *ids_q, const int64_t *ids_k, int batch, int heads, int sq, int sk, int causal,
                            float *m, float *l, float drop_p, uint32_t seed, void *stream);
 int emdr2_softmax_mask_bwd(const void *probs, void *dprobs, const int64_t *ids_q, const int64_t *ids_k, const float *m, const float *l,

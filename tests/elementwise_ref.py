@@ -1,6 +1,6 @@
-"""Float64 references, per-element structural bounds and input families for the kernels of csrc/elementwise.hip that are not attention:
-LayerNorm, log-softmax + gather, the LSE combine, the retriever prior, the EMDR2 marginal, the GELU derivative, AdamW (CPU and GPU tensors
-alike).  The pattern is that of tests/attention_ref.py, whose constants are imported, not restated.
+"""Float64 references, per-element structural bounds and input families for the row and elementwise kernels that are not attention (csrc/layernorm.hip,
+loss_tail.hip, elementwise.hip, optimizer.hip): LayerNorm, log-softmax + gather, the LSE combine, the retriever prior, the EMDR2 marginal, the
+GELU derivative, AdamW (CPU and GPU tensors alike).  The pattern is that of tests/attention_ref.py, whose constants are imported, not restated.
 
 Bounds.  An error is judged against the sum of the MAGNITUDES of the terms that make the value (never |value|, which can cancel, and never
 a whole-tensor maximum), times

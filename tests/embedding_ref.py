@@ -1,5 +1,5 @@
 """Float64 reference, per-element bounds, input families and a host restatement of the dropout bits for the embedding kernels of
-csrc/elementwise.hip (embedding_fwd_kernel dense and packed, embedding_bwd_kernel, embedding_bwd_pos_kernel, dropout_kernel) and their
+csrc/embedding.hip (embedding_fwd_kernel dense and packed, embedding_bwd_kernel, embedding_bwd_pos_kernel), dropout_kernel (csrc/elementwise.hip) and their
 fp32 twins in csrc/fp32_ops.hip -- CPU and GPU tensors alike.  The pattern is that of tests/attention_ref.py, tests/elementwise_ref.py and
 tests/gemm_ref.py, whose constants are imported, not restated.
 

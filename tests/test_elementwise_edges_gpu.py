@@ -67,8 +67,8 @@ What these tests found and what changed with them:
   * The centred pass of the 768 kernel first missed rstd by 1.2 bounds on the same near-constant rows, at outlier columns >= 512 only:
     with contraction on, the compiler had folded mean = s * (1 / 768) into the subtraction of 18 of a lane's 24 elements (an fma on the
     UNROUNDED product) and subtracted the rounded mean from the other 6, so the first-order cancellation of the mean's rounding error in
-    sum (x - mean)^2 was gone.  The mean is now one rounded product for all elements (mul_rounded in elementwise.hip): 0.04.
-  * lse_gather forward (elementwise.hip and fp32_ops.hip) read logits[row, label] unguarded: a label of -100 or >= V read a
+    sum (x - mean)^2 was gone.  The mean is now one rounded product for all elements (mul_rounded in prims.h): 0.04.
+  * lse_gather forward (loss_tail.hip and fp32_ops.hip) read logits[row, label] unguarded: a label of -100 or >= V read a
     neighbouring row (or outside the tensor on the first / last row).  Guarded: gold = -lse, as the fused LM head defines it.  The
     backward never matched such a label and was right: dlogits = -w softmax.
   * Nothing else: the persistent 768 backward on its second lap, its odd tails, the mask variant (dmask bit-equal to emdr2_dropout(dx),
@@ -225,7 +225,7 @@ LSE_CASES = [(fam, V, rows, False) for fam in R.LSE_FAMILIES for V in (1, 7, 255
 @pytest.mark.parametrize("fp32", [False, True])
 @pytest.mark.parametrize("fam,V,rows,out_of_range", LSE_CASES)
 def test_lse_gather(fam, V, rows, out_of_range, fp32):
-    """bf16 operands (elementwise.hip) and fp32 operands (fp32_ops.hip).  In-range labels: 0, V - 1, 255, 256 and a dominant column past
+    """bf16 operands (loss_tail.hip) and fp32 operands (fp32_ops.hip).  In-range labels: 0, V - 1, 255, 256 and a dominant column past
     255 (R.lse_inputs).  out_of_range: -100 and V + 7 on interior rows only, so that a read without the guard stays inside the logits and
     the case fails by value: gold = -lse, dlogits = -w softmax with a non-zero w on both rows."""
     from emdr2_amd.model import kernels as K

@@ -1,4 +1,4 @@
-"""The embedding family of csrc/elementwise.hip (embedding_fwd_kernel dense and packed, embedding_bwd_kernel, embedding_bwd_pos_kernel,
+"""The embedding family of csrc/embedding.hip (embedding_fwd_kernel dense and packed, embedding_bwd_kernel, embedding_bwd_pos_kernel,
 dropout_kernel) and its fp32 twin (csrc/fp32_ops.hip) against the float64 reference, the per-element bounds and the host restatement of
 the dropout bits of tests/embedding_ref.py (tests/test_embedding_ref_cpu.py shows what those bounds catch that max|a - r| / max|r| < 2e-2
 lets through).  Every case runs through the C ABI with dW / dP / dT PRE-FILLED by a sentinel pattern (after - before is judged on touched

@@ -1,4 +1,4 @@
-"""The optimizer kernels of csrc/elementwise.hip through the C ABI: the deterministic sum of squares every replica's clip factor rests on,
+"""The optimizer kernels of csrc/optimizer.hip through the C ABI: the deterministic sum of squares every replica's clip factor rests on,
 both Adam kernels against the float64 AdamW reference of tests/elementwise_ref.py (one step at a time from the kernel's own fp32 state,
 under per-element bounds), and the cast kernels of the gradient exchange bit for bit.
 

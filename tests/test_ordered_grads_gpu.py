@@ -22,7 +22,7 @@ from tests import ordered_grads_ref as R
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GUARD = 64
-CHUNK = 128                                    # EMB_CHUNK of csrc/elementwise.hip
+CHUNK = 128                                    # EMB_CHUNK of csrc/embedding.hip
 NAN_PAYLOAD = 0x7fc12345
 NEG_ZERO = 0x80000000
 

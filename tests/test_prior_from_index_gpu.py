@@ -1,4 +1,4 @@
-"""GPU: the retriever prior over fp16 contexts (kernels.retriever_prior_h16; csrc/elementwise.hip: the prior kernels instantiated for the
+"""GPU: the retriever prior over fp16 contexts (kernels.retriever_prior_h16; csrc/loss_tail.hip: the prior kernels instantiated for the
 index's element type).  With --context-embeddings-from-index the K contexts of a question are rows gathered from the evidence index: fp16
 constants, widened exactly inside the kernel -- not cast to bf16, which would drop three mantissa bits of every stored value.  The
 references are float64 torch computations of the same formula on the same bits."""

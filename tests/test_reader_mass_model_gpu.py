@@ -16,7 +16,7 @@ from tests.test_microbatch_gpu import _FixedRetriever, _cfg, _clear, _fb, _grads
 
 pytestmark = pytest.mark.gpu
 LAYERS, KK = 2, 3
-_ATOMIC = re.compile(r"layernorm\.(weight|bias)$|embeddings\.weight$")      # gradients accumulated by fp32 atomics (csrc/elementwise.hip)
+_ATOMIC = re.compile(r"layernorm\.(weight|bias)$|embeddings\.weight$")      # gradients accumulated by fp32 atomics (csrc/layernorm.hip, csrc/embedding.hip)
 
 
 def _case(flag=True, seed=7, B=4, S_ret=32, S=64, L=32, V=640, checkpoint=False, qext=None):
@@ -120,7 +120,7 @@ def test_flag_on_changes_no_logit_no_loss_and_no_gradient():
     for k in g0:
         if _ATOMIC.search(k):
             # LayerNorm weights / biases and the embedding tables: the blocks of their backward kernels add their partial sums into the
-            # gradient with fp32 atomics (csrc/elementwise.hip), in whatever order the blocks finish, so these gradients are not
+            # gradient with fp32 atomics (csrc/layernorm.hip, csrc/embedding.hip), in whatever order the blocks finish, so these gradients are not
             # bit-reproducible between two runs of the SAME code (measured on this very case, four runs with the flag off: 26 - 29 of
             # the 129 gradients differ from the first run, all of them of this kind, by 7e-9 .. 2e-7 of the tensor's largest value;
             # four runs with the flag on: 26 - 27, same tensors, same size).  The partial sums themselves are deterministic, so what
