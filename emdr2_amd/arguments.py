@@ -227,6 +227,17 @@ def get_parser():
                         'include/emdr2_ops.h) instead of fp32 atomics, so the same step from the same state gives the same bits.  Not '
                         'promised: equality with a run without the flag, across world sizes or across shapes that choose another split.  '
                         'Not with --fp32-validation.  Off: every launch is what it was')
+    g.add_argument('--skip-nonfinite-steps', action='store_true',
+                   help='(the reference: FP16_Optimizer skips a step on overflow, fp16/fp16.py:420-474, training.py:223-228) a step whose global '
+                        'gradient norm is NaN or Inf changes no weight, moment or working copy: decided and applied on the device (one '
+                        'small launch per step, no host read), the same on every data-parallel replica.  The iteration, the optimizer '
+                        'step count, the dropout step and the learning-rate schedule advance all the same.  The log line gains "number of '
+                        'skipped iterations" and "number of nan iterations", skipped steps stay out of the loss averages, and '
+                        '--index-writeback writes no row of a skipped step and no non-finite row.  Not with --fp32-validation.  Off: '
+                        'every launch is what it was')
+    g.add_argument('--max-consecutive-skipped-steps', type=int, default=0,
+                   help='with --skip-nonfinite-steps: end the run (RuntimeError on every rank, at a --log-interval boundary) once this many '
+                        'consecutive steps were skipped.  0: no limit')
     return p
 
 
@@ -290,6 +301,12 @@ def parse_args(argv=None):
     if args.deterministic_gradients and args.fp32_validation:
         raise ValueError("--deterministic-gradients orders the sums of the bf16 training path: it does not run with --fp32-validation "
                          "(the fp32 validation kernels keep their atomics)")
+    if args.skip_nonfinite_steps and args.fp32_validation:
+        raise ValueError("--skip-nonfinite-steps guards the optimizer step of the bf16 training path: it does not run with --fp32-validation")
+    if args.max_consecutive_skipped_steps < 0:
+        raise ValueError("--max-consecutive-skipped-steps must be >= 0")
+    if args.max_consecutive_skipped_steps and not args.skip_nonfinite_steps:
+        raise ValueError("--max-consecutive-skipped-steps needs --skip-nonfinite-steps (nothing is skipped without it)")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

@@ -49,7 +49,9 @@ def _cross_entropy_forward_step(batch, model, eos_id):
 
 
 def train_step(forward_step_func, data_iterator, model, optimizer, lr_scheduler, eos_id, dp_group=None, guard=None):
-    """megatron/training.py:202-230 without the fp16 machinery (bf16 needs no loss scale / overflow skip).  `guard` (training.RetentionGuard,
+    """megatron/training.py:202-230 without the loss scale (bf16 needs none).  The other half of the fp16 machinery, never applying a step
+    whose gradients are non-finite (fp16/fp16.py:420-474), is the optimizer's: FlatAdam(skip_nonfinite=True), --skip-nonfinite-steps,
+    decides it on the device, and the schedule below advances either way.  `guard` (training.RetentionGuard,
     built when --recompute-keep-last-layers / --selective-retention-layers ask for activations to be kept or --question-micro-batches
     splits the step): a step that runs out of HBM is run again on all ranks together, with a thinner retention plan / a finer split if
     need be, instead of ending the job."""
@@ -213,7 +215,8 @@ def _setup_model_and_optimizer(model_provider):
     from emdr2_amd.training import FlatAdam
     # flat buckets (masters, gradients, moments, bf16 working copies), no-decay grouping of model/utils.py:64-83 inside each bucket; it is
     # also the gradient sink of the backward: data-parallel buckets are exchanged in bf16 as soon as they are complete
-    optimizer = kernels.GRAD_SINK = FlatAdam(model, lr=args.lr, weight_decay=args.weight_decay, clip_grad=args.clip_grad)
+    optimizer = kernels.GRAD_SINK = FlatAdam(model, lr=args.lr, weight_decay=args.weight_decay, clip_grad=args.clip_grad,
+                                             skip_nonfinite=bool(getattr(args, 'skip_nonfinite_steps', False)))
     num_iters = args.lr_decay_iters if args.lr_decay_iters is not None else args.train_iters
     num_iters = max(1, num_iters)
     lr_scheduler = AnnealingLR(args.lr, warmup_iter=args.warmup * num_iters, total_iters=num_iters, min_lr=args.min_lr)
@@ -231,7 +234,7 @@ def _save(iteration, model, optimizer, lr_scheduler):
                                   barrier=torch.distributed.barrier if world > 1 else None, args=args)
 
 
-def index_writeback(model, batch_size, topk, generation=None, newest_wins=False):
+def index_writeback(model, batch_size, topk, generation=None, newest_wins=False, skipped=None):
     """--index-writeback, at a step boundary: the embeddings the step has just computed for the passages it retrieved
     (`EMDR2Model.take_writeback`) go into the index rows they were retrieved from (`update_rows_at`).  The list always has
     batch_size * topk entries, padded with row -1 (skipped): the short last batch of an epoch under --keep-last, empty retrieval slots,
@@ -240,7 +243,10 @@ def index_writeback(model, batch_size, topk, generation=None, newest_wins=False)
     -- and applies the gathered list to its own shard: rows of other shards fall out of range there.  A passage retrieved by several
     questions holds the embedding of the last (rank, question, slot) that names it, the same on every rank.  `generation` (an index with
     generation stamps: --index-generations): the stamp of the rows, the step count of the weights the forward ran with; `newest_wins`
-    (--index-newest-wins): rows that hold a newer stamp are left alone."""
+    (--index-newest-wins): rows that hold a newer stamp are left alone.  `skipped` (--skip-nonfinite-steps: FlatAdam.last_step_skipped, a
+    device bool): every entry of a skipped step, and any entry whose embedding holds a non-finite value, becomes row -1 before the
+    gather -- device arithmetic on a list of unchanged length, so the collectives are the same and no non-finite row enters the index
+    through this writer."""
     retriever = model.evidence_retriever
     dev = torch.device("cuda", torch.cuda.current_device())
     n = int(batch_size) * int(topk)
@@ -250,6 +256,8 @@ def index_writeback(model, batch_size, topk, generation=None, newest_wins=False)
     if kept is not None:
         rows[:kept[0].shape[0]] = kept[0]
         embeds[:kept[1].shape[0]] = kept[1]
+    if skipped is not None:
+        rows = torch.where(~torch.isfinite(embeds).all(1) | skipped, torch.full_like(rows, -1), rows)
     rank, world = retriever._world()
     if world > 1:
         all_rows = torch.empty((world * n,), dtype=rows.dtype, device=dev)
@@ -262,6 +270,22 @@ def index_writeback(model, batch_size, topk, generation=None, newest_wins=False)
         retriever.mips_index.update_rows_at(rows, embeds)
     else:
         retriever.mips_index.update_rows_at(rows, embeds, generation=generation, newest_wins=newest_wins)
+
+
+def skipped_step_line(report, iteration):
+    """--skip-nonfinite-steps, at a --log-interval boundary: the first step skipped since the last such line (FlatAdam.guard_report)."""
+    if report["parameter"] is None and not (report["nan"] or report["inf"]):
+        where = "the squared gradient norm overflowed fp32 over finite elements"
+    elif report["parameter"] is None:
+        where = "first non-finite gradient element in no parameter's slice"
+    else:
+        where = "first non-finite gradient element: %s[%d]" % (report["parameter"], report["element"])
+    return "skipped step at iteration %d: %s | NaN elements: %d | Inf elements: %d" % (iteration, where, report["nan"], report["inf"])
+
+
+def interval_average(total, log_interval, skipped):
+    """training.py:298-306: the average of an interval's losses over the steps that were applied."""
+    return total / max(1, log_interval - skipped)
 
 
 def writeback_generation(iteration):
@@ -383,6 +407,13 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
     start_iteration = args.iteration % args.train_iters_per_epoch
     iteration = args.iteration
     sums, t_last = {}, time.time()
+    # --skip-nonfinite-steps: the verdict of every step stays on the device (FlatAdam.last_step_skipped); the host learns the counts once
+    # per --log-interval (FlatAdam.guard_report)
+    skip_guard = optimizer if getattr(optimizer, "skip_nonfinite", False) else None
+    max_skips = int(getattr(args, "max_consecutive_skipped_steps", 0) or 0)
+    if skip_guard is not None:
+        nan_steps = torch.zeros((), dtype=torch.int64, device="cuda")
+        skipped_logged = skip_guard.guard_report(clear=False)["skipped_total"]
     for epoch in range(start_epoch, args.epochs):
         print_rank_0('working on epoch {} ...'.format(epoch + 1))
         train_dataloader.sampler.set_epoch(args.seed + epoch)
@@ -419,11 +450,12 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 # written-back row tens of steps later, with weights up to a pass older -- unless --index-newest-wins: the write-back stamps
                 # iteration - 1, the weights the forward ran with, the refresher the step count of its snapshot, and either leaves a row with
                 # a higher stamp alone
+                skipped = skip_guard.last_step_skipped if skip_guard is not None else None
                 if stamped is not None:
                     index_writeback(model, args.batch_size, args.topk_retrievals, generation=writeback_generation(iteration),
-                                    newest_wins=newest_wins)
+                                    newest_wins=newest_wins, skipped=skipped)
                 else:
-                    index_writeback(model, args.batch_size, args.topk_retrievals)
+                    index_writeback(model, args.batch_size, args.topk_retrievals, skipped=skipped)
             if retrieved_ages is not None:
                 index_generation_line(stamped, iteration, retrieved_ages)
             if audited is not None:
@@ -432,6 +464,13 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
             if snapshots is not None:
                 snapshots.pump()
                 snapshots.maybe_finalize(iteration)
+            if skip_guard is not None:
+                # training.py:240-315: a skipped step's losses stay out of the averages, and it counts as a "nan iteration" when their sum
+                # is itself non-finite -- here without asking the device for the verdict
+                skipped = skip_guard.last_step_skipped
+                vals = {k: torch.as_tensor(v, dtype=torch.float32, device=skipped.device) for k, v in losses.items()}
+                nan_steps += skipped & ~torch.isfinite(sum(v.sum() for v in vals.values()))
+                losses = {k: torch.where(skipped, torch.zeros_like(v), v) for k, v in vals.items()}
             for k, v in losses.items():
                 sums[k] = sums.get(k, 0.0) + v
             if iteration % args.log_interval == 0:
@@ -439,14 +478,29 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 t_last = time.time()
                 msg = ' iteration {:8d}/{:8d} | elapsed time per iteration (ms): {:.1f} | learning rate: {:.3E} |'.format(
                     iteration, args.train_iters, dt, lr_scheduler.get_lr())
+                skipped_now = 0
+                if skip_guard is not None:
+                    report = skip_guard.guard_report()             # the guard's one host read of the interval
+                    skipped_now = report["skipped_total"] - skipped_logged
+                    skipped_logged = report["skipped_total"]
                 for k in sums:
-                    msg += ' {}: {:.6E} |'.format(k, float(sums[k]) / args.log_interval)
+                    msg += ' {}: {:.6E} |'.format(k, interval_average(float(sums[k]), args.log_interval, skipped_now))
+                if skip_guard is not None:
+                    msg += ' number of skipped iterations: {:3d} | number of nan iterations: {:3d} |'.format(skipped_now, int(nan_steps))
+                    nan_steps.zero_()
                 if hit_tracker is not None:                   # (collective: every rank is here at the same iterations)
                     msg += hit_tracker.line()
                 if read_meter is not None:
                     msg += read_meter.line()
                 print_rank_0(msg)
                 sums = {}
+                if skip_guard is not None:
+                    if report["step"] is not None:
+                        print_rank_0(skipped_step_line(report, iteration - (optimizer.step_count - report["step"])))
+                    if 0 < max_skips <= report["longest_run"]:
+                        # every rank holds the same counts at the same iterations (FlatAdam: the verdict needs no collective)
+                        raise RuntimeError("%d consecutive optimizer steps had non-finite gradients and were skipped "
+                                           "(--max-consecutive-skipped-steps %d), seen at iteration %d" % (report["longest_run"], max_skips, iteration))
             if args.save and args.save_interval and iteration % args.save_interval == 0:
                 checkpoint(iteration)
             if args.eval_interval and iteration % args.eval_interval == 0 and end_of_epoch_callback is not None:

@@ -1,6 +1,7 @@
 """Optimizer step of the hot path (reference: megatron/training.py:73-230, megatron/fp16/fp16.py, apex FusedAdam, mpu/grads.py,
 megatron/model/distributed.py, megatron/learning_rates.py), bf16 edition: parameters ARE the fp32 masters, gradients arrive in fp32
-from the weight-gradient GEMMs, so there is no loss scaling, no overflow check and no master-copy round trip."""
+from the weight-gradient GEMMs, so there is no loss scaling and no master-copy round trip; the reference's other use of its overflow check,
+never applying a step with non-finite gradients, is FlatAdam(skip_nonfinite=True), decided on the device."""
 import torch
 
 from emdr2_amd import _native
@@ -101,16 +102,29 @@ class FlatAdam(object):
     its peers in a collective: it issues the bucket all-reduces it still owes (buckets always leave in index order), raises the abort
     flag, and every rank's `finish()` raises `StepAborted`.
 
-    Parameters that never receive a gradient (the reader's unused token-type table) are left untouched, like apex / torch skip `grad is None`."""
+    Parameters that never receive a gradient (the reader's unused token-type table) are left untouched, like apex / torch skip `grad is None`.
+
+    `skip_nonfinite=True` (--skip-nonfinite-steps; the reference: FP16_Optimizer._check_overflow and the early return of its step(),
+    fp16/fp16.py:294-302,420-474): a step whose global squared gradient norm is NaN or +-Inf after the last bucket's sum stores nothing
+    into masters, moments or working copies.  The verdict is one small launch between the norm and the Adam launches (the norm pass counts
+    the non-finite elements on its way), the Adam kernel reads it, and the host reads nothing: `step_count`, the dropout step and the
+    caller's schedule advance whether the step was applied or not.  `last_step_skipped` is the verdict as a device bool,
+    `guard_report()` the one host read.
+    INVARIANT: replicas need no collective to agree on the verdict.  After `finish()` every rank holds the same gradient buckets -- the
+    all-reduced bucket contents and the all-reduced late-contribution buffers added to them -- and the norm is summed in a fixed order
+    (block partials in index order, buckets in launch order), so every rank computes the same bits of the norm and reaches the same
+    verdict in the same step.  Whatever one rank's backward produced, NaN included, has reached every rank through the exchange."""
 
     def __init__(self, module, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, clip_grad=1.0, group=None, bucket_bytes=512 << 20,
-                 exchange_dtype="bf16"):
+                 exchange_dtype="bf16", skip_nonfinite=False):
         from emdr2_amd.model import kernels
         if exchange_dtype not in ("bf16", "fp32"):
             raise ValueError("exchange_dtype must be 'bf16' or 'fp32'")
         self.lr, self.betas, self.eps, self.weight_decay, self.clip_grad, self.group = lr, betas, eps, weight_decay, clip_grad, group
         self.exchange_dtype, self.pattern_changes = exchange_dtype, 0
         self.step_count = 0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.names = {p: n for n, p in module.named_parameters()}         # guard_report() names the first offender's tensor
         no_decay = set(id(p) for n, p in module.named_parameters() if self.is_no_decay(n))      # model/utils.py:64-83
         self.params = [p for p in module.parameters() if p.requires_grad][::-1]
         self.slot = {}
@@ -131,8 +145,14 @@ class FlatAdam(object):
         if not self.on_device and exchange_dtype != "fp32":
             raise _native.NativeError("FlatAdam on host tensors is the exchange bookkeeping only: exchange_dtype must be 'fp32' (the bf16 "
                                       "exchange and the optimizer step are HIP kernels)")
+        if self.skip_nonfinite and not self.on_device:
+            raise _native.NativeError("skip_nonfinite is decided and applied by HIP kernels (no host implementation)")
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._scratch = torch.zeros(1025, dtype=torch.float32, device=dev)
+        if self.skip_nonfinite:
+            # uint64 words held as int64 (bit patterns; include/emdr2_ops.h, "Step guard"): the census of the norm pass and the guard's state
+            self._census = torch.tensor([0, 0, -1, 0], dtype=torch.int64, device=dev)
+            self._guard_state = torch.zeros(8, dtype=torch.int64, device=dev)
         self._stale = False
         self.expected = None                  # {param: contributions per step}, learned in the first step
         self.count = {p: 0 for p in self.params}
@@ -390,22 +410,40 @@ class FlatAdam(object):
             self.finish()                                          # single-process use without an explicit finish()
         self.step_count += 1
         active = [b for b in self.buckets if any(self.count[p] for p in b["params"])]
+        guarded = self.skip_nonfinite
         if not active:
+            if guarded:                       # nothing to apply and nothing to skip: the verdict of this step is "applied" (norm 0)
+                self._gsq.zero_()
+                _native.check(lib.emdr2_step_verdict(self._gsq.data_ptr(), self._census.data_ptr(), self._guard_state.data_ptr(), self.step_count, sp),
+                              "step_verdict")
             return 0.0
         self._gsq.zero_()
         # parameters without a gradient this step are untouched by the update -- master AND both moments -- like `grad is None` in apex / torch
         saved = [(p, p.data.clone()) + tuple(t.clone() for t in self._moments(p)) for p in getattr(self, "inactive", [])]
         for b in active:
-            _native.check(lib.emdr2_sumsq_f32(b["grad"].data_ptr(), b["n"], self._gsq.data_ptr(), self._scratch.data_ptr(), sp), "sumsq")
+            if guarded:
+                _native.check(lib.emdr2_sumsq_census_f32(b["grad"].data_ptr(), b["n"], self._gsq.data_ptr(), self._scratch.data_ptr(),
+                                                         self._census.data_ptr(), b["idx"], sp), "sumsq_census")
+            else:
+                _native.check(lib.emdr2_sumsq_f32(b["grad"].data_ptr(), b["n"], self._gsq.data_ptr(), self._scratch.data_ptr(), sp), "sumsq")
+        if guarded:                           # ONE rule, decided once per step on the device: the Adam launches below read state[0]
+            _native.check(lib.emdr2_step_verdict(self._gsq.data_ptr(), self._census.data_ptr(), self._guard_state.data_ptr(), self.step_count, sp),
+                          "step_verdict")
         for b in active:
-            _native.check(lib.emdr2_adam_step_flat(b["master"].data_ptr(), b["grad"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), b["work"].data_ptr(),
-                                                   b["n"], b["split"], lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
-                                                   self._gsq.data_ptr(), self.clip_grad, sp), "adam_step_flat")
+            if guarded:
+                _native.check(lib.emdr2_adam_step_flat_guarded(b["master"].data_ptr(), b["grad"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(),
+                                                               b["work"].data_ptr(), b["n"], b["split"], lr, self.betas[0], self.betas[1], self.eps,
+                                                               self.weight_decay, self.step_count, self._gsq.data_ptr(), self.clip_grad,
+                                                               self._guard_state.data_ptr(), sp), "adam_step_flat_guarded")
+            else:
+                _native.check(lib.emdr2_adam_step_flat(b["master"].data_ptr(), b["grad"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), b["work"].data_ptr(),
+                                                       b["n"], b["split"], lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
+                                                       self._gsq.data_ptr(), self.clip_grad, sp), "adam_step_flat")
         for p, old, m_old, v_old in saved:
             p.data.copy_(old)
             m, v = self._moments(p)
             m.copy_(m_old); v.copy_(v_old)
-        self.launches_last_step += 1 + 2 * len(active) + 6 * len(saved)
+        self.launches_last_step += 1 + 2 * len(active) + 6 * len(saved) + (1 if guarded else 0)
         self.optimizer_launches = self.launches_last_step
         self.launches_last_step = 0
         self._stale = True                    # the gradient buckets are spent: the next contribution starts a new step if zero_grad() does not
@@ -417,6 +455,49 @@ class FlatAdam(object):
         kernels.DROPOUT.step = self.step_count
         return self._gsq
 
+    # ---- the step guard (skip_nonfinite) ---------------------------------------------------------------------------------------------------
+    NO_OFFENDER = (1 << 64) - 1               # first-offender key of a step whose sum overflowed over finite elements
+
+    @property
+    def last_step_skipped(self):
+        """The last step's verdict, a 0-dim device bool that aliases the guard's state (byte 0 of word 0, which holds 0 or 1): no host
+        read, and it changes under the caller at the next step()."""
+        return self._guard_state.view(torch.bool)[0]
+
+    def resolve_offender(self, key):
+        """(parameter name, element index inside that tensor) for a first-offender key `(bucket << 40) | index into the bucket`;
+        (None, None) for NO_OFFENDER and for an index no tensor owns (the zero padding between two tensors)."""
+        key = int(key) & self.NO_OFFENDER
+        if key == self.NO_OFFENDER:
+            return None, None
+        bucket, index = key >> 40, key & ((1 << 40) - 1)
+        for p in (self.buckets[bucket]["params"] if bucket < len(self.buckets) else ()):
+            _, o, n = self.slot[p]
+            if o <= index < o + n:
+                return self.names.get(p), index - o
+        return None, None
+
+    def report_from_words(self, words):
+        """The guard's eight state words (include/emdr2_ops.h, emdr2_step_verdict) as guard_report()'s dict."""
+        w = [int(x) & self.NO_OFFENDER for x in words]
+        rep = {"skipped_total": w[1], "consecutive": w[2], "longest_run": w[3], "step": None, "parameter": None, "element": None, "nan": 0, "inf": 0}
+        if w[4]:                              # the sticky record is set (steps count from 1)
+            name, element = self.resolve_offender(w[5])
+            rep.update(step=w[4], parameter=name, element=element, nan=w[6], inf=w[7])
+        return rep
+
+    def guard_report(self, clear=True):
+        """The guard's ONE host read: steps skipped in total, the current and the longest run of consecutive skips, and the sticky record of
+        the first skipped step since the record was last cleared -- its `step`, the `parameter` (name) and `element` of its first
+        non-finite gradient element (None, None when the sum overflowed over finite elements), its `nan` and `inf` element counts; `step`
+        is None when nothing was skipped since.  `clear`: empty the record, so that the next skip fills it."""
+        if not self.skip_nonfinite:
+            raise RuntimeError("guard_report() needs FlatAdam(skip_nonfinite=True)")
+        rep = self.report_from_words(self._guard_state.tolist())
+        if clear and rep["step"] is not None:
+            self._guard_state[4:8].zero_()
+        return rep
+
     # ---- checkpoint format of FusedAdam (moments in parameter order) ---------------------------------------------------------------------
     def _ordered(self):
         return self.params[::-1]
@@ -426,11 +507,17 @@ class FlatAdam(object):
         return b["m"][o:o + n].view(p.shape), b["v"][o:o + n].view(p.shape)
 
     def state_dict(self):
-        return {'step': self.step_count,
-                'state': {i: {'exp_avg': self._moments(p)[0], 'exp_avg_sq': self._moments(p)[1]} for i, p in enumerate(self._ordered())}}
+        sd = {'step': self.step_count,
+              'state': {i: {'exp_avg': self._moments(p)[0], 'exp_avg_sq': self._moments(p)[1]} for i, p in enumerate(self._ordered())}}
+        if self.skip_nonfinite:               # (guard off: the reference-pinned layout, unchanged)
+            sd['skipped_steps'] = int(self._guard_state[1])
+        return sd
 
     def load_state_dict(self, sd):
         self.step_count = sd['step']
+        if self.skip_nonfinite:               # a checkpoint written with the guard off has no count: 0
+            self._guard_state.zero_()
+            self._guard_state[1] = int(sd.get('skipped_steps', 0))
         ordered = self._ordered()
         for i, st in sd['state'].items():
             m, v = self._moments(ordered[int(i)])

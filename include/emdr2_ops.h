@@ -264,6 +264,28 @@ int emdr2_adam_step(float *master, const float *grad, float *m, float *v, void *
  * the weight decay, the rest none.  n, decay_split multiples of 4; fp32 buffers 16-byte aligned. */
 int emdr2_adam_step_flat(float *master, const float *grad, float *m, float *v, void *work_bf16, int64_t n, int64_t decay_split, float lr,
                          float beta1, float beta2, float eps, float weight_decay, int step, const float *gnorm_sq, float clip, void *stream);
+/* ---- Step guard (--skip-nonfinite-steps): a step whose global gradient norm is not finite stores nothing, decided and applied on the
+ * device.  Replaces FP16_Optimizer._check_overflow and the early return of FP16_Optimizer.step (fp16/fp16.py:294-302,420-474) and the
+ * skipped-iteration branch of train_step (training.py:223-228) -- without their host read of the overflow flag. */
+/* emdr2_sumsq_f32 with a census of the non-finite elements riding in the same pass (fp16/fp16.py:294-302 looks for them in a pass of its
+ * own): *out receives exactly the bits emdr2_sumsq_f32 gives for the same g, n and prior *out (same grid rule, same order of partials,
+ * same last-block sum).  census: device uint64[4], 8-byte aligned -- [0] += NaN elements, [1] += +-Inf elements, [2] = min([2], (bucket
+ * << 40) | index) over the non-finite elements (all ones: none), [3] reserved.  Integer atomics, at most one per census word and wave,
+ * none from a wave that saw finite elements only.  n < 2^40, 0 <= bucket < 2^23 (-1 otherwise). */
+int emdr2_sumsq_census_f32(const float *g, int64_t n, float *out, float *scratch, uint64_t *census, int bucket, void *stream);
+/* The verdict of step `step` (>= 1), one single-workgroup launch after the last bucket's census and before the first Adam launch
+ * (fp16/fp16.py:420-474 returns before the update; training.py:223-228 counts the skip): skipped exactly when *gnorm_sq is NaN or +-Inf.
+ * state: device uint64[8], zero before the first use -- [0] the verdict (0 applied, 1 skipped), [1] steps skipped in total, [2] current
+ * run of consecutive skips, [3] longest run, [4..7] the STICKY record of the first skipped step since the caller last zeroed these four
+ * words ([4] == 0: empty): its step, its first-offender key (census[2]; all ones when the sum overflowed over finite elements), its NaN
+ * and Inf counts.  Leaves the census ready for the next step: {0, 0, all ones, 0} -- which is also what the caller sets it to once. */
+int emdr2_step_verdict(const float *gnorm_sq, uint64_t *census, uint64_t *state, int64_t step, void *stream);
+/* emdr2_adam_step_flat under the verdict (fp16/fp16.py:420-474: no update on overflow): state[0] == 1 -- every thread returns before its
+ * first load of grad / m / v / master and nothing is stored; state[0] == 0 -- the arithmetic and the bits of emdr2_adam_step_flat (one
+ * kernel template).  state non-NULL, 8-byte aligned. */
+int emdr2_adam_step_flat_guarded(float *master, const float *grad, float *m, float *v, void *work_bf16, int64_t n, int64_t decay_split,
+                                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float *gnorm_sq,
+                                 float clip, const uint64_t *state, void *stream);
 /* Gradient exchange in 16 bits (the reference all-reduces fp16 gradients pre-divided by the world size, model/distributed.py:53-62):
  * dst = bf16(scale * src) before the all-reduce, dst = float(src) after it.  n % 4 == 0. */
 int emdr2_scale_cast_f32_to_bf16(const float *src, void *dst, int64_t n, float scale, void *stream);
