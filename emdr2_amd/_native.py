@@ -118,6 +118,9 @@ SIGNATURES.update({
     "emdr2_widen_bf16_to_f32": (_i32, [_vp, _vp, _i64, _vp]),
     "emdr2_cast_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "emdr2_accum_bf16_to_f32": (_i32, [_vp, _vp, _i64, _f32, _vp]),
+    # "State audit": master, m, v, work_bf16, n, block_keys, report, stream
+    "emdr2_state_audit_ws_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
+    "emdr2_state_audit": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 })
 
 

@@ -238,6 +238,16 @@ def get_parser():
     g.add_argument('--max-consecutive-skipped-steps', type=int, default=0,
                    help='with --skip-nonfinite-steps: end the run (RuntimeError on every rank, at a --log-interval boundary) once this many '
                         'consecutive steps were skipped.  0: no limit')
+    g.add_argument('--audit-optimizer-state-interval', type=int, default=0,
+                   help='(not in the reference; Megatron-LM: --check-weight-hash-across-dp-replicas-interval) audit the optimizer state '
+                        'before the first step and at every iteration divisible by N, at the step boundary before that boundary\'s '
+                        'checkpoint: one streaming HIP pass per bucket (csrc/state_audit.hip) over the fp32 masters, both Adam moments and '
+                        'the bf16 working copies counts non-finite elements, negative second moments and working copies that are not the '
+                        'rounding of their master, and digests the bit patterns; two small all-reduces compare the digests of the '
+                        'data-parallel replicas.  Rank 0 prints one line; an unsound state or a replica that differs raises RuntimeError on '
+                        'every rank, naming the array, the parameter and the element.  Checkpoints gain a digest that the next load '
+                        'verifies.  Promised: equal bits and the invariants, not right values.  Not with --fp32-validation.  0: never, '
+                        'every launch, log line and checkpoint byte is what it was')
     return p
 
 
@@ -307,6 +317,11 @@ def parse_args(argv=None):
         raise ValueError("--max-consecutive-skipped-steps must be >= 0")
     if args.max_consecutive_skipped_steps and not args.skip_nonfinite_steps:
         raise ValueError("--max-consecutive-skipped-steps needs --skip-nonfinite-steps (nothing is skipped without it)")
+    if args.audit_optimizer_state_interval < 0:
+        raise ValueError("--audit-optimizer-state-interval must be >= 0")
+    if args.audit_optimizer_state_interval and args.fp32_validation:
+        raise ValueError("--audit-optimizer-state-interval audits the buckets of the bf16 training path (fp32 masters against their bf16 working "
+                         "copies): it does not run with --fp32-validation")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

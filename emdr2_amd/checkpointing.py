@@ -164,6 +164,9 @@ def load_checkpoint(load_dir, model, optimizer=None, lr_scheduler=None):
         except (KeyError, TypeError, AttributeError) as exc:
             raise ValueError("the optimizer state of this checkpoint is not in this package's format (a reference FP16_Optimizer state?): "
                              "load the weights only with --no-load-optim (%r)" % (exc,))
+        if getattr(optimizer, 'audit_state', False) and 'state_digest' in state['optimizer']:
+            # --audit-optimizer-state-interval: masters (the model's parameters) and moments are in -- do they hash to what was saved?
+            optimizer.verify_state_digest(state['optimizer']['state_digest'])
         if lr_scheduler is not None and 'lr_scheduler' in state:      # the reference loads the schedule only together with the optimizer
             lr_scheduler.load_state_dict(state['lr_scheduler'])
     return state.get('iteration', iteration)

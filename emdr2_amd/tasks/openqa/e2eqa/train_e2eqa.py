@@ -216,7 +216,8 @@ def _setup_model_and_optimizer(model_provider):
     # flat buckets (masters, gradients, moments, bf16 working copies), no-decay grouping of model/utils.py:64-83 inside each bucket; it is
     # also the gradient sink of the backward: data-parallel buckets are exchanged in bf16 as soon as they are complete
     optimizer = kernels.GRAD_SINK = FlatAdam(model, lr=args.lr, weight_decay=args.weight_decay, clip_grad=args.clip_grad,
-                                             skip_nonfinite=bool(getattr(args, 'skip_nonfinite_steps', False)))
+                                             skip_nonfinite=bool(getattr(args, 'skip_nonfinite_steps', False)),
+                                             audit_state=int(getattr(args, 'audit_optimizer_state_interval', 0) or 0) > 0)
     num_iters = args.lr_decay_iters if args.lr_decay_iters is not None else args.train_iters
     num_iters = max(1, num_iters)
     lr_scheduler = AnnealingLR(args.lr, warmup_iter=args.warmup * num_iters, total_iters=num_iters, min_lr=args.min_lr)
@@ -349,6 +350,46 @@ def maybe_audit_index(index, iteration, interval):
     return True
 
 
+def optimizer_audit_failures(result):
+    """The non-zero counts of a FlatAdam.audit() result on the worst replica, each with its first offender: '' for a sound state.  Built
+    from all-reduced words, so every rank holds the same text."""
+    bad = []
+    for name, count in result["worst"].items():
+        if count:
+            parameter, element = result["worst_first"][name]
+            where = "%s[%d]" % (parameter, element) if parameter is not None else "bucket element %d (padding)" % element
+            bad.append("%s = %d (first: %s)" % (name, count, where))
+    return ", ".join(bad)
+
+
+def audit_optimizer_state(optimizer, iteration):
+    """--audit-optimizer-state-interval: one audit of the optimizer state (`FlatAdam.audit`: a streaming launch per bucket, two small
+    all-reduces over the data-parallel group, one host read; every rank holds the same result and takes the same decision).  Rank 0
+    prints one line; a replica that differs raises RuntimeError on every rank inside the audit, an unsound state here, naming the
+    non-zero counts and the first offender."""
+    torch.cuda.synchronize()
+    t0 = time.time()
+    result = optimizer.audit()                                  # (ends with its one host read: the time below is the audit's)
+    ms = (time.time() - t0) * 1000.0
+    bad = optimizer_audit_failures(result)
+    if bad:
+        print_rank_0("optimizer state audit at iteration %d: %d elements in %d buckets, FAILED: %s (%.2f ms)"
+                     % (iteration, result["elements"], result["buckets"], bad, ms))
+        raise RuntimeError("optimizer state audit failed at iteration %d: %s" % (iteration, bad))
+    print_rank_0("optimizer state audit at iteration %d: %d elements in %d buckets, sound, replicas identical (world %d) (%.2f ms)"
+                 % (iteration, result["elements"], result["buckets"], result["world"], ms))
+    return result
+
+
+def maybe_audit_optimizer_state(optimizer, iteration, interval):
+    """The step-boundary rule of --audit-optimizer-state-interval: audit at every iteration divisible by `interval`; 0 = never.  Whether
+    a boundary audits -- and so issues the audit's collectives -- depends on the iteration number alone.  -> whether it did."""
+    if interval <= 0 or iteration % interval:
+        return False
+    audit_optimizer_state(optimizer, iteration)
+    return True
+
+
 def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_of_epoch_callback, end_of_epoch_callback2, eos_id, indexer=None):
     """train_e2eqa.py:413-552.  `indexer`: an AsyncIndexBuilder when --async-indexer (re-indexing on a side stream; the swap at a step
     boundary replaces the NEW_INDEX_READY / NEW_CHKPT_READY handshake and the reload from disk)."""
@@ -399,6 +440,9 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
     audited = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if audit_interval > 0 else None
     if audited is not None:
         audit_index(audited, args.iteration)          # what was loaded or restored, before the first step searches it
+    state_audit_interval = int(getattr(args, "audit_optimizer_state_interval", 0) or 0)
+    if state_audit_interval > 0:
+        audit_optimizer_state(optimizer, args.iteration)          # what was initialised or loaded, before the first step runs on it
     stamped = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if getattr(args, "index_generations", False) else None
     newest_wins = bool(getattr(args, "index_newest_wins", False))
     hit_tracker = getattr(model, "answer_hits", None)        # --retrieval-answer-hits
@@ -425,6 +469,9 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
                 indexer.pump()
             losses = train_step(forward_step, batch, model, optimizer, lr_scheduler, eos_id, guard=guard)
             iteration += 1
+            if state_audit_interval > 0:
+                # right behind the step, before any checkpoint save of this boundary: a state that fails is never saved
+                maybe_audit_optimizer_state(optimizer, iteration, state_audit_interval)
             if hit_tracker is not None:
                 hit_tracker.commit()
             if read_meter is not None:

@@ -75,6 +75,76 @@ class StepAborted(RuntimeError):
     collectives, in the same order, on all ranks -- and its result is to be discarded by all of them together."""
 
 
+# ---- the state audit (include/emdr2_ops.h, "State audit"; FlatAdam.audit) -----------------------------------------------------------------
+AUDIT_WORDS = 18                              # the report of emdr2_state_audit, uint64 words held as int64 bit patterns
+AUDIT_BLOCK = 8192                            # elements per block key
+AUDIT_ARRAYS = ("master", "exp_avg", "exp_avg_sq")                       # digest order; words 11 + 2 a (sum) and 12 + 2 a (xor)
+AUDIT_CHECKS = ("nonfinite_master", "nonfinite_exp_avg", "nonfinite_exp_avg_sq", "negative_exp_avg_sq", "work_mismatch")   # words 1..5, firsts 6..10
+AUDIT_DIGEST = slice(11, 17)
+_AUDIT_BUCKET_KEY = {"master": "master", "exp_avg": "m", "exp_avg_sq": "v"}
+_U64 = (1 << 64) - 1
+
+
+def first_difference(lo, hi):
+    """Index of the first position at which two equally shaped integer tensors differ, None when they are equal.  Over the MIN and the MAX
+    of an all-reduce: the first word that is not the same on every rank."""
+    diff = (lo.reshape(-1) != hi.reshape(-1)).nonzero()
+    return int(diff[0]) if diff.numel() else None
+
+
+def first_digest_difference(lo, hi):
+    """(bucket, array index) of the first digest word that differs between the MIN and the MAX of the replicas' reports ([B, 18]); None when
+    every digest is the same everywhere."""
+    at = first_difference(lo[:, AUDIT_DIGEST], hi[:, AUDIT_DIGEST])
+    return None if at is None else (at // 6, (at % 6) // 2)
+
+
+def replica_mismatch_message(array, bucket, parameter, element, lo, hi):
+    """What every rank raises: MIN and MAX are the same everywhere, so the text is."""
+    where = "%s[%d]" % (parameter, element) if parameter is not None else "element %d of bucket %d (padding between two tensors)" % (element, bucket)
+    return "optimizer state differs between data-parallel replicas: %s of %s holds the bit patterns 0x%08x and 0x%08x" % (array, where, lo, hi)
+
+
+def compare_state_replicas(report, group=None, block_keys=None, block_bits=None, locate=None):
+    """Are the optimizer states of the data-parallel replicas the same bits?  `report`: this rank's audit words, int64 [B, 18], host or
+    device (FlatAdam.audit passes the device tensor; over gloo host tensors do).  Only all-reduces of int64 bit patterns with MIN and MAX:
+    a word is the same on every rank iff its minimum equals its maximum.
+    Level 1, always: the whole report -- every bucket's digests, and its counts and first offenders in the same round, so that every
+    rank learns the worst replica's counts and takes the same decision -- in TWO all-reduces.  (Counts are equal on identical replicas;
+    the maximum says whether any replica is unsound, which is all a sum would be asked.)
+    Level 2, only when a digest differs, and therefore on every rank together: the block keys `block_keys(bucket, array index)` of the
+    first differing (bucket, array), MIN and MAX -> the first differing block.
+    Level 3: that block's 32-bit patterns widened to int64, `block_bits(bucket, array index, block)`, MIN and MAX -> the first differing
+    element; `locate(bucket, index)` -> (parameter name or None, element).  Every rank raises the same RuntimeError.
+    Which collectives run depends on reduced values alone.  -> (local, minimum, maximum) as ONE host tensor [3, B, 18]: the call's one
+    host read when the replicas agree."""
+    dist = torch.distributed
+    lo, hi = report.clone(), report.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    words = torch.stack([report, lo, hi]).cpu()
+    where = first_digest_difference(words[1], words[2])
+    if where is None:
+        return words
+    bucket, a = where
+    steps = []
+    for fetch in (lambda: block_keys(bucket, a), lambda: block_bits(bucket, a, steps[0])):
+        x = fetch()
+        lo, hi = x.clone(), x.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+        lo, hi = lo.cpu(), hi.cpu()
+        at = first_difference(lo, hi)
+        if at is None:                        # (the level above differed, this one does not: the state changed between the two reads)
+            raise RuntimeError("optimizer state differs between data-parallel replicas: the digest of %s in bucket %d differs, but the %s "
+                               "it was made of are the same everywhere (the state changed under the audit?)"
+                               % (AUDIT_ARRAYS[a], bucket, "elements of block %d" % steps[0] if steps else "block keys"))
+        steps.append(at)
+    index = steps[0] * AUDIT_BLOCK + steps[1]
+    parameter, element = locate(bucket, index)
+    raise RuntimeError(replica_mismatch_message(AUDIT_ARRAYS[a], bucket, parameter, element, int(lo[steps[1]]), int(hi[steps[1]])))
+
+
 class FlatAdam(object):
     """The optimizer step AND the data-parallel gradient exchange over FLAT buckets (the reference: apex FusedAdam through
     amp_C.multi_tensor_apply on fp32 masters, fp16/fp16.py:332-354,420-474; global-norm clip via amp_C.multi_tensor_l2norm, mpu/grads.py:74-127;
@@ -113,10 +183,14 @@ class FlatAdam(object):
     INVARIANT: replicas need no collective to agree on the verdict.  After `finish()` every rank holds the same gradient buckets -- the
     all-reduced bucket contents and the all-reduced late-contribution buffers added to them -- and the norm is summed in a fixed order
     (block partials in index order, buckets in launch order), so every rank computes the same bits of the norm and reaches the same
-    verdict in the same step.  Whatever one rank's backward produced, NaN included, has reached every rank through the exchange."""
+    verdict in the same step.  Whatever one rank's backward produced, NaN included, has reached every rank through the exchange.
+
+    `audit()` (--audit-optimizer-state-interval) checks what the paragraphs above claim: one streaming launch per bucket
+    digests the bits of masters and moments and counts what can never be right, two all-reduces compare the replicas' digests.
+    `audit_state=True` adds the digests to `state_dict()` and has a checkpoint load verify them; off, no launch and no key is added."""
 
     def __init__(self, module, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, clip_grad=1.0, group=None, bucket_bytes=512 << 20,
-                 exchange_dtype="bf16", skip_nonfinite=False):
+                 exchange_dtype="bf16", skip_nonfinite=False, audit_state=False):
         from emdr2_amd.model import kernels
         if exchange_dtype not in ("bf16", "fp32"):
             raise ValueError("exchange_dtype must be 'bf16' or 'fp32'")
@@ -124,6 +198,7 @@ class FlatAdam(object):
         self.exchange_dtype, self.pattern_changes = exchange_dtype, 0
         self.step_count = 0
         self.skip_nonfinite = bool(skip_nonfinite)
+        self.audit_state = bool(audit_state)  # --audit-optimizer-state-interval: state_dict() carries 'state_digest', a load verifies it
         self.names = {p: n for n, p in module.named_parameters()}         # guard_report() names the first offender's tensor
         no_decay = set(id(p) for n, p in module.named_parameters() if self.is_no_decay(n))      # model/utils.py:64-83
         self.params = [p for p in module.parameters() if p.requires_grad][::-1]
@@ -498,6 +573,87 @@ class FlatAdam(object):
             self._guard_state[4:8].zero_()
         return rep
 
+    # ---- the state audit (audit_state; include/emdr2_ops.h, "State audit") ----------------------------------------------------------------
+    def locate_element(self, bucket, index):
+        """(parameter name, element inside that tensor) of element `index` of bucket `bucket`, the way resolve_offender names one;
+        (None, index) for an index in the zero padding between two tensors."""
+        name, element = self.resolve_offender((int(bucket) << 40) | int(index))
+        return (name, element) if name is not None else (None, int(index))
+
+    def _audit_buffers(self):
+        if getattr(self, "_audit_report", None) is None:
+            dev = self.buckets[0]["master"].device
+            self._audit_report = torch.zeros((len(self.buckets), AUDIT_WORDS), dtype=torch.int64, device=dev)
+            self._audit_keys = [torch.zeros(3 * ((b["n"] + AUDIT_BLOCK - 1) // AUDIT_BLOCK), dtype=torch.int64, device=dev) for b in self.buckets]
+        return self._audit_report, self._audit_keys
+
+    def _audit_block_keys(self, bucket, a):
+        nb = self._audit_keys[bucket].numel() // 3
+        return self._audit_keys[bucket][a * nb:(a + 1) * nb]
+
+    def _audit_block_bits(self, bucket, a, block):
+        x = self.buckets[bucket][_AUDIT_BUCKET_KEY[AUDIT_ARRAYS[a]]][block * AUDIT_BLOCK:(block + 1) * AUDIT_BLOCK]
+        return x.view(torch.int32).to(torch.int64) & 0xffffffff
+
+    def audit_from_words(self, words):
+        """audit()'s dict from the host words [3, B, 18] = (this rank's, the replicas' minimum, their maximum)."""
+        local, hi = words[0], words[2]
+        out = {"elements": int(local[:, 0].sum()), "buckets": int(local.shape[0]), "world": self._world(),
+               "digests": local[:, AUDIT_DIGEST].clone(), "first": {}, "worst": {}, "worst_first": {}}
+        for c, name in enumerate(AUDIT_CHECKS):
+            out[name] = int(local[:, 1 + c].sum())
+            out["worst"][name] = int(hi[:, 1 + c].sum())
+            for key, w in (("first", local), ("worst_first", hi)):
+                bad = w[:, 1 + c].nonzero()
+                out[key][name] = self.locate_element(int(bad[0]), int(w[int(bad[0]), 6 + c]) & _U64) if bad.numel() else None
+        out["sound"] = not any(out["worst"].values())
+        return out
+
+    def audit(self, compare=True):
+        """One audit of the optimizer state: a streaming launch per bucket on the current stream (emdr2_state_audit), with world > 1 and
+        `compare` the comparison of the replicas (compare_state_replicas: two small all-reduces; a replica that differs raises the same
+        RuntimeError on every rank), ONE host read at the end.  Stale working copies (after a checkpoint load, or where an inactive
+        parameter's master was restored) are first brought up to date through work_view(p) -- the casts the next forward would run
+        anyway -- so that a mismatch means wrong bytes, not late ones.
+        -> {'elements', 'buckets', 'world', one count per AUDIT_CHECKS name summed over the buckets, 'first': {check: (parameter name,
+        element) of the first offender, (None, index into the bucket) in the padding, None when the count is 0}, 'digests': int64 [B, 6]
+        (sum, xor of master, exp_avg, exp_avg_sq per bucket), 'worst' / 'worst_first': the same counts and offenders of the worst
+        replica (the all-reduced maxima: the same on every rank), 'sound': no count is non-zero on any replica}."""
+        if not self.on_device:
+            raise _native.NativeError("the state audit runs on HIP kernels only (no host implementation)")
+        for p in self.params:
+            self.work_view(p)
+        lib, sp = _native.lib(), _native.stream_ptr()
+        report, keys = self._audit_buffers()
+        for b, k in zip(self.buckets, keys):
+            _native.check(lib.emdr2_state_audit(b["master"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), b["work"].data_ptr(), b["n"],
+                                                k.data_ptr(), report[b["idx"]].data_ptr(), sp), "state_audit")
+        if compare and self._world() > 1:
+            words = compare_state_replicas(report, self.group, self._audit_block_keys, self._audit_block_bits, self.locate_element)
+        else:
+            words = report.cpu().unsqueeze(0).expand(3, -1, -1)
+        return self.audit_from_words(words)
+
+    def state_digest(self):
+        """What state_dict() carries with audit_state: the digest words of every bucket and the bucket sizes as the layout's signature.  Not
+        collective (rank 0 alone writes a checkpoint)."""
+        return {"words": self.audit(compare=False)["digests"].tolist(), "layout": [b["n"] for b in self.buckets]}
+
+    def verify_state_digest(self, saved, log=print):
+        """After a checkpoint's model and optimizer states are in: recompute the digests and compare them with the saved ones.  A layout
+        that differs (other bucket sizes: another model or bucket_bytes) cannot be compared -- one printed line; -> whether it verified.
+        ValueError names the first bucket and array that differ."""
+        layout = [b["n"] for b in self.buckets]
+        if list(saved["layout"]) != layout:
+            log("optimizer state digest not verified: the checkpoint's buckets %s are not this run's %s" % (list(saved["layout"]), layout))
+            return False
+        mine = self.audit(compare=False)["digests"]
+        at = first_difference(torch.tensor(saved["words"], dtype=torch.int64), mine)
+        if at is not None:
+            raise ValueError("checkpoint does not hold the optimizer state it was saved from: the digest of %s in bucket %d differs "
+                             "(a torn or altered file)" % (AUDIT_ARRAYS[(at % 6) // 2], at // 6))
+        return True
+
     # ---- checkpoint format of FusedAdam (moments in parameter order) ---------------------------------------------------------------------
     def _ordered(self):
         return self.params[::-1]
@@ -511,6 +667,8 @@ class FlatAdam(object):
               'state': {i: {'exp_avg': self._moments(p)[0], 'exp_avg_sq': self._moments(p)[1]} for i, p in enumerate(self._ordered())}}
         if self.skip_nonfinite:               # (guard off: the reference-pinned layout, unchanged)
             sd['skipped_steps'] = int(self._guard_state[1])
+        if self.audit_state:                  # (audit off: the same)
+            sd['state_digest'] = self.state_digest()
         return sd
 
     def load_state_dict(self, sd):

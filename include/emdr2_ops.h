@@ -293,6 +293,37 @@ int emdr2_widen_bf16_to_f32(const void *src, float *dst, int64_t n, void *stream
 int emdr2_cast_f32_to_bf16(const float *src, void *dst, int64_t n, void *stream);
 int emdr2_accum_bf16_to_f32(const void *src, float *dst, int64_t n, float scale, void *stream);
 
+/* ---- State audit (--audit-optimizer-state-interval; not in the reference): ONE streaming pass over one flat optimizer bucket -- fp32
+ * masters, both Adam moments and the bf16 working copies, 14 bytes per element, each read exactly once -- that leaves a digest of the
+ * three fp32 arrays and five counts with their first offenders (csrc/state_audit.hip).  It writes nothing but block_keys and report.
+ * Integer folds only (sums mod 2^64, xor, min; integer atomics): the words do not depend on the grid, the workgroup order or the device.
+ * The audit states that bits are equal and that the invariants below hold; it does not state that the values are right.
+ *
+ * THE DIGEST -- fixed here; change it only for a reason written here.  It is taken over the 32-bit patterns w[i] of an array's n
+ * elements: -0.0 and +0.0 differ, and so do two NaNs with different payloads.  mix = splitmix64's finaliser (digest_mix of
+ * csrc/mips_digest.h, the function of the index digest of emdr2_mips.h), G = 0x9E3779B97F4A7C15, all sums mod 2^64:
+ *   pair p holds elements 2p and 2p + 1:     e(p) = mix((((uint64)w[2p + 1] << 32) | w[2p]) + (p + 1) * G)
+ *   block j = elements [8192 j, 8192 (j + 1)), the last one may be short; n_blocks = ceil(n / 8192):
+ *                                            key_a(j) = mix((sum of e(p) over the block's pairs) ^ ((j + 1) * G) ^ TAG_a)
+ *   TAG_a = 0x4D535452 << 32 for a = 0 master, 0x45585041 << 32 for a = 1 exp_avg (m), 0x45585053 << 32 for a = 2 exp_avg_sq (v)
+ *   block_keys[a * n_blocks + j] = key_a(j); the digest of array a = (sum over j of key_a(j), xor over j of key_a(j)).
+ * The pair's position is inside e, the block's inside the key and the array's in the tag: exchanging two pairs, two blocks or two arrays
+ * changes the digest, and one flipped bit changes exactly one key.
+ *
+ * THE REPORT: device uint64[18] (held by callers as int64 bit patterns, like the step guard's words), set by the call itself:
+ *   [0] n    [1] non-finite elements of master, [2] of m, [3] of v    [4] elements of v below zero (-Inf counts, -0.0 and NaN do not: a
+ *   second moment is a sum of squares)    [5] work_mismatch: elements whose working copy differs in bits from f2bf(master), f2bf being the
+ *   converter of csrc/prims.h that the Adam kernel and the cast kernel apply (the same function: exact for every input, NaN included)
+ *   [6..10] for each of the checks [1..5] the lowest offending index inside the bucket, all ones when there is none
+ *   [11] master sum, [12] master xor, [13] m sum, [14] m xor, [15] v sum, [16] v xor    [17] n_blocks
+ * Two launches: one wave that sets the report, then the pass -- workgroups of 256 threads, min(n_blocks, 1024) of them, a function of n
+ * alone; 16-byte loads of the fp32 arrays, 8-byte loads of the working copies.
+ * n >= 8, n % 8 == 0 (bucket slots are 8-element aligned), master / m / v 16-byte, work_bf16 / block_keys / report 8-byte aligned, none
+ * NULL: -1 otherwise, before any launch.  block_keys: emdr2_state_audit_ws_bytes(n) = 3 * n_blocks * 8 bytes. */
+int emdr2_state_audit_ws_bytes(int64_t n, size_t *bytes);
+int emdr2_state_audit(const float *master, const float *m, const float *v, const void *work_bf16, int64_t n, uint64_t *block_keys,
+                      uint64_t *report, void *stream);
+
 /* C[m, n-tile partials]: the tied LM head without the logits (language_model.py:28-41 + the log-softmax / gather of
  * train_e2eqa.py:79-96).  For x[m, n] = bf16(alpha * sum_k A[m,k] B[n,k] + bias[n]) -- the value the unfused path would have stored -- writes per
  * row m and per 64-column block j (N / 64 of them): part_max[m, j] = max_n x, part_sum[m, j] = sum_n exp(x - part_max), and gold[m] =
