@@ -121,6 +121,11 @@ SIGNATURES.update({
     # "State audit": master, m, v, work_bf16, n, block_keys, report, stream
     "emdr2_state_audit_ws_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
     "emdr2_state_audit": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # "Parameter statistics": the host-only plan (offsets, lengths, n_params, n, items, first, n_items); master, grad, m, v, n, items,
+    # n_items, first, n_params, beta1, beta2, eps, step, workspace, out, stream
+    "emdr2_param_stats_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64)]),
+    "emdr2_param_stats_ws_bytes": (_i32, [_i64, ctypes.POINTER(_sz)]),
+    "emdr2_param_stats": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _f32, _f32, _i32, _vp, _vp, _vp]),
 })
 
 

@@ -248,6 +248,16 @@ def get_parser():
                         'every rank, naming the array, the parameter and the element.  Checkpoints gain a digest that the next load '
                         'verifies.  Promised: equal bits and the invariants, not right values.  Not with --fp32-validation.  0: never, '
                         'every launch, log line and checkpoint byte is what it was')
+    g.add_argument('--log-param-stats-interval', type=int, default=0,
+                   help='(not in the reference; Megatron-LM: --log-params-norm, --log-num-zeros-in-grad) at every iteration divisible by N, '
+                        'right behind the step: per-parameter statistics of the optimizer buckets from one streaming HIP pass per bucket '
+                        '(csrc/param_stats.hip) over gradients, fp32 masters and both Adam moments, one host read.  Rank 0 prints a '
+                        'summary line (grad norm, params norm, num zeros, the clip factor, the five parameters with the largest '
+                        'lr * |d| / |w| and the five with the largest share of the squared gradient norm) and one line per group '
+                        '(a layer, or the first two name components).  The sums are added in a fixed order: replicas hold the same bits '
+                        'with no collective.  Not with --fp32-validation.  0: never, no launch, no buffer, every log line is what it was')
+    g.add_argument('--param-stats-file', type=str, default=None,
+                   help='with --log-param-stats-interval: rank 0 appends one JSON line per call with every parameter\'s record')
     return p
 
 
@@ -322,6 +332,12 @@ def parse_args(argv=None):
     if args.audit_optimizer_state_interval and args.fp32_validation:
         raise ValueError("--audit-optimizer-state-interval audits the buckets of the bf16 training path (fp32 masters against their bf16 working "
                          "copies): it does not run with --fp32-validation")
+    if args.log_param_stats_interval < 0:
+        raise ValueError("--log-param-stats-interval must be >= 0")
+    if args.log_param_stats_interval and args.fp32_validation:
+        raise ValueError("--log-param-stats-interval reads the flat buckets of the bf16 training path: it does not run with --fp32-validation")
+    if args.param_stats_file and not args.log_param_stats_interval:
+        raise ValueError("--param-stats-file needs --log-param-stats-interval (nothing is collected without it)")
     if args.context_embeddings_from_index and not args.no_context_embedder_training:
         raise ValueError("--context-embeddings-from-index needs --no-context-embedder-training (the context tower is not run, so it would "
                          "silently stop receiving gradients)")

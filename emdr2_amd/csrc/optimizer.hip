@@ -2,6 +2,7 @@
 // exchange (include/emdr2_ops.h).
 #include "../../include/emdr2_ops.h"
 #include "prims.h"
+#include "adam_bias.h"
 
 namespace {
 
@@ -214,7 +215,8 @@ extern "C" int emdr2_adam_step(float *master, const float *grad, float *m, float
                                float eps, float weight_decay, int step, const float *gnorm_sq, float clip, void *stream)
 {
     if (!master || !grad || !m || !v || n < 1 || step < 1) return -1;
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    float bc1, bc2;
+    adam_bias_corrections(beta1, beta2, step, &bc1, &bc2);
     launch(adam_kernel, grid256(n), 256, stream, master, grad, m, v, param_bf16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, gnorm_sq, clip);
     return LAUNCH_OK();
 }
@@ -225,7 +227,8 @@ static int adam_flat(float *master, const float *grad, float *m, float *v, void 
 {
     if (!master || !grad || !m || !v || n < 4 || (n & 3) || (decay_split & 3) || decay_split < 0 || decay_split > n || step < 1) return -1;
     if (((uintptr_t)master | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) & 15 || ((uintptr_t)work_bf16 & 7) || ((uintptr_t)state & 7)) return -1;
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    float bc1, bc2;
+    adam_bias_corrections(beta1, beta2, step, &bc1, &bc2);
     launch(state ? adam_flat_kernel<true> : adam_flat_kernel<false>, grid256(n / 4), 256, stream, master, grad, m, v, work_bf16, n / 4,
            decay_split / 4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, gnorm_sq, clip, state);
     return LAUNCH_OK();

@@ -1,5 +1,6 @@
 """Training-step driver of the QA task (reference: tasks/openqa/e2eqa/train_e2eqa.py:28-41,126-181 and
 megatron/training.py:165-230).  Same forward-step contract: forward_step(batch_or_iter, model) -> (loss, {'lm_loss', 'retriever_loss'})."""
+import json
 import os
 import time
 
@@ -390,6 +391,55 @@ def maybe_audit_optimizer_state(optimizer, iteration, interval):
     return True
 
 
+def param_stats_lines(stats, iteration, lr, clip):
+    """The log lines of one FlatAdam.param_stats() result: the summary -- grad norm, params norm and num zeros over all parameters (what
+    Megatron-LM logs under these names), the clip factor the step derived from that norm (min(1, clip / (norm + 1e-6)), the Adam kernel's
+    expression; 1 with clipping off), the five parameters with the largest lr * |d| / |w| (the Adam part of the last update against the
+    weights it moved) and the five with the largest share of the squared gradient norm -- then one line per group.  Pure."""
+    from emdr2_amd.training import group_param_stats
+    params = stats["params"]
+    gsq, wsq = sum(r["grad_sq"] for r in params.values()), sum(r["weight_sq"] for r in params.values())
+    gnorm = gsq ** 0.5
+    factor = min(1.0, clip / (gnorm + 1.0e-6)) if clip and clip > 0 else 1.0
+    ratio = {n: lr * r["direction_sq"] ** 0.5 / r["weight_norm"] for n, r in params.items() if r["weight_norm"] > 0}
+    moved = sorted(ratio, key=lambda n: -ratio[n])[:5]
+    share = sorted(params, key=lambda n: -params[n]["grad_sq"])[:5] if gsq > 0 else []
+    lines = [" param stats at iteration %d (step %d, gradients %s): grad norm: %.6E | params norm: %.6E | num zeros: %d | non-finite: %d | "
+             "clip factor: %.6f | largest lr*|d|/|w|: %s | largest share of grad norm^2: %s"
+             % (iteration, stats["step"], "current" if stats["grads_current"] else "not current", gnorm, wsq ** 0.5,
+                sum(r["grad_zeros"] for r in params.values()), sum(r["grad_nonfinite"] for r in params.values()), factor,
+                ", ".join("%s %.3E" % (n, ratio[n]) for n in moved) or "-",
+                ", ".join("%s %.1f%%" % (n, 100.0 * params[n]["grad_sq"] / gsq) for n in share) or "-")]
+    for name, g in group_param_stats(stats).items():
+        lines.append(" param stats group %s: %d tensors, %d elements | grad norm: %.6E | params norm: %.6E | direction rms: %.6E | "
+                     "max abs grad: %.3E | num zeros: %d | non-finite: %d"
+                     % (name, g["params"], g["n"], g["grad_norm"], g["weight_norm"], g["direction_rms"], g["max_abs_grad"], g["grad_zeros"],
+                        g["grad_nonfinite"]))
+    return lines
+
+
+def log_param_stats(optimizer, iteration, path=None):
+    """--log-param-stats-interval: one FlatAdam.param_stats() call (two launches per bucket, one host read, no collective: every rank
+    would read the same bits), the lines of param_stats_lines on rank 0 and, with --param-stats-file, one appended JSON line holding
+    every parameter's record."""
+    stats = optimizer.param_stats()
+    lr = float(getattr(optimizer, "last_lr", optimizer.lr))
+    for line in param_stats_lines(stats, iteration, lr, optimizer.clip_grad):
+        print_rank_0(line)
+    if path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
+        with open(path, "a") as f:
+            f.write(json.dumps(dict(stats, iteration=iteration, lr=lr)) + "\n")
+    return stats
+
+
+def maybe_log_param_stats(optimizer, iteration, interval, path=None):
+    """The step-boundary rule of --log-param-stats-interval: at every iteration divisible by `interval`; 0 = never.  -> whether it did."""
+    if interval <= 0 or iteration % interval:
+        return False
+    log_param_stats(optimizer, iteration, path)
+    return True
+
+
 def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_of_epoch_callback, end_of_epoch_callback2, eos_id, indexer=None):
     """train_e2eqa.py:413-552.  `indexer`: an AsyncIndexBuilder when --async-indexer (re-indexing on a side stream; the swap at a step
     boundary replaces the NEW_INDEX_READY / NEW_CHKPT_READY handshake and the reload from disk)."""
@@ -443,6 +493,7 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
     state_audit_interval = int(getattr(args, "audit_optimizer_state_interval", 0) or 0)
     if state_audit_interval > 0:
         audit_optimizer_state(optimizer, args.iteration)          # what was initialised or loaded, before the first step runs on it
+    param_stats_interval = int(getattr(args, "log_param_stats_interval", 0) or 0)
     stamped = getattr(getattr(model, "evidence_retriever", None), "mips_index", None) if getattr(args, "index_generations", False) else None
     newest_wins = bool(getattr(args, "index_newest_wins", False))
     hit_tracker = getattr(model, "answer_hits", None)        # --retrieval-answer-hits
@@ -472,6 +523,9 @@ def _train(model, optimizer, lr_scheduler, forward_step, train_dataloader, end_o
             if state_audit_interval > 0:
                 # right behind the step, before any checkpoint save of this boundary: a state that fails is never saved
                 maybe_audit_optimizer_state(optimizer, iteration, state_audit_interval)
+            if param_stats_interval > 0:
+                # behind the step and the audit, while the buckets still hold this step's gradient (until the next zero_grad())
+                maybe_log_param_stats(optimizer, iteration, param_stats_interval, getattr(args, "param_stats_file", None))
             if hit_tracker is not None:
                 hit_tracker.commit()
             if read_meter is not None:

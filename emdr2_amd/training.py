@@ -145,6 +145,39 @@ def compare_state_replicas(report, group=None, block_keys=None, block_bits=None,
     raise RuntimeError(replica_mismatch_message(AUDIT_ARRAYS[a], bucket, parameter, element, int(lo[steps[1]]), int(hi[steps[1]])))
 
 
+# ---- parameter statistics (include/emdr2_ops.h, "Parameter statistics"; FlatAdam.param_stats) ------------------------------------------------
+PARAM_STATS_WORDS = 8                         # uint64 words per parameter, held as int64 bit patterns
+PARAM_STATS_LR_NOTE = ("direction_rms is the root mean square of d = (m / bc1) / (sqrt(v / bc2) + eps): the Adam part of the last applied update "
+                       "without the learning rate and without the weight decay; the update's size is lr * direction")
+
+
+def param_stats_group(name):
+    """The group of a parameter name: up to and including 'layers.<i>' where the name has one, the first two components otherwise."""
+    parts = name.split(".")
+    for i in range(len(parts) - 1):
+        if parts[i] == "layers" and parts[i + 1].isdigit():
+            return ".".join(parts[:i + 2])
+    return ".".join(parts[:2])
+
+
+def group_param_stats(stats):
+    """FlatAdam.param_stats()'s result (or its 'params' dict) per group (param_stats_group), in the order the groups first appear: the
+    squared sums and the counts added up, the maxima taken, and from them 'grad_norm', 'weight_norm', 'direction_rms'; 'params' counts
+    the group's tensors.  Pure: no device, no collective."""
+    groups = {}
+    for name, r in stats.get("params", stats).items():
+        g = groups.setdefault(param_stats_group(name), {"params": 0, "n": 0, "grad_sq": 0.0, "weight_sq": 0.0, "direction_sq": 0.0, "grad_zeros": 0,
+                                                        "grad_nonfinite": 0, "max_abs_grad": 0.0, "max_abs_weight": 0.0})
+        g["params"] += 1
+        for k in ("n", "grad_sq", "weight_sq", "direction_sq", "grad_zeros", "grad_nonfinite"):
+            g[k] += r[k]
+        for k in ("max_abs_grad", "max_abs_weight"):
+            g[k] = max(g[k], r[k])
+    for g in groups.values():
+        g["grad_norm"], g["weight_norm"], g["direction_rms"] = g["grad_sq"] ** 0.5, g["weight_sq"] ** 0.5, (g["direction_sq"] / g["n"]) ** 0.5
+    return groups
+
+
 class FlatAdam(object):
     """The optimizer step AND the data-parallel gradient exchange over FLAT buckets (the reference: apex FusedAdam through
     amp_C.multi_tensor_apply on fp32 masters, fp16/fp16.py:332-354,420-474; global-norm clip via amp_C.multi_tensor_l2norm, mpu/grads.py:74-127;
@@ -187,7 +220,12 @@ class FlatAdam(object):
 
     `audit()` (--audit-optimizer-state-interval) checks what the paragraphs above claim: one streaming launch per bucket
     digests the bits of masters and moments and counts what can never be right, two all-reduces compare the replicas' digests.
-    `audit_state=True` adds the digests to `state_dict()` and has a checkpoint load verify them; off, no launch and no key is added."""
+    `audit_state=True` adds the digests to `state_dict()` and has a checkpoint load verify them; off, no launch and no key is added.
+
+    `param_stats()` (--log-param-stats-interval) is the view into the buckets: per parameter the norms of its gradient, its
+    weights and its Adam direction, both maxima, the zero and the non-finite gradient elements -- one streaming launch and one small fold
+    launch per bucket, one host read.  The sums are added in a fixed order, so replicas agree bit for bit with no collective, for the
+    reason the INVARIANT above gives.  Never called: no launch and no buffer."""
 
     def __init__(self, module, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, clip_grad=1.0, group=None, bucket_bytes=512 << 20,
                  exchange_dtype="bf16", skip_nonfinite=False, audit_state=False):
@@ -323,6 +361,7 @@ class FlatAdam(object):
 
     def begin_step(self):
         self._stale = False
+        self._grads_current = False           # param_stats(): the buckets no longer hold the gradient of step `step_count`
         self._ensure_exchange_buffers()
         for b in self.buckets:
             b["grad"].zero_()                 # ONE fill per bucket: the producing kernels accumulate straight into their slices (accumulation_target)
@@ -481,9 +520,11 @@ class FlatAdam(object):
             raise _native.NativeError("the optimizer step runs on HIP kernels only (no host implementation)")
         lib, sp = _native.lib(), _native.stream_ptr()
         lr = self.lr if lr is None else lr
+        self.last_lr = lr                     # the rate of the last update: what turns param_stats()'s direction into an update size
         if self.expected is None:
             self.finish()                                          # single-process use without an explicit finish()
         self.step_count += 1
+        self._grads_current = True            # until the next begin_step(): what param_stats() reads is this step's gradient
         active = [b for b in self.buckets if any(self.count[p] for p in b["params"])]
         guarded = self.skip_nonfinite
         if not active:
@@ -653,6 +694,70 @@ class FlatAdam(object):
             raise ValueError("checkpoint does not hold the optimizer state it was saved from: the digest of %s in bucket %d differs "
                              "(a torn or altered file)" % (AUDIT_ARRAYS[(at % 6) // 2], at // 6))
         return True
+
+    # ---- parameter statistics (include/emdr2_ops.h, "Parameter statistics") -------------------------------------------------------------
+    def _param_stats_buffers(self):
+        """The plan of every bucket (emdr2_param_stats_plan, built once; the device copies are kept), one workspace for the largest
+        bucket -- the launches of a call are ordered on one stream -- and the [P, 8] table, its rows in bucket order."""
+        if getattr(self, "_pstats", None) is None:
+            import ctypes
+            lib, dev = _native.lib(), self.buckets[0]["master"].device
+            plans, rows, most = [], 0, 0
+            for b in self.buckets:
+                offs = torch.tensor([self.slot[p][1] for p in b["params"]], dtype=torch.int64)
+                lens = torch.tensor([self.slot[p][2] for p in b["params"]], dtype=torch.int64)
+                first, count = torch.zeros(len(b["params"]) + 1, dtype=torch.int64), ctypes.c_int64()
+                _native.check(lib.emdr2_param_stats_plan(offs.data_ptr(), lens.data_ptr(), len(b["params"]), b["n"], None, first.data_ptr(),
+                                                         ctypes.byref(count)), "param_stats_plan")
+                items = torch.zeros((count.value, 2), dtype=torch.int64)
+                _native.check(lib.emdr2_param_stats_plan(offs.data_ptr(), lens.data_ptr(), len(b["params"]), b["n"], items.data_ptr(),
+                                                         first.data_ptr(), ctypes.byref(count)), "param_stats_plan")
+                plans.append({"items": items.to(dev), "first": first.to(dev), "n_items": count.value, "row": rows})
+                rows, most = rows + len(b["params"]), max(most, count.value)
+            size = ctypes.c_size_t()
+            _native.check(lib.emdr2_param_stats_ws_bytes(most, ctypes.byref(size)), "param_stats_ws_bytes")
+            self._pstats = (plans, torch.zeros(size.value // 8, dtype=torch.int64, device=dev),
+                            torch.zeros((rows, PARAM_STATS_WORDS), dtype=torch.int64, device=dev))
+        return self._pstats
+
+    def param_stats_words(self):
+        """The launches of param_stats() without its host read: int64 [P, 8] on the device (uint64 words as bit patterns), the rows in
+        bucket order, inside a bucket in slot order -- `param_stats_order()` names them."""
+        if not self.on_device:
+            raise _native.NativeError("the parameter statistics run on HIP kernels only (no host implementation)")
+        lib, sp = _native.lib(), _native.stream_ptr()
+        plans, ws, table = self._param_stats_buffers()
+        for b, pl in zip(self.buckets, plans):
+            _native.check(lib.emdr2_param_stats(b["master"].data_ptr(), b["grad"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), b["n"],
+                                                pl["items"].data_ptr(), pl["n_items"], pl["first"].data_ptr(), len(b["params"]),
+                                                self.betas[0], self.betas[1], self.eps, self.step_count, ws.data_ptr(),
+                                                table[pl["row"]].data_ptr(), sp), "param_stats")
+        return table
+
+    def param_stats_order(self):
+        return [p for b in self.buckets for p in b["params"]]
+
+    def param_stats(self):
+        """Per-parameter statistics of the buckets as they lie: two launches per bucket on the current stream (emdr2_param_stats), ONE
+        host read of the [P, 8] table.  No collective: after finish() every replica holds the same buckets and the sums have a fixed
+        order, so every replica reads the same bits.
+        -> {'step': step_count, 'grads_current': whether the buckets still hold the gradient of that step (between step() and the next
+        begin_step() / zero_grad(); otherwise the gradient sums are those of zeros or of a step under way), 'lr_note', 'params': {name:
+        {'n', 'grad_norm', 'weight_norm', 'direction_rms' = sqrt(sum d^2 / n), 'max_abs_grad', 'max_abs_weight', 'grad_zeros',
+        'grad_nonfinite', 'active': the parameter received a contribution (count > 0), and the three sums themselves: 'grad_sq',
+        'weight_sq', 'direction_sq'}}}.  The gradient is the unclipped one; d is the Adam part of the last applied update."""
+        words = self.param_stats_words().cpu().numpy()                   # the call's one host read
+        sums = words[:, :3].copy().view("float64")
+        maxima = (words[:, 3:5] & 0xffffffff).astype("uint32").view("float32")
+        params = {}
+        for row, p in enumerate(self.param_stats_order()):
+            n = int(words[row, 7])
+            params[self.names.get(p, "param%d" % row)] = {
+                "n": n, "grad_norm": float(sums[row, 0]) ** 0.5, "weight_norm": float(sums[row, 1]) ** 0.5,
+                "direction_rms": (float(sums[row, 2]) / n) ** 0.5, "max_abs_grad": float(maxima[row, 0]), "max_abs_weight": float(maxima[row, 1]),
+                "grad_zeros": int(words[row, 5]), "grad_nonfinite": int(words[row, 6]), "active": self.count[p] > 0,
+                "grad_sq": float(sums[row, 0]), "weight_sq": float(sums[row, 1]), "direction_sq": float(sums[row, 2])}
+        return {"step": self.step_count, "grads_current": bool(self._grads_current), "lr_note": PARAM_STATS_LR_NOTE, "params": params}
 
     # ---- checkpoint format of FusedAdam (moments in parameter order) ---------------------------------------------------------------------
     def _ordered(self):

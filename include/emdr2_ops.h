@@ -324,6 +324,49 @@ int emdr2_state_audit_ws_bytes(int64_t n, size_t *bytes);
 int emdr2_state_audit(const float *master, const float *m, const float *v, const void *work_bf16, int64_t n, uint64_t *block_keys,
                       uint64_t *report, void *stream);
 
+/* ---- Parameter statistics (--log-param-stats-interval; Megatron-LM: --log-params-norm, --log-num-zeros-in-grad): ONE streaming pass over
+ * one flat optimizer bucket -- fp32 gradients, masters and both Adam moments, 16 bytes per element, each read exactly once -- that leaves
+ * eight words for EVERY parameter of the bucket (csrc/param_stats.hip).  It writes nothing but workspace and out.  No atomics: every
+ * floating-point addition happens in the order stated below, so data-parallel replicas, which hold the same buckets after the gradient
+ * exchange, get the same bits with no collective.
+ *
+ * THE PLAN (emdr2_param_stats_plan: host only, touches no GPU; the one place where the chunk rule lives).  A bucket of n elements is
+ * described by its parameters' element offsets and lengths: offsets multiples of 8 (FlatAdam's slot alignment), ascending, not
+ * overlapping, length >= 1, offset + length <= n, n >= 8 and n % 8 == 0, n_params >= 1 -- anything else returns -1.  Parameter p is cut into
+ * chunks of PARAM_STATS_CHUNK = 8192 elements from ITS OWN start, the last one may be short; a chunk is an ITEM.
+ *   items: int64 [n_items, 2] = (first element inside the bucket, length), parameter after parameter, chunks ascending; NULL: only count
+ *   first: int64 [n_params + 1], first[p] = index of parameter p's first item, first[n_params] = n_items (never NULL)
+ * The padding between two tensors belongs to no item and never reaches a result.
+ *
+ * THE WORDS: out is uint64 [n_params, 8], every word written by the call; the workspace holds one record of the same eight words per item
+ * (emdr2_param_stats_ws_bytes(n_items) = n_items * 64 bytes).
+ *   [0] sum g^2 as float64 bits (the gradient as it lies in the bucket: unclipped)    [1] sum w^2 as float64 bits (fp32 masters)
+ *   [2] sum d^2 as float64 bits, d = (m / bc1) / (sqrtf(v / bc2) + eps) evaluated in fp32, statement for statement the Adam kernel's
+ *       (csrc/optimizer.hip, adam_flat_kernel), bc1 = 1 - powf(beta1, step), bc2 = 1 - powf(beta2, step) from the function the Adam entries
+ *       call (csrc/adam_bias.h): the Adam part of the last applied update without the learning rate.  step == 0: 0, m and v are not read
+ *   [3] max |g|, [4] max |w|: the fp32 bit pattern of the absolute value in the low 32 bits, compared as integers; NaN elements are left
+ *       out, Inf elements counted in (0x7f800000)
+ *   [5] gradient elements equal to +-0 (denormals are not zeros)    [6] non-finite gradient elements    [7] the parameter's element count
+ *
+ * THE ORDER of the additions -- fixed here; change it only for a reason written here.  Squares are formed and added in double (the square
+ * of an fp32 value is exact in double, so only the order counts).
+ *   1. First launch, 256 threads, min(n_items, 1024) workgroups (a function of the plan alone); workgroup g takes items g, g + grid, ...
+ *      Thread t takes the 4-element groups t, t + 256, ... of the item (one 16-byte load per array) and adds into its own sums from 0.0:
+ *      groups ascending, elements ascending; elements at or beyond the item's end are masked out one by one
+ *   2. the xor butterfly over the 64 lanes of a wave, x += x[lane ^ o] for o = 32, 16, 8, 4, 2, 1
+ *   3. the four waves through LDS: (w0 + w1) + (w2 + w3).  That is the item's record
+ *   4. Second launch, one wave per parameter: lane group s = 0 .. 7 adds, from 0.0, the records of the parameter's items s, s + 8, ... in
+ *      ascending order; then the xor butterfly over the groups, x += x[s ^ o] for o = 4, 2, 1
+ * Maxima and counts are integer folds along the same paths.
+ * Null pointers, master / grad / m / v not 16-byte or items / first / workspace / out not 8-byte aligned, n < 8, n % 8, n_items < 1,
+ * n_params < 1, n_params > n_items, step < 0: -1 before any launch.  items and first are DEVICE copies of the plan. */
+int emdr2_param_stats_plan(const int64_t *offsets, const int64_t *lengths, int64_t n_params, int64_t n, int64_t *items, int64_t *first,
+                           int64_t *n_items);
+int emdr2_param_stats_ws_bytes(int64_t n_items, size_t *bytes);
+int emdr2_param_stats(const float *master, const float *grad, const float *m, const float *v, int64_t n, const int64_t *items, int64_t n_items,
+                      const int64_t *first, int64_t n_params, float beta1, float beta2, float eps, int step, uint64_t *workspace, uint64_t *out,
+                      void *stream);
+
 /* C[m, n-tile partials]: the tied LM head without the logits (language_model.py:28-41 + the log-softmax / gather of
  * train_e2eqa.py:79-96).  For x[m, n] = bf16(alpha * sum_k A[m,k] B[n,k] + bias[n]) -- the value the unfused path would have stored -- writes per
  * row m and per 64-column block j (N / 64 of them): part_max[m, j] = max_n x, part_sum[m, j] = sum_n exp(x - part_max), and gold[m] =
